@@ -16,6 +16,10 @@ from ONE process through training.platform.gpu_ids, the reference's nn.DataParal
 
 One JSON line on rank 0.  `roofline` is measured live: every launch of the conv kernels is bracketed by HIP events on the
 launch stream inside the timed region; achieved = algorithmic FLOPs of those launches / their summed duration.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` then also writes what the last timed
+step returned (belief maps + keypoints, or the loss in training) as DIR/<name>.npy.  `--full` adds the blocks below, each of which
+takes runs of its own:
   * N == 1: `secondary` = the other single-GPU configurations of BASELINE.json under the same clock: configs[2] (vgg_q
     training b=128) and one GPU's share of configs[3] (resnet_h training, 16 frames) and configs[4] (resnet_f inference, 32
     frames), two timed steps each, every one with its executed-multiplication roofline fraction; `cpu_baseline` times the CPU
@@ -60,6 +64,10 @@ def parse():
     ap.add_argument("--precision", choices=["fp32", "fp16x3"], default="fp32",
                     help="conv kernel for inference: exact fp32 MFMA, or split-precision fp16x3 (fp32 in/out, fp32-class error)")
     ap.add_argument("--arch", choices=["vgg_q", "vgg_f", "resnet_h", "resnet_f"], default="vgg_q")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the `secondary` (N = 1) / `scale` (N > 1) blocks of the "
+                    "other BASELINE.json configurations and the `cpu_baseline` block (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned as "
+                    "DIR/<name>.npy (float32; at most 64 MB in all, a fixed seeded sample of the frames beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="inference through DreamNetwork.hip_graph (hipGraph replay; "
                     "per-launch HIP events are not recorded then)")
@@ -589,6 +597,29 @@ def dp_check(ctx, net):
             "param_l2": float(flat.double().norm()), "ranks": ctx.world}
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, mode, directory):
+    """--dump-outputs: what a caller of the timed path received from its last step, as DIR/<name>.npy in float32 -- the belief maps
+    [B,K,H,W] and the keypoints [B,K,2] of an inference step, the loss of a training step.  Beyond DUMP_BYTES in all, the same fixed
+    seeded sample of the frames is kept from every array (their indices in sampled_frames.npy).  -> the names written."""
+    import numpy as np
+    named = [("loss", out)] if mode == "train" else [("belief_maps", out[0]), ("keypoints", out[1])]
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in named}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        frames = arrays["belief_maps"].shape[0]
+        keep = max(1, frames * (DUMP_BYTES - 2 ** 16) // (total + 8 * frames))      # room for the headers and the indices
+        idx = np.sort(np.random.default_rng(0).choice(frames, keep, replace=False))
+        arrays = {n: np.ascontiguousarray(a[idx]) for n, a in arrays.items()}
+        arrays["sampled_frames"] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(directory, n + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     """A failure (RCCL initialisation on a multi-GPU node, a device that is missing ...) leaves ONE JSON line with an `error` field (from
     the rank that failed) and a non-zero exit status instead of N interleaved tracebacks, so that a SCALE record is diagnosable."""
@@ -665,6 +696,9 @@ def _main(args, stage):
     dt, conv, out_main = timed_region(ctx, net, x, tgt, spec)
     main_rank_seconds = list(ctx.rank_seconds)
     main_step_ms = ctx.step_ms
+    if args.dump_outputs and ctx.rank == 0 and out_main is not None:
+        stage[0] = "writing the outputs (--dump-outputs)"
+        dump_outputs(out_main, args.mode, args.dump_outputs)
     check = dp_check(ctx, net) if spec["dp_check"] else None
     stage[0] = "reporting"
     # roofline peak: the fp32 MFMA rate for the exact kernel; for the split kernel every algorithmic MAC costs three
@@ -701,7 +735,7 @@ def _main(args, stage):
     side = None
     default_main = (args.arch, args.mode, args.res, args.precision, args.conv_algorithm) == ("vgg_q", "inference", 400, "fp32", "winograd") \
         and not args.global_batch and not args.graph
-    if default_main and not args.no_secondary:
+    if default_main and args.full and not args.no_secondary:
         base = {"res": 400, "steps": args.secondary_steps, "warmup": 1, "precision": "fp32", "conv_algorithm": "winograd"}
         # a training step is in its steady state from the third on (the first records which packed weight copies it builds, the
         # second builds the one-launch packing table: models._repack_weights)
@@ -757,7 +791,7 @@ def _main(args, stage):
             line["dp_check"] = check
         if side:
             line["secondary" if ctx.n_gpus == 1 else "scale"] = side
-        if ctx.world == 1 and not ctx.single and not args.no_cpu_baseline and args.mode == "inference":
+        if args.full and ctx.world == 1 and not ctx.single and not args.no_cpu_baseline and args.mode == "inference":
             line["cpu_baseline"] = cpu_baseline(args.arch, args.res, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

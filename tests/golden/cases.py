@@ -1,6 +1,9 @@
 """Seeded synthetic inputs shared by make_golden.py (dev container, runs the real reference) and
 by the test-suite (dev container + GPU box, compares oracle / HIP path with the stored outputs).
 Pure NumPy: the same seeds give the same bytes everywhere."""
+import glob
+import os
+
 import numpy as np
 
 
@@ -163,6 +166,46 @@ STRUCTURED_MIN_REJECTIONS = {"vgg_q_400": 2, "vgg_f": 2, "resnet_h": 2}
 # (vgg_f_recipe: 0 -- the recipe weights give every full-resolution map several comparable peaks, all rejected by the 0.25 rule; the case
 # is there for the MAP values, which every tap of every layer and every transposed-conv phase feeds asymmetrically)
 STRUCTURED_MIN_DETECTIONS = {"vgg_q_400": 0.7, "vgg_f": 0.55, "resnet_h": 0.64, "vgg_f_recipe": 0.0}
+
+
+FIXTURE_BYTES = 1 << 20          # largest committed file
+
+
+def save_structured(golden_dir, case, maps, **arrays):
+    """structured_<case>.npz.  Where one file would be larger than FIXTURE_BYTES, the maps go into structured_<case>.maps<i>.npz
+    instead, split along the keypoint axis into as few parts as keep every file under the limit (load_structured joins them)."""
+    base = os.path.join(golden_dir, "structured_%s" % case)
+    for f in [base + ".npz"] + sorted(glob.glob(base + ".maps*.npz")):
+        os.remove(f)
+    np.savez_compressed(base + ".npz", maps=maps, **arrays)
+    if os.path.getsize(base + ".npz") <= FIXTURE_BYTES:
+        return [base + ".npz"]
+    np.savez_compressed(base + ".npz", **arrays)
+    for n in range(2, maps.shape[1] + 1):
+        parts = ["%s.maps%d.npz" % (base, i) for i in range(n)]
+        for p, m in zip(parts, np.array_split(maps, n, axis=1)):
+            np.savez_compressed(p, maps=m)
+        if all(os.path.getsize(p) <= FIXTURE_BYTES for p in parts):
+            return [base + ".npz"] + parts
+        for p in parts:
+            os.remove(p)
+    raise AssertionError("structured_%s: one keypoint's maps do not fit in %d bytes" % (case, FIXTURE_BYTES))
+
+
+def load_structured(golden_dir, case):
+    """The arrays of a structured fixture (save_structured), the maps joined from their parts where they are split."""
+    base = os.path.join(golden_dir, "structured_%s" % case)
+    with np.load(base + ".npz") as g:
+        out = {k: g[k] for k in g.files}
+    if "maps" not in out:
+        parts, i = [], 0
+        while os.path.exists("%s.maps%d.npz" % (base, i)):
+            with np.load("%s.maps%d.npz" % (base, i)) as g:
+                parts.append(g["maps"])
+            i += 1
+        assert parts, "structured_%s: no maps stored" % case
+        out["maps"] = np.concatenate(parts, axis=1)
+    return out
 
 
 def structured_input(case):

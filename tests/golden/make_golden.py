@@ -10,7 +10,8 @@ Fixtures are data only (inputs are regenerated from seeds by cases.py; outputs a
   variant_<name>.npz    G7     skip / full_output / soft-argmax / multi-stage hourglasses (--only-variants)
   belief_map_golden.npz G10    create_belief_map (--only-belief-maps)
   peak_rule_golden.npz  G12    selection rule with use_belief_peak_scores / belief_peak_next_best_score changed (--only-peak-rules)
-  structured_<arch>.npz G11    blob-like O(1) belief maps end to end: maps, keypoints, calibrated last layer (--only-structured)
+  structured_<arch>.npz G11    blob-like O(1) belief maps end to end: maps, keypoints, calibrated last layer (--only-structured);
+                               maps too large for one file in structured_<arch>.maps<i>.npz (cases.save_structured)
 """
 import json
 import os
@@ -241,8 +242,8 @@ def structured(dream):
                 break
         else:
             raise AssertionError("no channel mix gave a balanced fixture whose decisions are stable under +-1e-4")
-        np.savez_compressed(os.path.join(HERE, "structured_%s.npz" % case), maps=maps, keypoints=kps, centres=centres,
-                            final_weight=w[wk].numpy(), final_bias=w[bk].numpy())
+        cases.save_structured(HERE, case, maps, keypoints=kps, centres=centres,
+                              final_weight=w[wk].numpy(), final_bias=w[bk].numpy())
 
 
 def grad_sample(t, n=64):

@@ -630,7 +630,7 @@ def check_structured(dev, arch, precision="fp32", repeat=1):
     (the BASELINE batch sizes: the algorithm selection and the grids of the benchmarked configuration), EVERY copy held to the bounds."""
     case = arch
     arch, manip, k, last, (b, h, w), recipe, zero_bg = cases.STRUCTURED_CASES[case]
-    g = np.load(os.path.join(GOLD, "structured_%s.npz" % case))
+    g = cases.load_structured(GOLD, case)
     sd = om.build_model(arch, k).state_dict()
     weights = {"structured": om.structured_weights, "smooth": om.smooth_weights, "recipe": om.recipe_weights}[recipe](sd)
     weights[last + ".weight"] = torch.from_numpy(g["final_weight"])

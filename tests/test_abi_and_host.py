@@ -196,6 +196,42 @@ def test_bench_leaves_one_json_error_line_without_a_gpu():
     assert line["value"] is None and "needs a GPU" in line["error"] and line["n_gpus"] == 1
 
 
+def test_bench_plain_run_and_its_options(monkeypatch):
+    """bench.py: the blocks beyond the headline (secondary / scale, cpu_baseline) only with --full; --dump-outputs takes a directory."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_float32_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: what the last step returned, as <name>.npy in float32; beyond the byte budget the same seeded sample
+    of the frames from every array, the same from run to run, the files within the budget."""
+    import numpy as np
+    import bench
+    maps, kps = torch.rand(64, 3, 16, 16, dtype=torch.float64), torch.rand(64, 3, 2)
+    assert bench.dump_outputs([maps, kps], "inference", str(tmp_path / "all")) == ["belief_maps", "keypoints"]
+    got = np.load(tmp_path / "all" / "belief_maps.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, maps.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "keypoints.npy"), kps.numpy())
+    assert bench.dump_outputs(torch.tensor(0.25), "train", str(tmp_path / "train")) == ["loss"]
+    assert np.load(tmp_path / "train" / "loss.npy") == np.float32(0.25)
+    budget = 2 ** 16 + 100000
+    monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs([maps, kps], "inference", str(tmp_path / d)) == ["belief_maps", "keypoints", "sampled_frames"]
+        assert sum(os.path.getsize(tmp_path / d / n) for n in os.listdir(tmp_path / d)) <= budget
+    idx = np.load(tmp_path / "s1" / "sampled_frames.npy")
+    assert idx.dtype == np.float64 and 1 < len(idx) < 64 and np.array_equal(idx, np.load(tmp_path / "s2" / "sampled_frames.npy"))
+    rows = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "belief_maps.npy"), maps.float().numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "keypoints.npy"), kps.numpy()[rows])
+
+
 def test_deferred_side_hands_the_leaves_over_in_segments(monkeypatch):
     """models._DeferredSide (a backward captured as a sequence of graphs, DREAM_TRAIN_GRAPH_SPLIT): leaves are not run where they are
     queued but handed to the capture controller every `leaves` of them, in order, and the rest at join(); their inputs stay

@@ -63,7 +63,7 @@ def test_structured_fixture_regenerates_from_the_oracle(arch):
     oracle reproduces the reference's maps / keypoints -- on any box, without the reference."""
     case = arch
     arch, manip, k, last, (b, h, w), recipe, zero_bg = cases.STRUCTURED_CASES[case]
-    g = np.load(os.path.join(GOLD, "structured_%s.npz" % case))
+    g = cases.load_structured(GOLD, case)
     m = om.build_model(arch, k)
     wts = {"structured": om.structured_weights, "smooth": om.smooth_weights, "recipe": om.recipe_weights}[recipe](m.state_dict())
     wts[last + ".weight"], wts[last + ".bias"] = torch.from_numpy(g["final_weight"]), torch.from_numpy(g["final_bias"])

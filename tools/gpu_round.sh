@@ -462,7 +462,7 @@ rehearse8)
   # Round 6, verdict task 7: both multi-GPU paths at the REAL rank count (8) on the one GPU of the box -- the numbers mean nothing, the
   # code path (self-launch under torch.distributed.run, 8 ranks, the `scale` block with configs[3] 8 x 16 frames and configs[4] 8 x 32 frames
   # at K = 17; 8 replicas in one process, split graphs, one exchange) is what the first 8-GPU node will run.
-  DREAM_BENCH_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --steps 2 --warmup 1 --secondary-steps 2 --secondary-train-steps 3 > $O/rehearsal_8ranks_gloo.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_8ranks_gloo.log | cut -c1-600
+  DREAM_BENCH_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --steps 2 --warmup 1 --full --secondary-steps 2 --secondary-train-steps 3 > $O/rehearsal_8ranks_gloo.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_8ranks_gloo.log | cut -c1-600
   DREAM_BENCH_GPU_IDS=0,0,0,0,0,0,0,0 timeout 900 python bench.py --gpus 8 --single-process --arch resnet_h --mode train --steps 4 --warmup 3 --global-batch 128 --no-cpu-baseline > $O/rehearsal_single_process_8replicas_train.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_single_process_8replicas_train.log | cut -c1-600
   DREAM_BENCH_GPU_IDS=0,0,0,0,0,0,0,0 timeout 900 python bench.py --gpus 8 --single-process --arch resnet_f --steps 3 --warmup 2 --global-batch 256 --no-cpu-baseline > $O/rehearsal_single_process_8replicas_infer.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_single_process_8replicas_infer.log | cut -c1-600
   ;;
@@ -782,7 +782,7 @@ final)
     echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $O/smoke.log | cut -c1-60,100-190
   fi
   echo "== rehearsals on this one GPU (the numbers mean nothing)"
-  DREAM_BENCH_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --steps 2 --warmup 1 --secondary-steps 2 --secondary-train-steps 3 > $O/rehearsal_8ranks_gloo.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_8ranks_gloo.log | cut -c1-60,100-190
+  DREAM_BENCH_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --steps 2 --warmup 1 --full --secondary-steps 2 --secondary-train-steps 3 > $O/rehearsal_8ranks_gloo.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_8ranks_gloo.log | cut -c1-60,100-190
   DREAM_BENCH_GPU_IDS=0,0,0,0,0,0,0,0 timeout 900 python bench.py --gpus 8 --single-process --arch resnet_h --mode train --steps 4 --warmup 3 --global-batch 128 --no-cpu-baseline > $O/rehearsal_single_process_8replicas_train.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_single_process_8replicas_train.log | cut -c1-60,100-190
   DREAM_BENCH_GPU_IDS=0,0,0,0 timeout 600 python bench.py --gpus 4 --single-process --arch resnet_h --mode train --steps 6 --warmup 3 --global-batch 64 --no-cpu-baseline > $O/rehearsal_single_process_4replicas_train.log 2>&1; echo "rc=$?"; tail -1 $O/rehearsal_single_process_4replicas_train.log | cut -c1-60,100-190
   echo "== rocprof default bench (kernel trace)"; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$R/$O/prof_default" -o dflt -- python "$R/bench.py" --no-cpu-baseline --no-secondary > "$R/$O/rocprof_default.log" 2>&1); echo "rc=$?"; grep -h '^{"metric' $O/rocprof_default.log | cut -c1-60,100-190
@@ -841,7 +841,7 @@ for k,v in d.items(): print(k, {a: round(b,3) for a,b in v.items() if a in ('mfm
   timeout 400 python tools/wgw_diag.py run --batch 128 2>&1 | grep -v "Warning\|amdgpu.ids" > $O/wgw_diag.txt; tail -4 $O/wgw_diag.txt | cut -c1-300
   cp $O/pmc_traffic.json profiles/r06_pmc_traffic.json
   cp $O/pmc_traffic_resnet_train.json profiles/r06_pmc_traffic_resnet_train.json
-  echo "== default bench (with the PMC traffic of this bench.py)"; T0=$SECONDS; timeout 1200 python bench.py > $O/bench_default.log 2> $O/bench_default.err; tail -1 $O/bench_default.log | cut -c1-2400; echo "$((SECONDS - T0)) s wall"
+  echo "== default bench (with the PMC traffic of this bench.py)"; T0=$SECONDS; timeout 1200 python bench.py --full > $O/bench_default.log 2> $O/bench_default.err; tail -1 $O/bench_default.log | cut -c1-2400; echo "$((SECONDS - T0)) s wall"
   du -sh $O
   ;;
 collect)
