@@ -152,6 +152,7 @@ _SIGNATURES = {
     "dream_loss_workspace": (_SZ, [_SZ]),
     "dream_mse_fwd_bwd_f32": (_I, [_P, _P, _P, _P, _P, _SZ, _D, _P]),
     "dream_normalize_u8_hwc_to_chw_f32": (_I, [_P, _P, _I, _I, _I, _c.POINTER(_F), _c.POINTER(_F), _P]),
+    "dream_preprocess_frames_u8_f32": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P, _I, _P, _P, _I, _I, _I, _I, _c.POINTER(_F), _c.POINTER(_F), _P]),
     "dream_create_belief_maps_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_create_belief_maps_f64kps_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_smoothl1_fwd_bwd_f32": (_I, [_P, _P, _P, _P, _P, _SZ, _D, _P]),

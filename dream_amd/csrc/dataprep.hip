@@ -48,6 +48,139 @@ __global__ void __launch_bounds__(256) belief_maps_kernel(const double *kps, con
     }
 }
 
+// Raw camera frame -> network input (dream/image_proc.py:26-51 preprocess_image + :291-351, then ToTensor + Normalize as
+// dream/network.py:449-459), batched: optional crop, PIL's 8-bit BILINEAR resize, normalise.  Bit-identical to Pillow's
+// Resample.c: per-axis int32 coefficients (float64 weights scaled by 2^22 and rounded, built on the host), a horizontal
+// pass over the rows the vertical pass needs, rounded to uint8 (clip8), then the vertical pass on those uint8 rows,
+// rounded to uint8 again.  The intermediate rounding is part of the result, so the intermediate stays uint8.
+//
+// One workgroup = 64 output columns x `tile_rows` output rows of one frame.  LDS (dynamic, 16-byte aligned):
+//   in_s  [span_rows][rs]    the tile's input window (crop-relative rows r0.., columns c0..), copied with 16-byte loads from
+//                            a 16-byte aligned global address; each row starts `shift` bytes into its LDS row;
+//   mid_s [span_rows][192]   horizontal pass: uint8 RGB of the 64 output columns for every input row of the window;
+//   hk_s / hb_s, vk_s / vb_s the tile's coefficients and (lo, n) bounds.
+// The vertical pass and the normalise store each fp32 plane row as 64 consecutive floats per wave.
+constexpr int kPrepTileW = 64;
+constexpr int kPrepMidRow = kPrepTileW * 3;
+typedef unsigned u32x4_prep __attribute__((ext_vector_type(4)));
+
+__device__ inline unsigned char prep_clip8(int acc) {
+    return acc <= 0 ? 0 : (acc >= (255 << 22) ? 255 : (unsigned char)(acc >> 22));
+}
+
+__global__ void __launch_bounds__(256) preprocess_frames_kernel(
+    const unsigned char *img, float *out, unsigned char *out_u8, int B, int H, int W, int cx, int cy, int OH, int OW,
+    const int *hb, const int *hk, int ksx, const int *vb, const int *vk, int ksy, int tile_rows, int span_rows, int span_cols,
+    int rs, int ntx, int nty, float m0, float m1, float m2, float s0, float s1, float s2) {
+    DREAM_DYNAMIC_LDS(unsigned char, lds);
+    unsigned char *in_s = lds;
+    unsigned char *mid_s = in_s + (size_t)span_rows * rs;
+    int *hk_s = (int *)(mid_s + (size_t)span_rows * kPrepMidRow);
+    int *hb_s = hk_s + kPrepTileW * ksx;
+    int *vk_s = hb_s + kPrepTileW * 2;
+    int *vb_s = vk_s + tile_rows * ksy;
+
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % ntx, ty = (blockIdx.x / ntx) % nty, b = blockIdx.x / (ntx * nty);
+    const int ox0 = tx * kPrepTileW, oy0 = ty * tile_rows;
+    const int ncol = OW - ox0 < kPrepTileW ? OW - ox0 : kPrepTileW, nrow_out = OH - oy0 < tile_rows ? OH - oy0 : tile_rows;
+    // crop-relative input window of the tile (Pillow's bounds are monotone in the output index)
+    const int c0 = hb[2 * ox0], c1 = hb[2 * (ox0 + ncol - 1)] + hb[2 * (ox0 + ncol - 1) + 1];
+    const int r0 = vb[2 * oy0], r1 = vb[2 * (oy0 + nrow_out - 1)] + vb[2 * (oy0 + nrow_out - 1) + 1];
+    const int nrows = r1 - r0, ncols = c1 - c0;
+    if (nrows > span_rows || ncols > span_cols) {
+        // the caller's span sizes do not cover this tile: nothing is read into LDS, the tile is marked NaN
+        for (int i = tid; i < 3 * nrow_out * kPrepTileW; i += 256) {
+            const int x = i % kPrepTileW, y = (i / kPrepTileW) % nrow_out, c = i / (kPrepTileW * nrow_out);
+            if (x < ncol) out[(((size_t)b * 3 + c) * OH + oy0 + y) * OW + ox0 + x] = __builtin_nanf("");
+        }
+        return;
+    }
+
+    for (int i = tid; i < kPrepTileW * ksx; i += 256) {
+        const int x = i / ksx;
+        hk_s[i] = x < ncol ? hk[(size_t)(ox0 + x) * ksx + i % ksx] : 0;
+    }
+    for (int i = tid; i < kPrepTileW * 2; i += 256) hb_s[i] = (i >> 1) < ncol ? hb[2 * ox0 + i] : 0;
+    for (int i = tid; i < tile_rows * ksy; i += 256) {
+        const int y = i / ksy;
+        vk_s[i] = y < nrow_out ? vk[(size_t)(oy0 + y) * ksy + i % ksy] : 0;
+    }
+    for (int i = tid; i < tile_rows * 2; i += 256) vb_s[i] = (i >> 1) < nrow_out ? vb[2 * oy0 + i] : 0;
+
+    // input window -> LDS, 16 bytes per lane from the 16-byte aligned address at or below each row's first byte.  The frame
+    // buffer is 16-byte aligned (checked on the host); a chunk that would run past its end is read byte by byte.
+    const size_t total = (size_t)B * H * W * 3;
+    const int chunks = rs / 16;
+    for (int i = tid; i < nrows * chunks; i += 256) {
+        const int r = i / chunks, j = i - r * chunks;
+        const size_t start = (((size_t)b * H + cy + r0 + r) * W + cx + c0) * 3;
+        const int shift = (int)(start & 15);
+        if (16 * j >= shift + ncols * 3) continue;
+        const size_t g = (start & ~(size_t)15) + 16 * (size_t)j;
+        u32x4_prep v;
+        if (g + 16 <= total) {
+            v = *(const u32x4_prep *)(img + g);
+        } else {
+            unsigned char tmp[16];
+            for (int k = 0; k < 16; ++k) tmp[k] = g + k < total ? img[g + k] : 0;
+            __builtin_memcpy(&v, tmp, 16);
+        }
+        *(u32x4_prep *)(in_s + (size_t)r * rs + 16 * j) = v;
+    }
+    __syncthreads();
+
+    // horizontal pass: lane = output column, the four waves stride over the window's rows
+    const int x = tid & (kPrepTileW - 1);
+    if (x < ncol) {
+        const int lo = hb_s[2 * x] - c0, n = hb_s[2 * x + 1];
+        const int *k = hk_s + x * ksx;
+        for (int r = tid >> 6; r < nrows; r += 4) {
+            const size_t start = (((size_t)b * H + cy + r0 + r) * W + cx + c0) * 3;
+            const unsigned char *p = in_s + (size_t)r * rs + (start & 15) + lo * 3;
+            int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+            for (int t = 0; t < n; ++t) {
+                a0 += (int)p[3 * t] * k[t];
+                a1 += (int)p[3 * t + 1] * k[t];
+                a2 += (int)p[3 * t + 2] * k[t];
+            }
+            unsigned char *q = mid_s + (size_t)r * kPrepMidRow + 3 * x;
+            q[0] = prep_clip8(a0);
+            q[1] = prep_clip8(a1);
+            q[2] = prep_clip8(a2);
+        }
+    }
+    __syncthreads();
+
+    // vertical pass + ToTensor + Normalize: each wave stores whole 64-float runs of a plane row
+    if (x < ncol) {
+        const int ox = ox0 + x;
+        for (int y = tid >> 6; y < nrow_out; y += 4) {
+            const int lo = vb_s[2 * y] - r0, n = vb_s[2 * y + 1];
+            const int *k = vk_s + y * ksy;
+            const unsigned char *p = mid_s + (size_t)lo * kPrepMidRow + 3 * x;
+            int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+            for (int t = 0; t < n; ++t) {
+                a0 += (int)p[t * kPrepMidRow] * k[t];
+                a1 += (int)p[t * kPrepMidRow + 1] * k[t];
+                a2 += (int)p[t * kPrepMidRow + 2] * k[t];
+            }
+            const unsigned char v0 = prep_clip8(a0), v1 = prep_clip8(a1), v2 = prep_clip8(a2);
+            const int oy = oy0 + y;
+            const size_t plane = (size_t)OH * OW, o = ((size_t)b * 3 * OH + oy) * OW + ox;
+            out[o] = (((float)v0 / 255.0f) - m0) / s0;
+            out[o + plane] = (((float)v1 / 255.0f) - m1) / s1;
+            out[o + 2 * plane] = (((float)v2 / 255.0f) - m2) / s2;
+            if (out_u8) {
+                unsigned char *d = out_u8 + (((size_t)b * OH + oy) * OW + ox) * 3;
+                d[0] = v0;
+                d[1] = v1;
+                d[2] = v2;
+            }
+        }
+    }
+}
+
 inline unsigned sgrid(size_t n) {
     size_t g = (n + 255) / 256;
     if (g > 2048) g = 2048;
@@ -82,6 +215,40 @@ extern "C" int dream_normalize_u8_hwc_to_chw_f32(const unsigned char *img, float
                                                  const float *mean3, const float *stdev3, void *stream) {
     DREAM_REQUIRE(img && out && mean3 && stdev3 && B > 0 && H > 0 && W > 0, "normalize_u8: bad arguments");
     hipLaunchKernelGGL(normalize_u8_kernel, dim3(sgrid((size_t)B * H * W)), dim3(256), 0, (hipStream_t)stream, img, out, B, H, W,
+                       mean3[0], mean3[1], mean3[2], stdev3[0], stdev3[1], stdev3[2]);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+
+// LDS bytes of preprocess_frames_kernel for the given plan (the layout at the kernel; the input row padded for the alignment shift)
+static size_t preprocess_lds_bytes(int tile_rows, int span_rows, int span_cols, int ksx, int ksy, int *rs) {
+    *rs = ((span_cols * 3 + 15) + 15) / 16 * 16;
+    return (size_t)span_rows * (*rs + kPrepMidRow) + 4 * ((size_t)kPrepTileW * (ksx + 2) + (size_t)tile_rows * (ksy + 2));
+}
+
+extern "C" int dream_preprocess_frames_u8_f32(const unsigned char *frames, float *out, unsigned char *out_u8, int B, int H, int W,
+                                              int crop_x0, int crop_y0, int crop_w, int crop_h, int OH, int OW,
+                                              const int32_t *hbounds, const int32_t *hcoeffs, int ksize_x,
+                                              const int32_t *vbounds, const int32_t *vcoeffs, int ksize_y, int tile_rows,
+                                              int span_rows, int span_cols, const float *mean3, const float *stdev3,
+                                              void *stream) {
+    DREAM_REQUIRE(frames && out && hbounds && hcoeffs && vbounds && vcoeffs && mean3 && stdev3 && B > 0 && H > 0 && W > 0 &&
+                  OH > 0 && OW > 0 && ksize_x > 0 && ksize_y > 0 && tile_rows > 0 && span_rows > 0 && span_cols > 0,
+                  "preprocess_frames: bad arguments");
+    DREAM_REQUIRE(crop_x0 >= 0 && crop_y0 >= 0 && crop_w > 0 && crop_h > 0 && crop_x0 + crop_w <= W && crop_y0 + crop_h <= H,
+                  "preprocess_frames: crop window (%d,%d)+(%d,%d) outside the %dx%d frame", crop_x0, crop_y0, crop_w, crop_h, W, H);
+    DREAM_REQUIRE(span_rows <= crop_h && span_cols <= crop_w, "preprocess_frames: span (%d rows, %d columns) exceeds the crop",
+                  span_rows, span_cols);
+    DREAM_REQUIRE(((uintptr_t)frames & 15) == 0, "preprocess_frames: the frame buffer must be 16-byte aligned");
+    int rs = 0;
+    const size_t lds = preprocess_lds_bytes(tile_rows, span_rows, span_cols, ksize_x, ksize_y, &rs);
+    DREAM_REQUIRE(lds <= 65536, "preprocess_frames: %zu bytes of LDS (tile_rows %d, span %dx%d): use fewer tile rows", lds,
+                  tile_rows, span_rows, span_cols);
+    const int ntx = ceil_div(OW, kPrepTileW), nty = ceil_div(OH, tile_rows);
+    DREAM_REQUIRE((long)ntx * nty * B < (1l << 31), "preprocess_frames: batch too large");
+    hipLaunchKernelGGL(preprocess_frames_kernel, dim3((unsigned)(ntx * nty * B)), dim3(256), lds, (hipStream_t)stream, frames, out,
+                       out_u8, B, H, W, crop_x0, crop_y0, OH, OW, (const int *)hbounds, (const int *)hcoeffs, ksize_x,
+                       (const int *)vbounds, (const int *)vcoeffs, ksize_y, tile_rows, span_rows, span_cols, rs, ntx, nty,
                        mean3[0], mean3[1], mean3[2], stdev3[0], stdev3[1], stdev3[2]);
     DREAM_LAUNCH_OK();
     return 0;

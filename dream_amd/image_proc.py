@@ -177,3 +177,118 @@ def create_belief_map_batch(image_resolution, keypoints_bk2, sigma=2):
     out = torch.empty((b, k, height, width), dtype=torch.float32, device=kps.device)
     _hip.call("dream_create_belief_maps_f64kps_f32", ops.ptr(kps), ops.ptr(blob), ops.ptr(out), b * k, height, width, w, ops.stream())
     return out
+
+
+# ---- raw frames -> network input on the device (image_proc.py:26-51, 291-351; network.py:449-459) -------------------
+PREPROCESS_TILE_W = 64          # output columns per workgroup of dream_preprocess_frames_u8_f32
+PREPROCESS_LDS_BUDGET = 32768   # LDS bytes the planner aims at per workgroup (the entry point accepts up to 64 KiB)
+
+
+def resample_coefficients(n_in, n_out):
+    """Pillow's BILINEAR coefficients for one axis of an 8-bit image (Resample.c precompute_coeffs +
+    normalize_coeffs_8bpc), in float64 as Pillow computes them: n_in input pixels (the cropped extent) -> n_out.
+    -> (bounds int32 [n_out, 2] = (first input pixel, tap count), coeffs int32 [n_out, ksize] in units of 2^-22)."""
+    scale = float(n_in) / float(n_out)
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    bounds = np.zeros((n_out, 2), np.int32)
+    coeffs = np.zeros((n_out, ksize), np.int32)
+    for o in range(n_out):
+        center = (o + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), n_in) - lo
+        w = []
+        for i in range(n):
+            t = abs((i + lo - center + 0.5) * ss)
+            w.append(1.0 - t if t < 1.0 else 0.0)
+        ww = 0.0
+        for v in w:
+            ww += v
+        for i, v in enumerate(w):
+            v = v / ww if ww != 0.0 else v
+            coeffs[o, i] = int(v * (1 << 22) + 0.5) if v >= 0 else int(v * (1 << 22) - 0.5)
+        bounds[o] = (lo, n)
+    return bounds, coeffs
+
+
+def preprocess_geometry(image_raw_resolution, image_ref_resolution, image_preprocessing):
+    """-> ((crop x0, y0, width, height), (out width, height)) of preprocess_image for a raw frame of this size."""
+    assert image_preprocessing in KNOWN_IMAGE_PREPROC_TYPES, 'Image preprocessing type "{}" is not recognized.'.format(
+        image_preprocessing)
+    w, h = int(image_raw_resolution[0]), int(image_raw_resolution[1])
+    if image_preprocessing == "shrink-and-crop":
+        (cw, ch), (x0, y0) = shrink_and_crop_resolution((w, h), image_ref_resolution)
+        crop = (x0, y0, cw, ch)
+    else:
+        crop = (0, 0, w, h)
+    out = tuple(int(v) for v in resolution_after_preprocessing((w, h), image_ref_resolution, image_preprocessing))
+    return crop, out
+
+
+def _window(bounds, first, last):
+    return int(bounds[last, 0] + bounds[last, 1] - bounds[first, 0])
+
+
+def preprocess_plan(image_raw_resolution, image_ref_resolution, image_preprocessing):
+    """Host side of dream_preprocess_frames_u8_f32 for one raw frame size: crop, output size, both axes' coefficient tables and
+    the tiling (rows per workgroup, largest input window of a tile) -- numpy only, no device."""
+    crop, (ow, oh) = preprocess_geometry(image_raw_resolution, image_ref_resolution, image_preprocessing)
+    hb, hk = resample_coefficients(crop[2], ow)
+    vb, vk = resample_coefficients(crop[3], oh)
+    span_cols = max(_window(hb, x, min(x + PREPROCESS_TILE_W, ow) - 1) for x in range(0, ow, PREPROCESS_TILE_W))
+    rs = (span_cols * 3 + 30) // 16 * 16                   # the kernel's LDS row: 16-byte chunks from an aligned address
+    for tile_rows in (32, 16, 8, 4, 2, 1):
+        span_rows = max(_window(vb, y, min(y + tile_rows, oh) - 1) for y in range(0, oh, tile_rows))
+        lds = span_rows * (rs + 3 * PREPROCESS_TILE_W) + 4 * (PREPROCESS_TILE_W * (hk.shape[1] + 2) + tile_rows * (vk.shape[1] + 2))
+        if lds <= PREPROCESS_LDS_BUDGET:
+            break
+    return {"crop": crop, "out": (ow, oh), "hbounds": hb, "hcoeffs": hk, "vbounds": vb, "vcoeffs": vk,
+            "tile_rows": tile_rows, "span_rows": span_rows, "span_cols": span_cols}
+
+
+_plans = {}
+
+
+def _device_plan(device, image_raw_resolution, image_ref_resolution, image_preprocessing):
+    key = (str(device), tuple(image_raw_resolution), tuple(image_ref_resolution), image_preprocessing)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = dict(preprocess_plan(image_raw_resolution, image_ref_resolution, image_preprocessing))
+        for name in ("hbounds", "hcoeffs", "vbounds", "vcoeffs"):
+            plan[name] = torch.from_numpy(np.ascontiguousarray(plan[name])).to(device)
+        _plans[key] = plan
+    return plan
+
+
+def preprocess_frames(frames_u8_bhwc, image_ref_resolution, image_preprocessing, mean, stdev, return_u8=False):
+    """Batched, on-device preprocess_image + ToTensor + Normalize(mean, stdev) of raw RGB frames of one size (the per-frame
+    path is network.py:436-459): uint8 [B,H,W,3] (device or host tensor, or numpy array; host data is uploaded as uint8) ->
+    (normalised fp32 [B,3,h,w] on the device, (w, h)[, resized uint8 [B,h,w,3]]).  The uint8 frames are bit for bit PIL's
+    crop + resize(BILINEAR) and the fp32 tensor bit for bit what the host path computes from them."""
+    import ctypes
+    assert image_preprocessing in KNOWN_IMAGE_PREPROC_TYPES, 'Image preprocessing type "{}" is not recognized.'.format(
+        image_preprocessing)
+    x = frames_u8_bhwc
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3, "expected uint8 RGB frames [B,H,W,3]"
+    x = _hip.device_tensor(x).contiguous()
+    b, h, w = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    if image_preprocessing == "none":
+        out = normalize_images_u8(x, mean, stdev)
+        return (out, (w, h), x) if return_u8 else (out, (w, h))
+    if x.data_ptr() % 16:                       # the kernel reads the frames in aligned 16-byte chunks
+        x = x.clone()
+    plan = _device_plan(x.device, (w, h), image_ref_resolution, image_preprocessing)
+    (ow, oh), (cx, cy, cw, ch) = plan["out"], plan["crop"]
+    out = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=x.device)
+    u8 = torch.empty((b, oh, ow, 3), dtype=torch.uint8, device=x.device) if return_u8 else None
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in stdev])
+    _hip.call("dream_preprocess_frames_u8_f32", ops.ptr(x), ops.ptr(out), ops.ptr(u8), b, h, w, cx, cy, cw, ch, oh, ow,
+              ops.ptr(plan["hbounds"]), ops.ptr(plan["hcoeffs"]), int(plan["hcoeffs"].shape[1]), ops.ptr(plan["vbounds"]),
+              ops.ptr(plan["vcoeffs"]), int(plan["vcoeffs"].shape[1]), plan["tile_rows"], plan["span_rows"], plan["span_cols"],
+              m, s, ops.stream())
+    return (out, (ow, oh), u8) if return_u8 else (out, (ow, oh))

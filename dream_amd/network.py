@@ -17,6 +17,7 @@ What is different underneath:
     of nn.DataParallel's per-call replicate/scatter/gather (network.py:244-256); under torchrun it is one process per GPU with
     an RCCL all-reduce of the gradient buckets.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -321,6 +322,37 @@ class DreamNetwork:
             result["belief_maps"] = belief_maps_net_out
             result["detected_keypoints_net_output"] = kps_net_out
             result["detected_keypoints_net_input"] = kps_net_in
+        return result
+
+    # ---- batches of raw frames: keypoints_from_image with the preprocessing on the device ----------------------------
+    def keypoints_from_frames(self, frames, image_preprocessing_override=None, debug=False):
+        """The batched twin of keypoints_from_image for B raw RGB frames of one size (uint8 [B,H,W,3]: a device or host
+        tensor or a numpy array): crop + PIL-exact BILINEAR resize + normalise on self.device
+        (image_proc.preprocess_frames), inference(), then both keypoint frame conversions on the device.  -> {"detected_keypoints":
+        float64 [B,K,2] in raw-frame pixels}; per frame bit for bit what keypoints_from_image returns for a batch of the same
+        size built on the host.  debug=True adds "image_rgb_net_input" (uint8 [B,h,w,3] tensor), "belief_maps",
+        "detected_keypoints_net_output" and "detected_keypoints_net_input"."""
+        x = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+        assert isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3, \
+            'Expected "frames" to be uint8 RGB frames [B,H,W,3].'
+        input_image_resolution = (int(x.shape[2]), int(x.shape[1]))
+        preproc = image_preprocessing_override if image_preprocessing_override else self.image_preprocessing()
+        x = self._to_device(x)
+        with torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext():
+            net_in, netin_res_inf, u8 = image_proc.preprocess_frames(
+                x, self.trained_net_input_resolution(), preproc, self.image_normalization["mean"],
+                self.image_normalization["stdev"], return_u8=True)
+            with torch.no_grad():
+                belief_maps, kps_net_out = self.inference(net_in)
+            netout_res_inf = (int(belief_maps.shape[3]), int(belief_maps.shape[2]))
+            kps_net_in, kps_raw = image_proc.convert_keypoints_batch(kps_net_out, netout_res_inf, netin_res_inf,
+                                                                     input_image_resolution, preproc)
+        result = {"detected_keypoints": kps_raw.cpu().numpy()}
+        if debug:
+            result["image_rgb_net_input"] = u8
+            result["belief_maps"] = belief_maps
+            result["detected_keypoints_net_output"] = kps_net_out.numpy().astype(float)
+            result["detected_keypoints_net_input"] = kps_net_in.cpu().numpy()
         return result
 
     # ---- inference (network.py:503-590) --------------------------------------------------------------------------

@@ -346,6 +346,19 @@ int dream_normalize_u8_hwc_to_chw_f32(const unsigned char *img, float *out, int 
                                       const float *mean3, const float *stdev3, void *stream);
 int dream_create_belief_maps_f64kps_f32(const double *kps, const float *blob, float *out, int N, int H, int W, int w,
                                         void *stream);
+/* Raw camera frames -> network input, batched (dream/image_proc.py:26-51 preprocess_image with the resolutions of
+ * :291-351, then ToTensor + Normalize as dream/network.py:449-459): uint8 RGB frames [B,H,W,3] (16-byte aligned) -> the
+ * crop window (crop_x0, crop_y0, crop_w, crop_h) resized to OW x OH with PIL's 8-bit BILINEAR arithmetic (int32 weights in
+ * units of 2^-22, a horizontal pass rounded to uint8, then a vertical pass rounded to uint8) -> out fp32 [B,3,OH,OW]
+ * normalised like dream_normalize_u8_hwc_to_chw_f32; out_u8 [B,OH,OW,3] (may be NULL) receives the resized uint8 frames.
+ * Per axis the caller passes bounds [n_out][2] = (first input index in the crop, tap count) and coefficients
+ * [n_out][ksize] (image_proc.resample_coefficients); tile_rows output rows per workgroup, span_rows / span_cols = the
+ * largest input window of a 64-column x tile_rows tile (image_proc.preprocess_plan).  mean3 / stdev3: HOST pointers. */
+int dream_preprocess_frames_u8_f32(const unsigned char *frames, float *out, unsigned char *out_u8, int B, int H, int W,
+                                   int crop_x0, int crop_y0, int crop_w, int crop_h, int OH, int OW,
+                                   const int32_t *hbounds, const int32_t *hcoeffs, int ksize_x,
+                                   const int32_t *vbounds, const int32_t *vcoeffs, int ksize_y, int tile_rows,
+                                   int span_rows, int span_cols, const float *mean3, const float *stdev3, void *stream);
 /* ABI 1 took fp32 keypoints under this name; fp32 cannot hold the reference's float64 coordinates (57.9999999 is pixel 57,
  * its fp32 rounding pixel 58), so the entry point now FAILS with a message instead of reading fp32 data as float64. */
 int dream_create_belief_maps_f32(const float *kps, const float *blob, float *out, int N, int H, int W, int w,
