@@ -1118,33 +1118,7 @@ class ResnetSimple(nn.Module):
         self.full = full
         self.n_keypoints = n_keypoints
         self._cache = {}
-        self.precision = "fp32"        # "fp16x3": evaluation-mode forward on the split-precision conv kernel
-        self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
-        # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
-        self.conv1x1_algorithm = os.environ.get("DREAM_CONV1X1_ALGORITHM", "gemm")
-        # decoder ConvTranspose2d(k4,s2,p1) forward: "winograd" = minimal filtering on the Winograd kernel (9/16 of the direct
-        # multiplications, conv_wino.hip), "direct" = sub-pixel phases on conv_mfma
-        self.convT_algorithm = os.environ.get("DREAM_CONVT_ALGORITHM", "winograd")
-        # weight gradients on a second stream, concurrent with the data-gradient chain (DREAM_OVERLAP_WGRAD=0: in order), up to
-        # overlap_max_frames 400x400 frames per step (beyond, each kernel fills the chip on its own).  Round 5 tried 128: with the
-        # weight-gradient stream at the lowest HIP priority the overlap gave 447-453 frames/s at 128 frames in twelve runs on four boxes
-        # (in order: 435-438) -- and 414 in the round's final measurement run, 300 in two early ones: unreliable, so 96 stays
-        self.overlap_wgrad = os.environ.get("DREAM_OVERLAP_WGRAD", "1") != "0"
-        self.overlap_max_frames = int(os.environ.get("DREAM_OVERLAP_MAX_FRAMES", "96"))
-        # the 3x3 convs' BatchNorm statistics / masked backward reductions in the Winograd F(2x2) kernel's epilogue (csrc/conv_wino.hip
-        # WINO_STAT) -- 66 launches fewer per ResNet-101 step; measured round 5 (profiles/r05_ab_bn_fusion_3x3.txt, alternating on one
-        # box): 350.4 -> 358.5 frames/s at 16 frames (+2.3 %), so on by default; "0" = the stand-alone bn_stats / bn_bwd_stats passes
-        self.bn_fusion_3x3 = os.environ.get("DREAM_BN_FUSION_3X3", "1") == "1"
-        # ... and (round 6) the last decoder BatchNorm's in the head conv's data gradient (run_backward_fused, "final")
-        self.bn_fusion_head = os.environ.get("DREAM_BN_FUSION_HEAD", "1") == "1"
-        self.stem_on_gemm = os.environ.get("DREAM_STEM_GEMM", "1") == "1"     # training: the 7x7 stem + its statistics + its weight gradient on the 1x1 GEMM
-        self.ds_on_gemm = os.environ.get("DREAM_DS_GEMM", "1") == "1"         # training: the stride-2 downsample convs on the 1x1 GEMM over gathered pixels
-        self.CONVT_GEMM_MAX_PIXELS = int(os.environ.get("DREAM_CONVT_GEMM_MAX_PIXELS", "6000"))   # training forward: transposed convs on small maps as GEMM + gather
-        self.COL3_MAX_PIXELS = int(os.environ.get("DREAM_COL3_MAX_PIXELS", "12000"))   # ... and 3x3 stride-2 convs with at most this many output pixels
-        # training: BatchNorm without its separate passes (round 4) -- statistics finished inside the launch that sums them (the
-        # 1x1 convs' own epilogues where possible), BN + ReLU applied by the consuming 1x1 conv's loader, the backward reductions in
-        # the data-gradient epilogue; "0" = the three-launch kernels of rounds 1-3 (A/B, tests)
-        self.bn_fusion = os.environ.get("DREAM_BN_FUSION", "1") != "0"
+        self._read_switches()
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         inplanes = 64
@@ -1178,6 +1152,36 @@ class ResnetSimple(nn.Module):
         # models.py:22: resnet101(pretrained=pretrained) -- ImageNet trunk when it can be had, one loud warning otherwise.
         # ``freeze`` is accepted and unused, exactly as in the reference (models.py:19: never read).
         self.imagenet_initialised = _pretrained.init_resnet101_trunk(self) if pretrained else False
+
+    def _read_switches(self):
+        """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""
+        self.precision = "fp32"        # "fp16x3": evaluation-mode forward on the split-precision conv kernel
+        self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
+        # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
+        self.conv1x1_algorithm = os.environ.get("DREAM_CONV1X1_ALGORITHM", "gemm")
+        # decoder ConvTranspose2d(k4,s2,p1) forward: "winograd" = minimal filtering on the Winograd kernel (9/16 of the direct
+        # multiplications, conv_wino.hip), "direct" = sub-pixel phases on conv_mfma
+        self.convT_algorithm = os.environ.get("DREAM_CONVT_ALGORITHM", "winograd")
+        # weight gradients on a second stream, concurrent with the data-gradient chain (DREAM_OVERLAP_WGRAD=0: in order), up to
+        # overlap_max_frames 400x400 frames per step (beyond, each kernel fills the chip on its own).  Round 5 tried 128: with the
+        # weight-gradient stream at the lowest HIP priority the overlap gave 447-453 frames/s at 128 frames in twelve runs on four boxes
+        # (in order: 435-438) -- and 414 in the round's final measurement run, 300 in two early ones: unreliable, so 96 stays
+        self.overlap_wgrad = os.environ.get("DREAM_OVERLAP_WGRAD", "1") != "0"
+        self.overlap_max_frames = int(os.environ.get("DREAM_OVERLAP_MAX_FRAMES", "96"))
+        # the 3x3 convs' BatchNorm statistics / masked backward reductions in the Winograd F(2x2) kernel's epilogue (csrc/conv_wino.hip
+        # WINO_STAT) -- 66 launches fewer per ResNet-101 step; measured round 5 (profiles/r05_ab_bn_fusion_3x3.txt, alternating on one
+        # box): 350.4 -> 358.5 frames/s at 16 frames (+2.3 %), so on by default; "0" = the stand-alone bn_stats / bn_bwd_stats passes
+        self.bn_fusion_3x3 = os.environ.get("DREAM_BN_FUSION_3X3", "1") == "1"
+        # ... and (round 6) the last decoder BatchNorm's in the head conv's data gradient (run_backward, "final")
+        self.bn_fusion_head = os.environ.get("DREAM_BN_FUSION_HEAD", "1") == "1"
+        self.stem_on_gemm = os.environ.get("DREAM_STEM_GEMM", "1") == "1"     # training: the 7x7 stem + its statistics + its weight gradient on the 1x1 GEMM
+        self.ds_on_gemm = os.environ.get("DREAM_DS_GEMM", "1") == "1"         # training: the stride-2 downsample convs on the 1x1 GEMM over gathered pixels
+        self.CONVT_GEMM_MAX_PIXELS = int(os.environ.get("DREAM_CONVT_GEMM_MAX_PIXELS", "6000"))   # training forward: transposed convs on small maps as GEMM + gather
+        self.COL3_MAX_PIXELS = int(os.environ.get("DREAM_COL3_MAX_PIXELS", "12000"))   # ... and 3x3 stride-2 convs with at most this many output pixels
+        # training: BatchNorm without its separate passes (round 4) -- statistics finished inside the launch that sums them (the
+        # 1x1 convs' own epilogues where possible), BN + ReLU applied by the consuming 1x1 conv's loader, the backward reductions in
+        # the data-gradient epilogue; "0" = the three-launch kernels of rounds 1-3 (A/B, tests)
+        self.bn_fusion = os.environ.get("DREAM_BN_FUSION", "1") != "0"
 
     def output_resolution(self, input_wh):
         def trunk(v):
@@ -1296,30 +1300,102 @@ class ResnetSimple(nn.Module):
             bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
             conv_bias.detach() if conv_bias is not None else None))
 
+    # ---- the network, once: what every forward pass walks (the names are cache keys, _pack_state records, EARLY_BUCKET_FROM markers) ----
+    def _trunk(self):
+        """(name, Bottleneck) in execution order."""
+        for li in (1, 2, 3, 4):
+            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
+                yield "layer%d.%d" % (li, bi), blk
+
+    def _decoder(self):
+        """(name, ConvTranspose2d, BatchNorm2d) per decoder stage, then (name, head conv, None)."""
+        for sname in ("upsample", "upsample2") if self.full else ("upsample",):
+            mods = list(getattr(self, sname))
+            i = 0
+            while i < len(mods):
+                if isinstance(mods[i], nn.ConvTranspose2d):
+                    yield "%s.%d" % (sname, i), mods[i], mods[i + 1]
+                    i += 3                                  # ConvTranspose2d, BatchNorm2d, ReLU
+                else:                                       # final 1x1 conv -> K belief maps
+                    yield "%s.%d" % (sname, i), mods[i], None
+                    i += 1
+
+    # ---- packed weights: one place per cache key ----------------------------------------------------------------------------------
+    def _packed_w(self, name, conv, mode):
+        return self._cached(("w%d" % mode, name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), mode))
+
+    def _g(self, name, conv, mode, col3=False):
+        """-> (packed, rows) for the 1x1 GEMM: mode 0 = forward (key "g0"), 1 = data gradient ("g1").  ``col3``: a 3x3 conv that runs on its
+        patch rows (ops.im2col3s2), GEMM weight [Cout][t Cin + c] = w[co][c][ky][kx]."""
+        def build():
+            w = conv.weight.detach()
+            if col3:
+                w = w.permute(0, 2, 3, 1).reshape(int(w.shape[0]), -1, 1, 1).contiguous()
+            return ops.pack_conv1x1_weight(w, mode)
+        return self._cached(("g%d" % mode, name), [conv.weight], build)
+
+    def _g_head(self, name, m, mode, rows):
+        """The head conv's GEMM weight with its K output channels zero-padded to ``rows`` (keys "g0h" / "g1h") -> packed."""
+        def build():
+            cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
+            w2 = m.weight.detach().reshape(cout, cin)
+            return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((rows - cout, cin))]).reshape(rows, cin, 1, 1), mode)
+        return self._cached(("g%dh" % mode, name), [m.weight], build)[0]
+
+    def _wino(self, name, conv, mode, tile):
+        """-> (u, rows) of a stride-1 3x3 conv for the Winograd kernel of this tile: mode 0 = forward ("wino"), 1 = data gradient ("wino1")."""
+        return self._cached(("wino1" if mode else "wino", name, tile), [conv.weight],
+                            lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), mode, tile))
+
+    STEM_COLS = {"w": 160, "g0e": 160, "g0": 192}
+
+    def _stem_weight(self, kind):
+        """The 7x7 stem's weight for its im2col rows (147 taps, zero-padded to STEM_COLS[kind] columns): "w" = the 1-tap direct kernel,
+        "g0e" = the 1x1 GEMM in evaluation, "g0" = the 1x1 GEMM in training (192: the granularity of its statistics epilogue)."""
+        def build():
+            w2 = self.conv1.weight.detach().reshape(64, 147)
+            if kind == "w":
+                return ops.pack_matrix_weight(w2, 160)
+            kcol = self.STEM_COLS[kind]
+            return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((64, kcol - 147))], dim=1).reshape(64, kcol, 1, 1), 0)
+        return self._cached((kind, "conv1"), [self.conv1.weight], build)[0]
+
+    def _gemm1x1(self, conv, x, k=None, stride=None, bwd=False):
+        """Stride-1 1x1 convs with channel counts the LDS-free GEMM kernel takes (all of ResNet-101's: multiples of 64).  ``k`` / ``stride``:
+        as the unit ran, where that differs from the module (a downsample conv over gathered pixels runs with stride 1).  ``bwd``: the data
+        gradient -- x is dz, Cin and Cout swap roles."""
+        k = int(conv.kernel_size[0]) if k is None else k
+        stride = int(conv.stride[0]) if stride is None else stride
+        cout, cin = (int(v) for v in conv.weight.shape[:2])
+        if bwd:
+            cout, cin = cin, cout
+        return self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and cin == int(x.shape[3]) and ops.conv1x1_applies(x, cout)
+
     def _conv_bn(self, name, x, conv, bn, relu, residual=None):
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         scale, shift = self._fold(name, bn, conv.bias)
         cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
+        flags = CONV_RELU if relu else 0
         if k == 3 and stride == 1 and self.conv_algorithm == "winograd" and cin % 16 == 0 and cout >= 64:
             # the stride-1 3x3 convs of the bottlenecks: Winograd F(2x2,3x3) with the folded BatchNorm in the epilogue
             tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), cin, cout, int(x.shape[0]))
-            u, rows = self._cached(("wino", name, tile), [conv.weight], lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), 0, tile))
-            return ops.conv3x3_winograd_tile(tile, x, u, rows, scale, shift, residual, CONV_RELU if relu else 0)
+            u, rows = self._wino(name, conv, 0, tile)
+            return ops.conv3x3_winograd_tile(tile, x, u, rows, scale, shift, residual, flags)
         if self._gemm1x1(conv, x):
             # the 1x1 convs of the bottlenecks: a plain GEMM without LDS (gemm1x1.hip), folded BatchNorm / residual / ReLU fused
-            packed, rows = self._cached(("g0", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 0))
-            return ops.conv1x1(x, packed, rows, scale, shift, residual, CONV_RELU if relu else 0)
-        if (self.ds_on_gemm and k == 1 and stride == 2 and self.conv1x1_algorithm == "gemm" and cin == int(x.shape[3]) and cin % 64 == 0):
-            # the stride-2 downsample convs on the GEMM over the pixels they read (as in training: _unit_fused)
+            packed, rows = self._g(name, conv, 0)
+            return ops.conv1x1(x, packed, rows, scale, shift, residual, flags)
+        if self.ds_on_gemm and k == 1 and stride == 2 and self.conv1x1_algorithm == "gemm" and cin == int(x.shape[3]) and cin % 64 == 0:
+            # the stride-2 downsample convs on the GEMM over the pixels they read (as in training: _unit)
             xs = ops.subsample2(x)
             if ops.conv1x1_applies(xs, cout):
-                packed, rows = self._cached(("g0", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 0))
-                return ops.conv1x1(xs, packed, rows, scale, shift, residual, CONV_RELU if relu else 0)
+                packed, rows = self._g(name, conv, 0)
+                return ops.conv1x1(xs, packed, rows, scale, shift, residual, flags)
         packed, rows, _ = self._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
-        return ops.conv2d(x, packed, rows, k, stride, scale, shift, residual, CONV_RELU if relu else 0)
+        return ops.conv2d(x, packed, rows, k, stride, scale, shift, residual, flags)
 
     def _convT_gemm(self, name, m, y):
-        """Does this transposed conv run as one 1x1 GEMM (N = 16 Cout) + a gather (small maps: run_forward_train_fused)?  -> packed weight or None."""
+        """Does this transposed conv run as one 1x1 GEMM (N = 16 Cout) + a gather (small maps: _convT_forward)?  -> packed weight or None."""
         co_t, npx = int(m.weight.shape[1]), int(y.shape[0]) * int(y.shape[1]) * int(y.shape[2])
         if not (self.ds_on_gemm and self.conv1x1_algorithm == "gemm" and npx <= self.CONVT_GEMM_MAX_PIXELS and co_t % 4 == 0
                 and tuple(m.kernel_size) == (4, 4) and tuple(m.stride) == (2, 2) and tuple(m.padding) == (1, 1)
@@ -1328,10 +1404,22 @@ class ResnetSimple(nn.Module):
         return self._cached(("g0T", name), [m.weight], lambda: ops.pack_conv1x1_weight(
             m.weight.detach().permute(2, 3, 1, 0).reshape(16 * co_t, -1, 1, 1).contiguous(), 0))
 
-    def _gemm1x1(self, conv, x):
-        """Stride-1 1x1 convs with channel counts the LDS-free GEMM kernel takes (all of ResNet-101's: multiples of 64)."""
-        return (self.conv1x1_algorithm == "gemm" and int(conv.kernel_size[0]) == 1 and int(conv.stride[0]) == 1
-                and int(conv.weight.shape[1]) == int(x.shape[3]) and ops.conv1x1_applies(x, int(conv.weight.shape[0])))
+    def _convT_forward(self, name, m, y, scale, shift, flags, gemm=True):
+        """ConvTranspose2d(k4,s2,p1) * scale + shift (flags): evaluation passes the folded BatchNorm and CONV_RELU, training None, the bias
+        and 0.  ``gemm``: whether the GEMM form is eligible at all (not in training with bn_fusion off)."""
+        cout = int(m.weight.shape[1])
+        gT = self._convT_gemm(name, m, y) if gemm else None
+        if gT is not None:
+            # Round 6: a transposed conv on a small map (the first decoder layer: 2048 -> 256 on 13 x 13 maps, 2704 pixels at 16
+            # frames -- 50-100 workgroups of the Winograd kernel on 256 CUs) as ONE 1x1 GEMM with N = 16 Cout (the sixteen tap
+            # contributions of every input pixel) + a gather that sums the <= 4 contributions landing on each output pixel
+            return ops.col2im4s2(ops.conv1x1(y, gT[0], gT[1], None, None, None, ops.CONV_NO_KSPLIT), cout, shift, scale=scale, flags=flags)
+        if self.convT_algorithm == "winograd" and ops.convT4x4_winograd_applies(y, cout):
+            tile = ops.convT4x4_winograd_tile(y, cout)
+            u4, rows = self._cached(("wu4", name, tile), [m.weight], lambda: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile))
+            return ops.conv_transpose4x4s2_winograd_tile(tile, y, u4, rows, scale, shift, flags)
+        packed, rows = self._cached(("w", name), [m.weight], lambda: ops.pack_convT4x4_weight(m.weight.detach()))
+        return ops.conv_transpose4x4s2(y, packed, rows, scale, shift, flags)
 
     # ---- inference on the split-precision conv kernel (strided convs stay on the fp32 kernel) ------------------
     def _conv_bn16(self, name, x, amax, conv, bn, relu, residual=None):
@@ -1355,31 +1443,21 @@ class ResnetSimple(nn.Module):
         y, amax = ops.conv2d_f16x3(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
         del col
         y = ops.maxpool3s2(y)                              # pooling cannot raise the maximum: amax carries over
-        for li in (1, 2, 3, 4):
-            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
-                name = "layer%d.%d" % (li, bi)
-                idt = y
-                if hasattr(blk, "downsample"):
-                    idt, _ = self._conv_bn16(name + ".ds", y, amax, blk.downsample[0], blk.downsample[1], relu=False)
-                o, a1 = self._conv_bn16(name + ".1", y, amax, blk.conv1, blk.bn1, relu=True)
-                o, a2 = self._conv_bn16(name + ".2", o, a1, blk.conv2, blk.bn2, relu=True)
-                y, amax = self._conv_bn16(name + ".3", o, a2, blk.conv3, blk.bn3, relu=True, residual=idt)
-        seqs = [("upsample", self.upsample)] + ([("upsample2", self.upsample2)] if self.full else [])
-        for sname, seq in seqs:
-            mods = list(seq)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                name = "%s.%d" % (sname, i)
-                if isinstance(m, nn.ConvTranspose2d):
-                    p16 = self._cached(("w16", name), [m.weight], lambda m=m: ops.pack_convT4x4_weight_f16x3(m.weight.detach()))
-                    scale, shift = self._fold(name, mods[i + 1], m.bias)
-                    y, amax = ops.conv_transpose4x4s2_f16x3(y, amax, p16, p16[3], scale, shift, CONV_RELU)
-                    i += 3
-                else:
-                    p16 = self._cached(("w16", name), [m.weight], lambda m=m: ops.pack_conv_weight_f16x3(m.weight.detach(), 0))
-                    y, _ = ops.conv2d_f16x3(y, amax, p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)
-                    i += 1
+        for name, blk in self._trunk():
+            idt = y
+            if hasattr(blk, "downsample"):
+                idt, _ = self._conv_bn16(name + ".ds", y, amax, blk.downsample[0], blk.downsample[1], relu=False)
+            o, a1 = self._conv_bn16(name + ".1", y, amax, blk.conv1, blk.bn1, relu=True)
+            o, a2 = self._conv_bn16(name + ".2", o, a1, blk.conv2, blk.bn2, relu=True)
+            y, amax = self._conv_bn16(name + ".3", o, a2, blk.conv3, blk.bn3, relu=True, residual=idt)
+        for name, m, bn in self._decoder():
+            if bn is not None:
+                p16 = self._cached(("w16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16x3(m.weight.detach()))
+                scale, shift = self._fold(name, bn, m.bias)
+                y, amax = ops.conv_transpose4x4s2_f16x3(y, amax, p16, p16[3], scale, shift, CONV_RELU)
+            else:
+                p16 = self._cached(("w16", name), [m.weight], lambda: ops.pack_conv_weight_f16x3(m.weight.detach(), 0))
+                y, _ = ops.conv2d_f16x3(y, amax, p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)
         return y
 
     def run_forward(self, x):
@@ -1388,246 +1466,39 @@ class ResnetSimple(nn.Module):
         if self.precision == "fp16x3":
             return self.run_forward_f16x3(x)
         # stem: 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused; then MaxPool(3,2,1)
-        col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
+        col = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0e"])           # (= STEM_COLS["w"])
         s1, t1 = self._fold("bn1", self.bn1)
         if self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and ops.conv1x1_applies(col, 64):
             # Round 6: the im2col rows (K = 160) through the 1x1 GEMM kernel (the 1-tap direct kernel ran them at 69 TFLOP/s; this is a
             # stream of 0.8 GB in, 0.3 GB out at 32 frames)
-            def build():
-                w2 = self.conv1.weight.detach().reshape(64, 147)
-                return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((64, 13))], dim=1).reshape(64, 160, 1, 1), 0)
-            packed, rows = self._cached(("g0e", "conv1"), [self.conv1.weight], build)
-            y = ops.conv1x1(col, packed, rows, s1, t1, None, CONV_RELU)
+            y = ops.conv1x1(col, self._stem_weight("g0e"), 64, s1, t1, None, CONV_RELU)
         else:
-            w1 = self._cached(("w", "conv1"), [self.conv1.weight],
-                              lambda: ops.pack_matrix_weight(self.conv1.weight.detach().reshape(64, 147), 160))
-            y = ops.conv2d(col, w1[0], 64, 1, 1, s1, t1, None, CONV_RELU)
+            y = ops.conv2d(col, self._stem_weight("w"), 64, 1, 1, s1, t1, None, CONV_RELU)
         del col
         y = ops.maxpool3s2(y)
-        for li in (1, 2, 3, 4):
-            stage = getattr(self, "layer%d" % li)
-            for bi, blk in enumerate(stage):
-                name = "layer%d.%d" % (li, bi)
-                idt = y
-                if hasattr(blk, "downsample"):
-                    idt = self._conv_bn(name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
-                o = self._conv_bn(name + ".1", y, blk.conv1, blk.bn1, relu=True)
-                o = self._conv_bn(name + ".2", o, blk.conv2, blk.bn2, relu=True)
-                y = self._conv_bn(name + ".3", o, blk.conv3, blk.bn3, relu=True, residual=idt)
-        seqs = [("upsample", self.upsample)] + ([("upsample2", self.upsample2)] if self.full else [])
-        for sname, seq in seqs:
-            mods = list(seq)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                name = "%s.%d" % (sname, i)
-                if isinstance(m, nn.ConvTranspose2d):
-                    bn = mods[i + 1]
-                    scale, shift = self._fold(name, bn, m.bias)
-                    gT = self._convT_gemm(name, m, y)
-                    if gT is not None:
-                        y = ops.col2im4s2(ops.conv1x1(y, gT[0], gT[1], None, None, None, ops.CONV_NO_KSPLIT), int(m.weight.shape[1]), shift, scale=scale, flags=CONV_RELU)
-                    elif self.convT_algorithm == "winograd" and ops.convT4x4_winograd_applies(y, int(m.weight.shape[1])):
-                        tile = ops.convT4x4_winograd_tile(y, int(m.weight.shape[1]))
-                        u4, cout = self._cached(("wu4", name, tile), [m.weight], lambda m=m, tile=tile: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile))
-                        y = ops.conv_transpose4x4s2_winograd_tile(tile, y, u4, cout, scale, shift, CONV_RELU)
-                    else:
-                        packed, cout = self._cached(("w", name), [m.weight], lambda m=m: ops.pack_convT4x4_weight(m.weight.detach()))
-                        y = ops.conv_transpose4x4s2(y, packed, cout, scale, shift, CONV_RELU)
-                    i += 3                                  # ConvTranspose2d, BatchNorm2d, ReLU
-                else:                                       # final 1x1 conv -> K belief maps, NCHW
-                    packed, rows, _ = self._cached(("w", name), [m.weight], lambda m=m: ops.pack_conv_weight(m.weight.detach(), 0))
-                    y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
-                    i += 1
+        for name, blk in self._trunk():
+            idt = y
+            if hasattr(blk, "downsample"):
+                idt = self._conv_bn(name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
+            o = self._conv_bn(name + ".1", y, blk.conv1, blk.bn1, relu=True)
+            o = self._conv_bn(name + ".2", o, blk.conv2, blk.bn2, relu=True)
+            y = self._conv_bn(name + ".3", o, blk.conv3, blk.bn3, relu=True, residual=idt)
+        for name, m, bn in self._decoder():
+            if bn is not None:
+                scale, shift = self._fold(name, bn, m.bias)
+                y = self._convT_forward(name, m, y, scale, shift, CONV_RELU)
+            else:                                           # final 1x1 conv -> K belief maps, NCHW
+                packed, rows, _ = self._cached(("w", name), [m.weight], lambda: ops.pack_conv_weight(m.weight.detach(), 0))
+                y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
         return y
 
     # ---- training: train-mode BatchNorm (batch statistics), activations kept for the backward plan --------
-    def _packed_w(self, name, conv, mode):
-        return self._cached(("w%d" % mode, name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), mode))
-
-    def _unit_fwd(self, tape, name, x, conv, bn, relu, residual=None):
-        """conv -> BN(batch stats) (+residual) (ReLU); records what the backward needs."""
-        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
-        bias = conv.bias.detach() if conv.bias is not None else None
-        if self._wino_train(conv):
-            tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), int(conv.weight.shape[1]), int(conv.weight.shape[0]), int(x.shape[0]))
-            u, rows = self._cached(("wino", name, tile), [conv.weight], lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), 0, tile))
-            z = ops.conv3x3_winograd_tile(tile, x, u, rows, None, bias, None, 0)
-        elif self._gemm1x1(conv, x):
-            packed, rows = self._cached(("g0", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 0))
-            z = ops.conv1x1(x, packed, rows, None, bias, None, 0)
-        else:
-            packed, rows, _ = self._packed_w(name, conv, 0)
-            z = ops.conv2d(x, packed, rows, k, stride, None, bias, None, 0)
-        y, mean, invstd = ops.bn_train_fwd(z, bn, residual, relu)
-        tape.append(dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, z=z, y=y, mean=mean, invstd=invstd,
-                         k=k, stride=stride, has_res=residual is not None))
-        return y
-
-    def _wino_train(self, conv):
-        """Training: the stride-1 3x3 convs of the bottlenecks (forward and data gradient) on the Winograd kernel."""
-        return (self.conv_algorithm == "winograd" and int(conv.kernel_size[0]) == 3 and int(conv.stride[0]) == 1
-                and int(conv.weight.shape[1]) % 16 == 0 and int(conv.weight.shape[0]) % 16 == 0
-                and min(int(conv.weight.shape[0]), int(conv.weight.shape[1])) >= 64)
-
-    def _bwd_data(self, name, conv, dz, cin, k, stride, in_hw, residual=None):
-        if self._wino_train(conv):
-            tile = ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), int(conv.weight.shape[0]), int(conv.weight.shape[1]), int(dz.shape[0]))
-            u_t, rows = self._cached(("wino1", name, tile), [conv.weight], lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), 1, tile))
-            return ops.conv3x3_winograd_tile(tile, dz, u_t, rows, None, None, residual, 0)
-        if (self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and int(dz.shape[3]) == int(conv.weight.shape[0])
-                and ops.conv1x1_applies(dz, cin)):
-            packed_t, rows = self._cached(("g1", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 1))
-            return ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
-        packed_t, rows, _ = self._packed_w(name, conv, 1)
-        return ops.conv2d_bwd_data(dz, packed_t, cin, k, stride, in_hw, residual=residual)
-
-    def run_forward_train(self, x):
-        if self.bn_fusion:
-            return self.run_forward_train_fused(x)
-        self._repack_weights()
-        tape = []
-        col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
-        w1 = self._cached(("w", "conv1"), [self.conv1.weight],
-                          lambda: ops.pack_matrix_weight(self.conv1.weight.detach().reshape(64, 147), 160))
-        z = ops.conv2d(col, w1[0], 64, 1, 1)
-        y, mean, invstd = ops.bn_train_fwd(z, self.bn1, None, True)
-        tape.append(dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, x=col, z=z, y=y, mean=mean, invstd=invstd))
-        yp = ops.maxpool3s2(y)
-        tape.append(dict(kind="pool", x=y))
-        y = yp
-        for li in (1, 2, 3, 4):
-            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
-                name = "layer%d.%d" % (li, bi)
-                tape.append(dict(kind="block_begin", name=name, ds=hasattr(blk, "downsample")))
-                idt = y
-                if hasattr(blk, "downsample"):
-                    idt = self._unit_fwd(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
-                o = self._unit_fwd(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True)
-                o = self._unit_fwd(tape, name + ".2", o, blk.conv2, blk.bn2, relu=True)
-                y = self._unit_fwd(tape, name + ".3", o, blk.conv3, blk.bn3, relu=True, residual=idt)
-                tape.append(dict(kind="block_end", name=name))
-        seqs = [("upsample", self.upsample)] + ([("upsample2", self.upsample2)] if self.full else [])
-        for sname, seq in seqs:
-            mods = list(seq)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                name = "%s.%d" % (sname, i)
-                if isinstance(m, nn.ConvTranspose2d):
-                    bn = mods[i + 1]
-                    if self.convT_algorithm == "winograd" and ops.convT4x4_winograd_applies(y, int(m.weight.shape[1])):
-                        tile = ops.convT4x4_winograd_tile(y, int(m.weight.shape[1]))
-                        u4, cout = self._cached(("wu4", name, tile), [m.weight], lambda m=m, tile=tile: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile))
-                        z = ops.conv_transpose4x4s2_winograd_tile(tile, y, u4, cout, None, m.bias.detach(), 0)
-                    else:
-                        packed, cout = self._cached(("w", name), [m.weight], lambda m=m: ops.pack_convT4x4_weight(m.weight.detach()))
-                        z = ops.conv_transpose4x4s2(y, packed, cout, None, m.bias.detach(), 0)
-                    y2, mean, invstd = ops.bn_train_fwd(z, bn, None, True)
-                    tape.append(dict(kind="convT", name=name, conv=m, bn=bn, relu=True, x=y, z=z, y=y2, mean=mean, invstd=invstd))
-                    y = y2
-                    i += 3
-                else:
-                    packed, rows, _ = self._packed_w(name, m, 0)
-                    out = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
-                    tape.append(dict(kind="final", name=name, conv=m, x=y))
-                    y = out
-                    i += 1
-        return y, tape
-
-    def run_backward(self, tape, grad_out_nchw, reducer=None):
-        """-> {parameter: gradient}.  Walks the tape backwards; gradients that meet at a Bottleneck input are summed
-        by the residual input of the data-gradient conv (no separate add kernel)."""
-        if tape and tape[0].get("fused"):
-            return self.run_backward_fused(tape, grad_out_nchw, reducer)
-        grads = _GradDict(reducer)
-        # Measured (resnet_h, 400x400, one MI355X): +6.5 / +5.7 / +5.3 % at 16 / 32 / 64 frames, -2.7 % at 128, where
-        # every kernel already fills the chip and the two streams only disturb each other's L2.
-        stem_x = tape[0]["x"]                                  # im2col of the input: [B, H/2, W/2, 160]
-        input_px = 4 * int(stem_x.shape[0]) * int(stem_x.shape[1]) * int(stem_x.shape[2])
-        side = _SideStream.create(grad_out_nchw, self.overlap_wgrad and input_px <= self.overlap_max_frames * 400 * 400)
-        g = None                 # gradient w.r.t. the output of the unit being processed
-        block = None             # state of the Bottleneck being unwound
-        for rec in reversed(tape):
-            kind = rec["kind"]
-            if kind == "final":
-                m = rec["conv"]
-                cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
-                gy = ops.nchw_to_nhwc(grad_out_nchw, cpad=ops.round_up(cout, 16))
-                def leaf(m=m, x=rec["x"], gy=gy, cout=cout, cin=cin):
-                    grads[m.weight], grads[m.bias] = ops.conv2d_wgrad(x, gy, cout, cin, 1, 1, 0, want_bias=True)
-                _on_side(side, leaf, rec["x"], gy)
-                packed_t, rows, _ = self._packed_w(rec["name"], m, 1)
-                g = ops.conv2d(gy, packed_t, rows, 1, 1)
-            elif kind == "convT":
-                m, bn = rec["conv"], rec["bn"]
-                dz, _, dgam, dbet = ops.bn_train_bwd(rec["z"], g, rec["y"], bn.weight, rec["mean"], rec["invstd"], True)
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                def leaf(m=m, x=rec["x"], dz=dz):
-                    if ops.convT4x4_wgrad_winograd_applies(x, dz):        # nine-position minimal filtering + the bias sums, one launch
-                        grads[m.weight], grads[m.bias] = ops.convT4x4_wgrad_winograd(x, dz)
-                    else:
-                        grads[m.weight] = ops.convT4x4_wgrad(x, dz)
-                        grads[m.bias] = ops.channel_sum(dz)
-                _on_side(side, leaf, rec["x"], dz)
-                cin_t, cout_t = int(m.weight.shape[0]), int(m.weight.shape[1])
-                if (self.convT_algorithm == "winograd" and cout_t % 16 == 0 and cout_t >= 32 and cin_t > 64
-                        and int(dz.shape[3]) == cout_t and dz.shape[1] % 2 == 0 and dz.shape[2] % 2 == 0):
-                    tile = ops.conv4x4s2_winograd_tile_of(dz, cin_t)
-                    u4b, rows = self._cached(("wu4b", rec["name"], tile), [m.weight], lambda m=m, tile=tile: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile, 1))
-                    g = ops.conv4x4s2_winograd_tile(tile, dz, u4b, rows)
-                else:
-                    pk, rows = self._cached(("wTb", rec["name"]), [m.weight], lambda m=m: ops.pack_convT4x4_bwd_weight(m.weight.detach()))
-                    g = ops.conv4x4s2(dz, pk, rows)
-            elif kind == "block_end":
-                block = dict(g_out=g, g_idt=None, g_ds=None)
-            elif kind == "conv":
-                conv, bn, name = rec["conv"], rec["bn"], rec["name"]
-                cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
-                is_ds = name.endswith(".ds")
-                dy = block["g_idt"] if is_ds else g
-                dz, gm, dgam, dbet = ops.bn_train_bwd(rec["z"], dy, rec["y"], bn.weight, rec["mean"], rec["invstd"],
-                                                      rec["relu"], want_g=rec["has_res"])
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                if rec["has_res"]:
-                    block["g_idt"] = gm          # masked block-output gradient == gradient of the identity branch
-                def leaf(conv=conv, x=rec["x"], dz=dz, cout=cout, cin=cin, k=rec["k"], stride=rec["stride"]):
-                    if self._wino_train(conv) and ops.wgrad_winograd_pays(int(dz.shape[0]) * int(dz.shape[1]) * int(dz.shape[2]), cin, cout):
-                        grads[conv.weight] = ops.conv3x3_wgrad_winograd(x, dz, cout, cin, want_bias=False)[0]
-                    else:
-                        if self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and ops.conv1x1_wgrad_applies(x, dz, cout):
-                            grads[conv.weight] = ops.conv1x1_wgrad(x, dz, cout, cin)
-                        else:
-                            grads[conv.weight] = ops.conv2d_wgrad(x, dz, cout, cin, k, stride)[0]
-                _on_side(side, leaf, rec["x"], dz)
-                in_hw = (int(rec["x"].shape[1]), int(rec["x"].shape[2]))
-                if is_ds:
-                    block["g_ds"] = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-                elif name.endswith(".1"):
-                    # block input: main-path gradient + identity / downsample gradient
-                    block["dz1"] = (name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-                else:
-                    g = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-            elif kind == "block_begin":
-                name1, conv1, dz, cin, k, stride, in_hw = block["dz1"]
-                other = block["g_ds"] if rec["ds"] else block["g_idt"]
-                g = self._bwd_data(name1, conv1, dz, cin, k, stride, in_hw, residual=other)
-                block = None
-                _early_bucket_hook(reducer, rec["name"], side, lambda: [grads[p] for p in self._early_bucket_params()])
-            elif kind == "pool":
-                g = ops.maxpool3s2_bwd(g, rec["x"])
-            elif kind == "stem":
-                bn = rec["bn"]
-                dz, _, dgam, dbet = ops.bn_train_bwd(rec["z"], g, rec["y"], bn.weight, rec["mean"], rec["invstd"], True)
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                dw, _ = ops.conv2d_wgrad(rec["x"], dz, 64, 160, 1, 1)
-                grads[rec["conv"].weight] = dw.reshape(64, 160)[:, :147].reshape(64, 3, 7, 7).contiguous()
-                g = None
-        if side is not None:
-            side.join()
-        return grads
-
-    # ---- training, round 4: BatchNorm folded into its neighbours (csrc/bn.hip "round 4", csrc/gemm1x1.hip PRE / EPI) -------------
+    # One forward walk and one tape-driven backward.  ``bn_fusion`` (round 4, csrc/bn.hip "round 4", csrc/gemm1x1.hip PRE / EPI) chooses
+    # the BatchNorm form of every unit when it is RECORDED: off = the three-launch kernels of rounds 1-3 (bn_train_fwd / bn_train_bwd);
+    # on = statistics finished inside the launch that sums them, BatchNorm + ReLU applied by the consuming 1x1 conv's loader, the backward
+    # reductions in the data-gradient epilogue -- such a record carries ``ab``, and only such records are eligible for the GEMM forms of
+    # round 6 (sub2, col3, the stem on 192 columns, convT on the GEMM, the head behind the BatchNorm loader, materialize=False).  The
+    # backward unwinds every record the way it was recorded, whatever the attribute says by then.
     def _ctr(self, device):
         """Allocator of zero ticket words for the BatchNorm launches of this replica (ops.bn_counter_buffer: every launch takes its own
         slice of one persistent buffer and leaves it zero; the cursor restarts with every forward pass)."""
@@ -1646,197 +1517,200 @@ class ResnetSimple(nn.Module):
             return out
         return take
 
-    def _unit_fused(self, tape, name, x, conv, bn, relu, residual=None, pre=None, materialize=True):
-        """conv -> BatchNorm(batch statistics) (+ residual) (ReLU).  ``x``: the conv's input tensor, or -- with ``pre`` = the record of
-        the producing unit -- that unit's un-normalised output z, whose BatchNorm + ReLU this conv applies while loading.
-        ``materialize=False``: the normalised output is left to the consumer's loader (returns the record instead of a tensor)."""
+    def _bn_fwd(self, rec, residual=None, materialize=True):
+        """Train-mode BatchNorm (+ residual) (ReLU) of rec["z"] -> rec["y"].  bn_fusion on: the statistics in one launch of their own unless
+        the producing launch finished them (rec["ab"] set), then the apply pass -- which ``materialize=False`` leaves to the consumer's
+        loader (y stays None)."""
+        if not self.bn_fusion:
+            rec["y"], rec["mean"], rec["invstd"] = ops.bn_train_fwd(rec["z"], rec["bn"], residual, rec["relu"])
+            return
+        if rec["ab"] is None:
+            rec["ab"], rec["mean"], rec["invstd"] = ops.bn_stats(rec["z"], rec["bn"], self._ctr(rec["z"].device))
+        if materialize:
+            rec["y"] = ops.bn_apply_ab(rec["z"], rec["ab"], residual, rec["relu"])
+
+    def _unit(self, tape, name, x, conv, bn, relu, residual=None, pre=None, materialize=True):
+        """conv -> BatchNorm(batch statistics) (+ residual) (ReLU) -> the tape record (output: rec["y"]).  ``x``: the conv's input tensor,
+        or -- with ``pre`` = the record of the producing unit -- that unit's un-normalised output z, whose BatchNorm + ReLU this conv
+        applies while loading.  ``materialize``: see _bn_fwd."""
+        fused = self.bn_fusion
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         bias = conv.bias.detach() if conv.bias is not None else None
         cout = int(conv.weight.shape[0])
-        sub2 = None
-        if (self.ds_on_gemm and k == 1 and stride == 2 and pre is None and self.conv1x1_algorithm == "gemm"
+        sub2 = col3 = None
+        if (fused and self.ds_on_gemm and stride == 2 and pre is None and self.conv1x1_algorithm == "gemm"
                 and int(conv.weight.shape[1]) == int(x.shape[3]) and int(x.shape[3]) % 64 == 0):
-            # Round 6: a stride-2 1x1 conv (the trunk's three downsample branches) reads every second pixel of every second row: gathered
-            # once (ops.subsample2), it IS a stride-1 1x1 conv -- the GEMM kernel with the BatchNorm statistics in its epilogue instead of the
-            # direct kernel + a statistics pass; its weight gradient and its data gradient (scattered back onto the block input's grid in
-            # run_backward_fused) are GEMMs as well
-            xs = ops.subsample2(x)
-            if ops.conv1x1_applies(xs, cout):
-                sub2, x, stride = (int(x.shape[1]), int(x.shape[2])), xs, 1
-        col3 = None
-        if (self.ds_on_gemm and k == 3 and stride == 2 and pre is None and self.conv1x1_algorithm == "gemm" and int(conv.padding[0]) == 1
-                and int(conv.weight.shape[1]) == int(x.shape[3]) and int(x.shape[3]) % 64 == 0 and cout % 64 == 0
-                and int(x.shape[0]) * ((int(x.shape[1]) - 1) // 2 + 1) * ((int(x.shape[2]) - 1) // 2 + 1) <= self.COL3_MAX_PIXELS):
-            # ... and a 3x3 stride-2 conv with too few output pixels for the direct kernel to fill the chip (layer4.0.conv2 at 16 frames:
-            # 2704; 36 TFLOP/s) runs on the GEMM over its patch rows (ops.im2col3s2: [pixels][9 Cin]), in all three directions as well
-            col3 = (int(x.shape[1]), int(x.shape[2]))
-            x, k, stride = ops.im2col3s2(x), 1, 1
+            if k == 1:
+                # Round 6: a stride-2 1x1 conv (the trunk's three downsample branches) reads every second pixel of every second row:
+                # gathered once (ops.subsample2), it IS a stride-1 1x1 conv -- the GEMM kernel with the BatchNorm statistics in its epilogue
+                # instead of the direct kernel + a statistics pass; its weight gradient and its data gradient (scattered back onto the block
+                # input's grid in run_backward) are GEMMs as well
+                xs = ops.subsample2(x)
+                if ops.conv1x1_applies(xs, cout):
+                    sub2, x, stride = (int(x.shape[1]), int(x.shape[2])), xs, 1
+            elif (k == 3 and int(conv.padding[0]) == 1 and cout % 64 == 0
+                  and int(x.shape[0]) * ((int(x.shape[1]) - 1) // 2 + 1) * ((int(x.shape[2]) - 1) // 2 + 1) <= self.COL3_MAX_PIXELS):
+                # ... and a 3x3 stride-2 conv with too few output pixels for the direct kernel to fill the chip (layer4.0.conv2 at 16
+                # frames: 2704; 36 TFLOP/s) runs on the GEMM over its patch rows (ops.im2col3s2: [pixels][9 Cin]), in all three directions
+                col3 = (int(x.shape[1]), int(x.shape[2]))
+                x, k, stride = ops.im2col3s2(x), 1, 1
         rec = dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, pre=pre, k=k, stride=stride, has_res=residual is not None,
-                   y=None, sub2=sub2, col3=col3)
-        if self._gemm1x1(conv, x) or sub2 is not None or col3 is not None:
-            if col3 is not None:       # GEMM weight [Cout][t Cin + c] = w[co][c][ky][kx]
-                packed, rows = self._cached(("g0", name), [conv.weight], lambda: ops.pack_conv1x1_weight(
-                    conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 0))
+                   y=None, ab=None, sub2=sub2, col3=col3)
+        if col3 is not None or self._gemm1x1(conv, x, k, stride):
+            packed, rows = self._g(name, conv, 0, col3 is not None)
+            if fused:
+                rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn(
+                    x, packed, rows, bn, self._ctr(x.device), pre_ab=None if pre is None else pre["ab"], shift=bias)
             else:
-                packed, rows = self._cached(("g0", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 0))
-            rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn(
-                x, packed, rows, bn, self._ctr(x.device), pre_ab=None if pre is None else pre["ab"], shift=bias)
+                rec["z"] = ops.conv1x1(x, packed, rows, None, bias, None, 0)
         else:
             assert pre is None
-            z = None
             if self._wino_train(conv):
                 tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), int(conv.weight.shape[1]), cout, int(x.shape[0]))
-                u, rows = self._cached(("wino", name, tile), [conv.weight], lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), 0, tile))
-                if self.bn_fusion_3x3 and tile == 2 and cout % 64 == 0:
+                u, rows = self._wino(name, conv, 0, tile)
+                if fused and self.bn_fusion_3x3 and tile == 2 and cout % 64 == 0:
                     # the statistics ride in the F(2x2) kernel's epilogue: no separate pass over z
                     rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv3x3_winograd_bn(x, u, rows, bn, self._ctr(x.device), shift=bias)
                 else:
-                    z = ops.conv3x3_winograd_tile(tile, x, u, rows, None, bias, None, 0)
+                    rec["z"] = ops.conv3x3_winograd_tile(tile, x, u, rows, None, bias, None, 0)
             else:
                 packed, rows, _ = self._packed_w(name, conv, 0)
-                z = ops.conv2d(x, packed, rows, k, stride, None, bias, None, 0)
-            if z is not None:
-                rec["z"] = z
-                rec["ab"], rec["mean"], rec["invstd"] = ops.bn_stats(z, bn, self._ctr(x.device))
+                rec["z"] = ops.conv2d(x, packed, rows, k, stride, None, bias, None, 0)
         tape.append(rec)
-        if not materialize:
-            return rec
-        rec["y"] = ops.bn_apply_ab(rec["z"], rec["ab"], residual, relu)
-        return rec["y"]
+        self._bn_fwd(rec, residual, materialize)
+        return rec
 
-    def run_forward_train_fused(self, x):
-        self._repack_weights(split=True)
-        self._ctr_pos = 0
-        tape = [dict(kind="begin", fused=True)]
+    def _wino_train(self, conv):
+        """Training: the stride-1 3x3 convs of the bottlenecks (forward and data gradient) on the Winograd kernel."""
+        return (self.conv_algorithm == "winograd" and int(conv.kernel_size[0]) == 3 and int(conv.stride[0]) == 1
+                and int(conv.weight.shape[1]) % 16 == 0 and int(conv.weight.shape[0]) % 16 == 0
+                and min(int(conv.weight.shape[0]), int(conv.weight.shape[1])) >= 64)
+
+    def _head_on_gemm(self, head, z):
+        """Does the decoder's head conv (the module behind the last ConvTranspose2d + BatchNorm + ReLU) run on the 1x1 GEMM with that
+        BatchNorm in its loader?  (a 1x1 conv from a multiple of 64 channels, tensors within the GEMM's 2-GB operand limit)"""
+        return (self.bn_fusion and self.bn_fusion_head and isinstance(head, nn.Conv2d) and self.conv1x1_algorithm == "gemm"
+                and int(head.kernel_size[0]) == 1 and int(head.stride[0]) == 1 and head.bias is not None
+                and int(head.weight.shape[1]) == int(z.shape[3]) and int(z.shape[3]) % 64 == 0
+                and (z.numel() // int(z.shape[3]) + 64) * int(z.shape[3]) * 4 < (1 << 31))
+
+    def run_forward_train(self, x):
+        """-> (belief maps NCHW, tape)."""
+        fused = self.bn_fusion
+        self._repack_weights(split=fused)
+        if fused:
+            self._ctr_pos = 0
+        tape = []
         ho, wo = (int(x.shape[2]) + 6 - 7) // 2 + 1, (int(x.shape[3]) + 6 - 7) // 2 + 1
-        if self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and (int(x.shape[0]) * ho * wo + 64) * 192 * 4 < (1 << 31):
+        stem = dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, y=None, ab=None)
+        if fused and self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and (int(x.shape[0]) * ho * wo + 64) * 192 * 4 < (1 << 31):
             # Round 6: the 7x7 stem as a GEMM over im2col rows of 192 columns (147 taps, zero-padded to the 1x1 GEMM's granularity -- 160
             # for the direct kernel): the BatchNorm statistics ride in its epilogue (one pass over the 16 x 200 x 200 x 64 output less) and
             # its weight gradient runs on the GEMM-shaped kernel (0.56 -> ~0.2 ms on the MAIN stream: it is the last launch of a step)
-            col = ops.im2col_nchw(x, 7, 7, 2, 3, 192)
-            def build():
-                w2 = self.conv1.weight.detach().reshape(64, 147)
-                return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((64, 45))], dim=1).reshape(64, 192, 1, 1), 0)
-            packed, _ = self._cached(("g0", "conv1"), [self.conv1.weight], build)
-            z, ab, mean, invstd = ops.conv1x1_bn(col, packed, 64, self.bn1, self._ctr(col.device))
+            stem["x"] = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0"])
+            stem["z"], stem["ab"], stem["mean"], stem["invstd"] = ops.conv1x1_bn(
+                stem["x"], self._stem_weight("g0"), 64, self.bn1, self._ctr(stem["x"].device))
         else:
-            col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
-            w1 = self._cached(("w", "conv1"), [self.conv1.weight],
-                              lambda: ops.pack_matrix_weight(self.conv1.weight.detach().reshape(64, 147), 160))
-            z = ops.conv2d(col, w1[0], 64, 1, 1)
-            ab, mean, invstd = ops.bn_stats(z, self.bn1, self._ctr(z.device))
-        y = ops.bn_apply_ab(z, ab, None, True)
-        tape.append(dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, x=col, z=z, y=y, ab=ab, mean=mean, invstd=invstd))
-        yp, pidx = ops.maxpool3s2_idx(y)               # the backward pass compares one stored byte per window
-        tape.append(dict(kind="pool", x=y, idx=pidx))
-        y = yp
-        for li in (1, 2, 3, 4):
-            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
-                name = "layer%d.%d" % (li, bi)
-                tape.append(dict(kind="block_begin", name=name, ds=hasattr(blk, "downsample")))
-                idt = y
-                if hasattr(blk, "downsample"):
-                    idt = self._unit_fused(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
-                o = self._unit_fused(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True)
-                # conv2's BatchNorm + ReLU is applied by conv3's loader when conv3 runs on the GEMM kernel (always, for ResNet-101)
-                r2 = self._unit_fused(tape, name + ".2", o, blk.conv2, blk.bn2, relu=True, materialize=False)
+            stem["x"] = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["w"])
+            stem["z"] = ops.conv2d(stem["x"], self._stem_weight("w"), 64, 1, 1)
+        self._bn_fwd(stem)
+        tape.append(stem)
+        if fused:
+            y, pidx = ops.maxpool3s2_idx(stem["y"])        # the backward pass compares one stored byte per window
+        else:
+            y, pidx = ops.maxpool3s2(stem["y"]), None
+        tape.append(dict(kind="pool", x=stem["y"], idx=pidx))
+        for name, blk in self._trunk():
+            ds = hasattr(blk, "downsample")
+            tape.append(dict(kind="block_begin", name=name, ds=ds))
+            idt = y
+            if ds:
+                idt = self._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)["y"]
+            o = self._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True)["y"]
+            # fused: conv2's BatchNorm + ReLU is applied by conv3's loader when conv3 runs on the GEMM kernel (always, for ResNet-101)
+            r2 = self._unit(tape, name + ".2", o, blk.conv2, blk.bn2, relu=True, materialize=not fused)
+            pre = None
+            if fused:
                 # ... and when the BACKWARD GEMM applies too: conv3's data gradient (conv1x1_bwd_bnmask) reads dz3, which has 4x the
                 # channels of z2 and crosses the kernel's 2-GB offset limit first; relu(BN(z2)) is never stored on this path, so the
                 # decision has to be made here (round-4 advice: ~210 frames of 400x400 per GPU would pass the forward and raise in the backward)
                 z2 = r2["z"]
                 dz3_fits = int(z2.shape[0]) * int(z2.shape[1]) * int(z2.shape[2]) * int(blk.conv3.weight.shape[0]) * 4 < (1 << 31)
-                if self._gemm1x1(blk.conv3, r2["z"]) and dz3_fits:
-                    y = self._unit_fused(tape, name + ".3", r2["z"], blk.conv3, blk.bn3, relu=True, residual=idt, pre=r2)
+                if self._gemm1x1(blk.conv3, z2) and dz3_fits:
+                    pre = r2
                 else:
-                    r2["y"] = ops.bn_apply_ab(r2["z"], r2["ab"], None, True)
-                    y = self._unit_fused(tape, name + ".3", r2["y"], blk.conv3, blk.bn3, relu=True, residual=idt)
-                tape.append(dict(kind="block_end", name=name))
-        seqs = [("upsample", self.upsample)] + ([("upsample2", self.upsample2)] if self.full else [])
-        for sname, seq in seqs:
-            mods = list(seq)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                name = "%s.%d" % (sname, i)
-                if isinstance(m, nn.ConvTranspose2d):
-                    bn = mods[i + 1]
-                    co_t = int(m.weight.shape[1])
-                    gT = self._convT_gemm(name, m, y)
-                    if gT is not None:
-                        # Round 6: a transposed conv on a small map (the first decoder layer: 2048 -> 256 on 13 x 13 maps, 2704 pixels at 16
-                        # frames -- 50-100 workgroups of the Winograd kernel on 256 CUs) as ONE 1x1 GEMM with N = 16 Cout (the sixteen tap
-                        # contributions of every input pixel) + a gather that sums the <= 4 contributions landing on each output pixel
-                        z = ops.col2im4s2(ops.conv1x1(y, gT[0], gT[1], None, None, None, ops.CONV_NO_KSPLIT), co_t, m.bias.detach() if m.bias is not None else None)
-                    elif self.convT_algorithm == "winograd" and ops.convT4x4_winograd_applies(y, int(m.weight.shape[1])):
-                        tile = ops.convT4x4_winograd_tile(y, int(m.weight.shape[1]))
-                        u4, cout = self._cached(("wu4", name, tile), [m.weight], lambda m=m, tile=tile: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile))
-                        z = ops.conv_transpose4x4s2_winograd_tile(tile, y, u4, cout, None, m.bias.detach(), 0)
-                    else:
-                        packed, cout = self._cached(("w", name), [m.weight], lambda m=m: ops.pack_convT4x4_weight(m.weight.detach()))
-                        z = ops.conv_transpose4x4s2(y, packed, cout, None, m.bias.detach(), 0)
-                    ab, mean, invstd = ops.bn_stats(z, bn, self._ctr(z.device))
-                    # Round 6: the LAST decoder layer's normalised activation is consumed by the head conv only -- which applies the
-                    # BatchNorm + ReLU in its loader (and so do its weight gradient and the mask of its data gradient): never stored
-                    head = mods[i + 3] if i + 3 < len(mods) else None
-                    y2 = None if self._head_on_gemm(head, z) else ops.bn_apply_ab(z, ab, None, True)
-                    tape.append(dict(kind="convT", name=name, conv=m, bn=bn, relu=True, x=y, z=z, y=y2, ab=ab, mean=mean, invstd=invstd))
-                    y = y2
-                    i += 3
-                elif y is None:                                   # the head conv on the 1x1 GEMM, behind the BatchNorm loader
-                    prev = tape[-1]
-                    cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
-                    n4 = ops.round_up(cout, 4)
-                    def build(m=m, n4=n4, cout=cout, cin=cin):
-                        w2 = m.weight.detach().reshape(cout, cin)
-                        return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((n4 - cout, cin))]).reshape(n4, cin, 1, 1), 0)
-                    packed, _ = self._cached(("g0h", name), [m.weight], build)
-                    bias4 = self._cached(("g0hb", name), [m.bias], lambda m=m, n4=n4, cout=cout: torch.cat([m.bias.detach(), m.bias.new_zeros((n4 - cout,))]))
-                    out = ops.nhwc_to_nchw(ops.conv1x1_pre(prev["z"], packed, n4, prev["ab"], bias4))
-                    if n4 != cout:
-                        out = out[:, :cout].contiguous()
-                    tape.append(dict(kind="final", name=name, conv=m, x=None))
-                    y = out
-                    i += 1
-                else:
-                    packed, rows, _ = self._packed_w(name, m, 0)
-                    out = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
-                    tape.append(dict(kind="final", name=name, conv=m, x=y))
-                    y = out
-                    i += 1
+                    r2["y"] = ops.bn_apply_ab(z2, r2["ab"], None, True)
+            y = self._unit(tape, name + ".3", r2["y"] if pre is None else r2["z"], blk.conv3, blk.bn3, relu=True, residual=idt, pre=pre)["y"]
+            tape.append(dict(kind="block_end", name=name))
+        stages = list(self._decoder())
+        for j, (name, m, bn) in enumerate(stages):
+            if bn is not None:
+                z = self._convT_forward(name, m, y, None, m.bias.detach() if m.bias is not None else None, 0, gemm=fused)
+                rec = dict(kind="convT", name=name, conv=m, bn=bn, relu=True, x=y, z=z, y=None, ab=None)
+                # Round 6: the LAST decoder layer's normalised activation is consumed by the head conv only -- which applies the
+                # BatchNorm + ReLU in its loader (and so do its weight gradient and the mask of its data gradient): never stored
+                head = stages[j + 1][1] if j + 1 < len(stages) else None
+                self._bn_fwd(rec, materialize=not self._head_on_gemm(head, z))
+                tape.append(rec)
+                y = rec["y"]
+            elif y is None:                                   # the head conv on the 1x1 GEMM, behind the BatchNorm loader
+                prev = tape[-1]
+                cout = int(m.weight.shape[0])
+                n4 = ops.round_up(cout, 4)
+                packed = self._g_head(name, m, 0, n4)
+                bias4 = self._cached(("g0hb", name), [m.bias], lambda: torch.cat([m.bias.detach(), m.bias.new_zeros((n4 - cout,))]))
+                y = ops.nhwc_to_nchw(ops.conv1x1_pre(prev["z"], packed, n4, prev["ab"], bias4))
+                if n4 != cout:
+                    y = y[:, :cout].contiguous()
+                tape.append(dict(kind="final", name=name, conv=m, x=None))
+            else:
+                packed, rows, _ = self._packed_w(name, m, 0)
+                tape.append(dict(kind="final", name=name, conv=m, x=y))
+                y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
         return y, tape
 
-    def _head_on_gemm(self, head, z):
-        """Does the decoder's head conv (the module behind the last ConvTranspose2d + BatchNorm + ReLU) run on the 1x1 GEMM with that
-        BatchNorm in its loader?  (a 1x1 conv from a multiple of 64 channels, tensors within the GEMM's 2-GB operand limit)"""
-        return (self.bn_fusion_head and isinstance(head, nn.Conv2d) and self.conv1x1_algorithm == "gemm" and int(head.kernel_size[0]) == 1
-                and int(head.stride[0]) == 1 and head.bias is not None and int(head.weight.shape[1]) == int(z.shape[3]) and int(z.shape[3]) % 64 == 0
-                and (z.numel() // int(z.shape[3]) + 64) * int(z.shape[3]) * 4 < (1 << 31))
-
-    def _bn_bwd_fused(self, rec, dy, want_g=False):
-        """BatchNorm backward of a unit in two launches: (dgamma, dbeta) finished inside the reduction launch, then dz (and the masked
-        gradient g when the Bottleneck's identity branch needs it).  The ReLU mask comes from the stored activation where the forward
-        pass wrote one, else it is recomputed from (z, ab).  ``dy`` = ("masked", g, dgamma, dbeta): the consumer's data-gradient
-        epilogue already masked and summed (conv1x1_bwd_bnmask) -- one launch."""
+    def _bn_bwd(self, rec, dy, want_g=False):
+        """BatchNorm backward of a unit -> (dz, g or None, dgamma, dbeta), as the unit was recorded.  Without ``ab``: the three-launch
+        kernel.  With: two launches -- (dgamma, dbeta) finished inside the reduction launch, then dz (and the masked gradient g when the
+        Bottleneck's identity branch needs it); the ReLU mask comes from the stored activation where the forward pass wrote one, else it
+        is recomputed from (z, ab).  ``dy`` = ("masked", g, dgamma, dbeta): the consumer's data-gradient epilogue already masked and
+        summed (conv1x1_bwd_bnmask) -- one launch."""
         bn = rec["bn"]
-        dev, c = rec["z"].device, int(rec["z"].shape[3])
+        if rec["ab"] is None:
+            return ops.bn_train_bwd(rec["z"], dy, rec["y"], bn.weight, rec["mean"], rec["invstd"], rec["relu"], want_g=want_g)
         if isinstance(dy, tuple):
             _, g, dgam, dbet = dy
             dz, _ = ops.bn_bwd_apply(rec["z"], g, bn.weight, rec["mean"], rec["invstd"], dgam, dbet)
             return dz, g, dgam, dbet
         y_act = rec["y"] if rec["relu"] else None
         ab = rec["ab"] if (rec["relu"] and y_act is None) else None
-        dgam, dbet = ops.bn_bwd_stats(rec["z"], dy, rec["mean"], rec["invstd"], self._ctr(dev), y_act=y_act, ab=ab)
+        dgam, dbet = ops.bn_bwd_stats(rec["z"], dy, rec["mean"], rec["invstd"], self._ctr(rec["z"].device), y_act=y_act, ab=ab)
         dz, g = ops.bn_bwd_apply(rec["z"], dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=want_g)
         return dz, g, dgam, dbet
 
-    def run_backward_fused(self, tape, grad_out_nchw, reducer=None):
-        """run_backward for a tape of run_forward_train_fused."""
+    def _bwd_data(self, name, conv, dz, cin, k, stride, in_hw, residual=None):
+        if self._wino_train(conv):
+            tile = ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), int(conv.weight.shape[0]), int(conv.weight.shape[1]), int(dz.shape[0]))
+            u_t, rows = self._wino(name, conv, 1, tile)
+            return ops.conv3x3_winograd_tile(tile, dz, u_t, rows, None, None, residual, 0)
+        if self._gemm1x1(conv, dz, k, stride, bwd=True):
+            packed_t, rows = self._g(name, conv, 1)
+            return ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
+        packed_t, rows, _ = self._packed_w(name, conv, 1)
+        return ops.conv2d_bwd_data(dz, packed_t, cin, k, stride, in_hw, residual=residual)
+
+    def run_backward(self, tape, grad_out_nchw, reducer=None):
+        """-> {parameter: gradient}.  Walks the tape backwards; gradients that meet at a Bottleneck input are summed
+        by the residual input of the data-gradient conv (no separate add kernel).  A gradient that a data-gradient launch already masked
+        and reduced for its producer's BatchNorm travels as ("masked", g, dgamma, dbeta) (_bn_bwd)."""
         grads = _GradDict(reducer)
-        stem_x = tape[1]["x"]
+        # Measured (resnet_h, 400x400, one MI355X): +6.5 / +5.7 / +5.3 % at 16 / 32 / 64 frames, -2.7 % at 128, where
+        # every kernel already fills the chip and the two streams only disturb each other's L2.
+        stem_x = tape[0]["x"]                                  # im2col of the input: [B, H/2, W/2, 160 or 192]
         input_px = 4 * int(stem_x.shape[0]) * int(stem_x.shape[1]) * int(stem_x.shape[2])
         side = _SideStream.create(grad_out_nchw, self.overlap_wgrad and input_px <= self.overlap_max_frames * 400 * 400)
-        g = None
-        block = None
+        g = None                 # gradient w.r.t. the output of the unit being processed
+        block = None             # state of the Bottleneck being unwound
         for idx in range(len(tape) - 1, -1, -1):
             rec = tape[idx]
             kind = rec["kind"]
@@ -1855,7 +1729,7 @@ class ResnetSimple(nn.Module):
                     def leaf(m=m, x=rec["x"], gy=gy, cout=cout, cin=cin):
                         grads[m.weight], grads[m.bias] = ops.conv2d_wgrad(x, gy, cout, cin, 1, 1, 0, want_bias=True)
                     _on_side(side, leaf, rec["x"], gy)
-                if (self.bn_fusion_head and prev is not None and prev["kind"] == "convT" and prev["y"] is rec["x"] and prev.get("ab") is not None
+                if (self.bn_fusion_head and prev is not None and prev["kind"] == "convT" and prev["y"] is rec["x"] and prev["ab"] is not None
                         and self.conv1x1_algorithm == "gemm" and int(m.kernel_size[0]) == 1 and cin % 64 == 0
                         and tuple(prev["z"].shape) == tuple(gy.shape[:3]) + (cin,) and prev["z"].numel() < (1 << 31)
                         and (prev["z"].numel() // cin) * ops.round_up(cout, 32) * 4 < (1 << 31)):
@@ -1865,19 +1739,15 @@ class ResnetSimple(nn.Module):
                     # to the GEMM's 32.
                     kp = ops.round_up(cout, 32)
                     gy32 = gy if int(gy.shape[3]) == kp else ops.nchw_to_nhwc(grad_out_nchw, cpad=kp)
-                    def build(m=m, kp=kp, cout=cout, cin=cin):
-                        w2 = m.weight.detach().reshape(cout, cin)
-                        return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((kp - cout, cin))]).reshape(kp, cin, 1, 1), 1)
-                    packed_t, _ = self._cached(("g1h", rec["name"]), [m.weight], build)
-                    gmask, dgh, dbh = ops.conv1x1_bwd_bnmask(gy32, packed_t, cin, prev["z"], prev["ab"], prev["mean"], prev["invstd"],
-                                                             self._ctr(gy32.device), y_act=prev["y"])      # (y None: the mask from (z, ab))
+                    gmask, dgh, dbh = ops.conv1x1_bwd_bnmask(gy32, self._g_head(rec["name"], m, 1, kp), cin, prev["z"], prev["ab"], prev["mean"],
+                                                             prev["invstd"], self._ctr(gy32.device), y_act=prev["y"])   # (y None: the mask from (z, ab))
                     g = ("masked", gmask, dgh, dbh)
                 else:
                     packed_t, rows, _ = self._packed_w(rec["name"], m, 1)
                     g = ops.conv2d(gy, packed_t, rows, 1, 1)
             elif kind == "convT":
                 m, bn = rec["conv"], rec["bn"]
-                dz, _, dgam, dbet = self._bn_bwd_fused(rec, g)
+                dz, _, dgam, dbet = self._bn_bwd(rec, g)
                 grads[bn.weight], grads[bn.bias] = dgam, dbet
                 def leaf(m=m, x=rec["x"], dz=dz):
                     if ops.convT4x4_wgrad_winograd_applies(x, dz):        # nine-position minimal filtering + the bias sums, one launch
@@ -1902,12 +1772,12 @@ class ResnetSimple(nn.Module):
                 cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
                 is_ds = name.endswith(".ds")
                 dy = block["g_idt"] if is_ds else g
-                dz, gm, dgam, dbet = self._bn_bwd_fused(rec, dy, want_g=rec["has_res"])
+                dz, gm, dgam, dbet = self._bn_bwd(rec, dy, want_g=rec["has_res"])
                 grads[bn.weight], grads[bn.bias] = dgam, dbet
                 if rec["has_res"]:
                     block["g_idt"] = gm          # masked block-output gradient == gradient of the identity branch
                 pre = rec["pre"]
-                def leaf(conv=conv, x=rec["x"], dz=dz, cout=cout, cin=cin, k=rec["k"], stride=rec["stride"], pre=pre, col3=rec.get("col3")):
+                def leaf(conv=conv, x=rec["x"], dz=dz, cout=cout, cin=cin, k=rec["k"], stride=rec["stride"], pre=pre, col3=rec["col3"]):
                     if col3 is not None:         # the conv ran on its patch rows: dW [Cout][t Cin + c] -> [Cout][Cin][3][3]
                         dw2 = ops.conv1x1_wgrad(x, dz, cout, 9 * cin)
                         grads[conv.weight] = dw2.reshape(cout, 3, 3, cin).permute(0, 3, 1, 2).contiguous()
@@ -1927,31 +1797,31 @@ class ResnetSimple(nn.Module):
                 in_hw = (int(rec["x"].shape[1]), int(rec["x"].shape[2]))
                 if is_ds:
                     block["g_ds"] = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-                    if rec.get("sub2") is not None:       # the conv ran on the gathered pixels: its data gradient back on the input's grid
+                    if rec["sub2"] is not None:           # the conv ran on the gathered pixels: its data gradient back on the input's grid
                         block["g_ds"] = ops.scatter2(block["g_ds"], *rec["sub2"])
                 elif name.endswith(".1"):
+                    # block input: main-path gradient + identity / downsample gradient
                     block["dz1"] = (name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
                 elif pre is not None:
                     # data gradient + the ReLU mask and the two reductions of the producer's BatchNorm in ONE launch
-                    packed_t, rows = self._cached(("g1", name), [conv.weight], lambda: ops.pack_conv1x1_weight(conv.weight.detach(), 1))
+                    packed_t, rows = self._g(name, conv, 1)
                     gmask, dg2, db2 = ops.conv1x1_bwd_bnmask(dz, packed_t, cin, pre["z"], pre["ab"], pre["mean"], pre["invstd"],
                                                             self._ctr(dz.device))
                     g = ("masked", gmask, dg2, db2)
                 else:
                     prod = tape[idx - 1]
                     if (self.bn_fusion_3x3 and self._wino_train(conv) and cin % 64 == 0 and int(dz.shape[3]) == cout
-                            and prod["kind"] == "conv" and prod["y"] is rec["x"] and prod["relu"] and not prod["has_res"]
+                            and prod["kind"] == "conv" and prod["ab"] is not None and prod["y"] is rec["x"] and prod["relu"] and not prod["has_res"]
                             and ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), cout, cin, int(dz.shape[0])) == 2):
                         # data gradient + the ReLU mask and the two reductions of the producer's BatchNorm in ONE launch of the
                         # F(2x2) kernel (the mask is recomputed from the producer's (z, ab) exactly as its apply pass evaluated it)
-                        u_t, _ = self._cached(("wino1", name, 2), [conv.weight], lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), 1, 2))
+                        u_t, _ = self._wino(name, conv, 1, 2)
                         gmask, dg1, db1 = ops.conv3x3_winograd_bwd_bnmask(dz, u_t, cin, prod["z"], prod["ab"], prod["mean"], prod["invstd"],
                                                                          self._ctr(dz.device))
                         g = ("masked", gmask, dg1, db1)
-                    elif rec.get("col3") is not None:
+                    elif rec["col3"] is not None:
                         # the conv ran on its patch rows: the GEMM's data gradient is the gradient of those rows, summed back onto the map
-                        packed_t, rows = self._cached(("g1", name), [conv.weight], lambda: ops.pack_conv1x1_weight(
-                            conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 1))
+                        packed_t, rows = self._g(name, conv, 1, col3=True)
                         g = ops.col2im3s2(ops.conv1x1(dz, packed_t, rows, None, None, None, 0), *rec["col3"])
                     else:
                         g = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
@@ -1962,10 +1832,10 @@ class ResnetSimple(nn.Module):
                 # two backward reductions ride in the epilogue of this data-gradient GEMM (one full pass over three 4x-wide tensors
                 # and one launch fewer per Bottleneck)
                 prev = tape[idx - 2] if idx >= 2 and tape[idx - 1]["kind"] == "block_end" else None
-                if (prev is not None and prev["kind"] == "conv" and prev["has_res"] and prev["relu"] and prev["y"] is not None
-                        and self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and int(dz.shape[3]) == int(conv1.weight.shape[0])
-                        and ops.conv1x1_applies(dz, cin) and tuple(prev["y"].shape) == tuple(dz.shape[:3]) + (cin,)):
-                    packed_t, rows = self._cached(("g1", name1), [conv1.weight], lambda: ops.pack_conv1x1_weight(conv1.weight.detach(), 1))
+                if (prev is not None and prev["kind"] == "conv" and prev["ab"] is not None and prev["has_res"] and prev["relu"]
+                        and prev["y"] is not None and self._gemm1x1(conv1, dz, k, stride, bwd=True)
+                        and tuple(prev["y"].shape) == tuple(dz.shape[:3]) + (cin,)):
+                    packed_t, rows = self._g(name1, conv1, 1)
                     gmask, dg3, db3 = ops.conv1x1_bwd_bnmask(dz, packed_t, cin, prev["z"], None, prev["mean"], prev["invstd"],
                                                             self._ctr(dz.device), y_act=prev["y"], residual=other)
                     g = ("masked", gmask, dg3, db3)
@@ -1974,12 +1844,15 @@ class ResnetSimple(nn.Module):
                 block = None
                 _early_bucket_hook(reducer, rec["name"], side, lambda: [grads[p] for p in self._early_bucket_params()])
             elif kind == "pool":
-                g = ops.maxpool3s2_idx_bwd(g, rec["idx"], rec["x"].shape)
+                if rec["idx"] is None:
+                    g = ops.maxpool3s2_bwd(g, rec["x"])
+                else:
+                    g = ops.maxpool3s2_idx_bwd(g, rec["idx"], rec["x"].shape)
             elif kind == "stem":
                 bn = rec["bn"]
-                dz, _, dgam, dbet = self._bn_bwd_fused(rec, g)
+                dz, _, dgam, dbet = self._bn_bwd(rec, g)
                 grads[bn.weight], grads[bn.bias] = dgam, dbet
-                kcol = int(rec["x"].shape[3])                   # 192: the stem ran on the 1x1 GEMM (run_forward_train_fused), 160: direct
+                kcol = int(rec["x"].shape[3])                   # 192: the stem ran on the 1x1 GEMM (run_forward_train), 160: direct
                 if kcol == 192:
                     dw = ops.conv1x1_wgrad(rec["x"], dz, 64, 192)
                 else:
