@@ -153,6 +153,9 @@ _SIGNATURES = {
     "dream_mse_fwd_bwd_f32": (_I, [_P, _P, _P, _P, _P, _SZ, _D, _P]),
     "dream_normalize_u8_hwc_to_chw_f32": (_I, [_P, _P, _I, _I, _I, _c.POINTER(_F), _c.POINTER(_F), _P]),
     "dream_preprocess_frames_u8_f32": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P, _I, _P, _P, _I, _I, _I, _I, _c.POINTER(_F), _c.POINTER(_F), _P]),
+    "dream_training_keypoints_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _I] + [_D] * 10 + [_P]),
+    "dream_augment_partials_per_frame": (_SZ, [_I, _I]),
+    "dream_augment_frames_u8_f32": (_I, [_P] * 9 + [_I, _I, _I, _c.POINTER(_F), _c.POINTER(_F), _P]),
     "dream_create_belief_maps_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_create_belief_maps_f64kps_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_smoothl1_fwd_bwd_f32": (_I, [_P, _P, _P, _P, _P, _SZ, _D, _P]),

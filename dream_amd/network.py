@@ -280,6 +280,35 @@ class DreamNetwork:
             assert False, "Not yet implemented."
         return loss
 
+    # ---- training from raw frames: the dataset's per-frame work (datasets.py:127-208) on the device ------------------------
+    def _training_batch_from_frames(self, frames, keypoints_raw, augmentation, image_preprocessing_override):
+        x = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+        assert isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3, \
+            'Expected "frames" to be uint8 RGB frames [B,H,W,3].'
+        preproc = image_preprocessing_override if image_preprocessing_override else self.image_preprocessing()
+        net_input_resolution = self.trained_net_input_resolution()
+        preprocessed = image_proc.resolution_after_preprocessing((int(x.shape[2]), int(x.shape[1])), net_input_resolution, preproc)
+        assert tuple(preprocessed) == tuple(net_input_resolution), \
+            "Expected resolution for image_rgb_net_input to be equal to specified network input resolution, but they are different."
+        kps = keypoints_raw if isinstance(keypoints_raw, torch.Tensor) else torch.from_numpy(np.asarray(keypoints_raw, np.float64))
+        with torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext():
+            return image_proc.training_batch_from_frames(
+                self._to_device(x), self._to_device(kps), net_input_resolution, self.trained_net_output_resolution(), preproc,
+                self.image_normalization["mean"], self.image_normalization["stdev"], augmentation)
+
+    def train_from_frames(self, frames, keypoints_raw, augmentation=None, image_preprocessing_override=None):
+        """One training step from raw data: uint8 RGB frames [B,H,W,3] of one size (device or host tensor, or numpy array) and
+        raw keypoints [B,K,2] (x, y) in raw-frame pixels.  Crop, PIL-exact resize, the optional augmentation
+        (image_proc.AugmentationTable / sample_augmentation), normalisation, the keypoint frame conversions and the belief-map
+        targets are computed on self.device (image_proc.training_batch_from_frames), then train() runs on that batch."""
+        batch = self._training_batch_from_frames(frames, keypoints_raw, augmentation, image_preprocessing_override)
+        return self.train([batch["image_rgb_input"]], batch["belief_maps"])
+
+    def loss_from_frames(self, frames, keypoints_raw, augmentation=None, image_preprocessing_override=None):
+        """loss() on the batch train_from_frames would build (validation, scripts/train_network.py:534-570)."""
+        batch = self._training_batch_from_frames(frames, keypoints_raw, augmentation, image_preprocessing_override)
+        return self.loss([batch["image_rgb_input"]], batch["belief_maps"])
+
     # ---- resolutions (network.py:366-418) ------------------------------------------------------------------
     def net_resolutions_from_image_raw_resolution(self, image_raw_resolution, image_preprocessing_override=None):
         assert len(image_raw_resolution) == 2, \

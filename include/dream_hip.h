@@ -359,6 +359,33 @@ int dream_preprocess_frames_u8_f32(const unsigned char *frames, float *out, unsi
                                    const int32_t *hbounds, const int32_t *hcoeffs, int ksize_x,
                                    const int32_t *vbounds, const int32_t *vcoeffs, int ksize_y, int tile_rows,
                                    int span_rows, int span_cols, const float *mean3, const float *stdev3, void *stream);
+/* `out` may be NULL when out_u8 is given: only the resized uint8 frames are produced (the augmentation below reads those).
+ *
+ * Training batches from raw frames (dream/datasets.py:127-208, per batch instead of per frame).
+ * aug_table: [B][16] float64 per frame: [0..5] forward 2x3 affine matrix in net-input pixels, [6..11] its inverse, [12] noise
+ * sigma, [13] contrast alpha, [14] brightness beta, [15] 32-bit noise seed (sigma / alpha / beta are fp32 values).
+ *
+ * Keypoints: kps_raw [B*K,2] float64 (x, y) in raw-frame pixels -> net input (dream/image_proc.py:165-212; mode 0 = "none",
+ * mode 1 = (k - origin) / span * target: origin 0 and span = raw resolution for "resize" / "shrink", crop corner and cropped
+ * resolution for "shrink-and-crop"; target = the resolution after preprocessing) -> k' = M k for non-identity rows of aug_table
+ * (NULL = none) -> kps_netin float64 -> net output (image_proc.py:150-162) rounded to float32 as datasets.py:190-192 does:
+ * kps_netout_f32, and the same values widened to float64 (kps_netout_f64, the input of dream_create_belief_maps_f64kps_f32).
+ * Every float64 operation is rounded on its own, in the reference's order. */
+int dream_training_keypoints_f64(const double *kps_raw, const double *aug_table, double *kps_netin, float *kps_netout_f32,
+                                 double *kps_netout_f64, int B, int K, int mode, double origin_x, double origin_y,
+                                 double span_w, double span_h, double target_w, double target_h, double in_w, double in_h,
+                                 double out_w, double out_h, void *stream);
+/* Image augmentation of resized uint8 frames [B,H,W,3] (out_u8 of dream_preprocess_frames_u8_f32) + ToTensor + Normalize, three
+ * launches: noise n = clip(rint(u + sigma * z)) with z = quantiles[mix(seed, index) >> 20] (quantiles: 4096 fp32 standard-normal
+ * quantiles) into `noised` [B,H,W,3] and per-workgroup integer sums into `partials` [B * dream_augment_partials_per_frame(H, W)];
+ * frame_mean / beta_mean [B] = fp32 mean of the noised frame and beta * mean; then per output pixel the source position
+ * M^-1 (x, y) in float64, 5 fractional bits, four reflect-101 taps of c = clip(rint(alpha * n + beta * mean)), integer bilinear
+ * blend, normalised like dream_normalize_u8_hwc_to_chw_f32 into out fp32 [B,3,H,W]; out_u8 [B,H,W,3] (may be NULL) receives the
+ * augmented uint8 frames.  mean3 / stdev3: HOST pointers. */
+size_t dream_augment_partials_per_frame(int H, int W);
+int dream_augment_frames_u8_f32(const unsigned char *frames_u8, const double *aug_table, const float *quantiles,
+                                unsigned char *noised, uint64_t *partials, float *frame_mean, float *beta_mean, float *out,
+                                unsigned char *out_u8, int B, int H, int W, const float *mean3, const float *stdev3, void *stream);
 /* ABI 1 took fp32 keypoints under this name; fp32 cannot hold the reference's float64 coordinates (57.9999999 is pixel 57,
  * its fp32 rounding pixel 58), so the entry point now FAILS with a message instead of reading fp32 data as float64. */
 int dream_create_belief_maps_f32(const float *kps, const float *blob, float *out, int N, int H, int W, int w,
