@@ -13,10 +13,12 @@ Mirrors /root/reference/dream/models.py:
 
 ``nn.Conv2d`` objects are used purely as parameter containers (OIHW, as the reference stores them);
 their ATen forward is never called.  ``forward`` executes a static list of C-ABI calls on NHWC
-activations: first conv (NCHW image -> NHWC, VALU), 3x3 convs on the fp32 matrix cores (Winograd F(2x2,3x3) where it
-applies, direct implicit GEMM elsewhere) with fused bias/ReLU/upsample/max-pool,
-skip-connection adds, and an NCHW store in the last head conv; ``backward`` walks the same list in reverse.  If the HIP library or a GPU is missing the
-call raises -- there is no CPU path in this package.
+activations: first conv (NCHW image -> NHWC, VALU), 3x3 convs on the fp32 matrix cores (Winograd F(4x4,3x3) / F(2x2,3x3) where
+they apply, direct implicit GEMM elsewhere) with fused bias/ReLU/upsample/max-pool/skip-connection add, and an NCHW store in the
+last head conv; ``backward`` walks the same list in reverse.  ``DreamHourglass`` walks its plan once per pass: at each conv it
+resolves the group of entries that run as one (``_group``), the kernel of every 3x3 conv and of its data gradient is chosen in one
+place (``_conv3x3_choice`` / ``_conv3x3``, ``_ups_tile`` / ``_ups_conv``), and the split-precision inference path is the same walk
+on other launches.  If the HIP library or a GPU is missing the call raises -- there is no CPU path in this package.
 """
 import os
 import threading
@@ -47,36 +49,40 @@ class _Params(nn.Sequential):
 
 
 class _PackedCache:
-    """Packed copies of one conv weight for the MFMA kernels, refreshed when the parameter changes
-    (optimizer step / load_state_dict bump ``_version``)."""
+    """Packed copies of conv weights for the MFMA kernels, one per (weight, form, direction, tile), refreshed when the parameter
+    changes (optimizer step / load_state_dict bump ``_version``).  direction 0 / 1: the forward / the data-gradient operator
+    (transposed, flipped taps); tile 4 / 2: the Winograd kernel the operand is for (0 where the form has no tile)."""
 
     def __init__(self):
         self._store = {}
 
-    def get(self, weight, mode, f16x3=False):
-        """mode 0 / 1: forward / transposed tap-major packing; "ups": the conv that follows a nearest x2 upsample, as the
-        equivalent 4x4 transposed conv (ops.upsample_conv_weight) in the sub-pixel phase packing."""
-        key = (id(weight), mode, f16x3)
+    def get(self, weight, form, direction=0, tile=0):
+        key = (id(weight), form, direction, tile)
         tag = (weight._version, weight.data_ptr(), weight.device)
         hit = self._store.get(key)
         if hit is None or hit[0] != tag:
             with torch.no_grad():
-                if mode in ("wino0", "wino1"):                    # Winograd F(2x2,3x3) transformed weights (fwd / data gradient)
-                    packed = ops.pack_weight_winograd(weight.detach(), int(mode[-1]))
-                elif mode in ("wino4_0", "wino4_1"):              # Winograd F(4x4,3x3)
-                    packed = ops.pack_weight_winograd4(weight.detach(), int(mode[-1]))
-                elif mode == "ups":
-                    wt4 = ops.upsample_conv_weight(weight.detach())
-                    packed = ops.pack_convT4x4_weight_f16x3(wt4) if f16x3 else ops.pack_convT4x4_weight(wt4)
-                elif mode in ("ups_wino0", "ups_wino1"):          # the same transposed conv by minimal filtering (fwd / data gradient)
-                    packed = ops.pack_convT4x4_winograd_weight(ops.upsample_conv_weight(weight.detach()), int(mode[-1]))
-                elif mode in ("ups_wino4_0", "ups_wino4_1"):      # ... on the F(4x4,3x3) kernel (25-position phase patterns)
-                    packed = ops.pack_convT4x4_winograd4_weight(ops.upsample_conv_weight(weight.detach()), int(mode[-1]))
-                else:
-                    packed = ops.pack_conv_weight_f16x3(weight.detach(), mode) if f16x3 else ops.pack_weight(weight.detach(), mode)
-                hit = (tag, packed)
+                hit = (tag, self._pack(weight.detach(), form, direction, tile))
             self._store[key] = hit
         return hit[1]
+
+    @staticmethod
+    def _pack(w, form, direction, tile):
+        if form == "direct":                      # tap-major packing of the implicit-GEMM kernel
+            return ops.pack_weight(w, direction)
+        if form == "winograd":                    # transformed weights of the F(2x2,3x3) / F(4x4,3x3) kernel
+            return ops.pack_weight_winograd_tile(w, direction, tile)
+        if form == "ups":                         # the conv that follows a nearest x2 upsample, as the equivalent 4x4 transposed conv
+            return ops.pack_convT4x4_weight(ops.upsample_conv_weight(w))               # (sub-pixel phase packing)
+        if form == "ups_winograd":                # ... and that transposed conv by minimal filtering (9- / 25-position phase patterns)
+            return ops.pack_convT4x4_winograd_weight_tile(ops.upsample_conv_weight(w), tile, direction)
+        if form == "stride2":                     # a [Cin_T,Cout_T,3,3] ConvTranspose weight as the stride-2 conv that is its data gradient
+            return ops.pack_conv_weight(w, 0)
+        if form == "f16x3":                       # split precision: two fp16 planes of the tap-major packing
+            return ops.pack_conv_weight_f16x3(w, direction)
+        if form == "ups_f16x3":
+            return ops.pack_convT4x4_weight_f16x3(ops.upsample_conv_weight(w))
+        raise ValueError("unknown packed form %r" % (form,))
 
 
 class DreamHourglass(nn.Module):
@@ -168,6 +174,8 @@ class DreamHourglass(nn.Module):
             self.softmax = container([(0, SoftArgmaxPavlo(n_keypoints, learned_beta, initial_beta))])
         self._plan = plan
         self._skip_sources = {e[3] for e in plan if e[0] == "add"}
+        owners = [li for li, e in enumerate(plan) if e[1]]
+        self._param_slot = {li: 2 * k for k, li in enumerate(owners)}   # plan index -> index of its weight in plan_parameters() (bias: + 1)
         self._packed = _PackedCache()
         # "fp32": exact fp32 MFMA kernel everywhere.  "fp16x3": inference runs the split-precision kernel
         # (fp32 in/out, 3 fp16 MFMAs per product, fp32-class error); training always uses the fp32 kernels.
@@ -180,7 +188,6 @@ class DreamHourglass(nn.Module):
         # training forward: a conv that feeds MaxPool2d(2) stores the pooled tensor from its own epilogue (csrc/conv_wino4.hip MODE 4)
         # instead of a stand-alone max-pool pass over the un-pooled one; "0": the separate pass (A/B, tests)
         self.pool_in_training_conv = os.environ.get("DREAM_POOL_IN_TRAINING_CONV", "1") != "0"
-        self._aux = {}
         # the reference builds every hourglass on vgg19(pretrained=True).features (models.py:587): ImageNet weights for all
         # encoder convs but the first when they can be had, one loud warning otherwise (dream_amd/pretrained.py)
         self.imagenet_initialised = _pretrained.init_vgg19_encoder(self)
@@ -192,17 +199,6 @@ class DreamHourglass(nn.Module):
     def plan_layers(self):
         """[(kind, module-or-None, flags)] in execution order."""
         return [(kind, self._layer(c, ch) if c else None, flags) for kind, c, ch, flags in self._plan]
-
-    def _packed_aux(self, mod):
-        """[Cin_T,Cout_T,3,3] ConvTranspose weight packed as the stride-2 conv that is its data gradient."""
-        key = ("s2", id(mod.weight))
-        tag = (mod.weight._version, mod.weight.data_ptr())
-        hit = self._aux.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                hit = (tag, ops.pack_conv_weight(mod.weight.detach(), 0))
-            self._aux[key] = hit
-        return hit[1]
 
     def plan_parameters(self):
         out = []
@@ -232,15 +228,87 @@ class DreamHourglass(nn.Module):
         if not ok:
             raise RuntimeError("expected [B,%d,H,W] input, got %s" % (self.n_image_input_channels, tuple(x.shape)))
 
-    def _fuse_pool(self, layers, li, x_nhwc):
+    # ---- which kernel runs a conv -------------------------------------------------------------------------------------
+    def _conv3x3_choice(self, mod, direction, shape, flags=0):
+        """Which kernel runs the 3x3 stride-1 conv with ``mod``'s weight on an NHWC input of ``shape`` -> ("winograd", tile 4 | 2) or
+        ("direct", 0); launches nothing.  direction 0: the forward operator; 1: the data-gradient operator (the input is dy, the channel
+        counts swap).  ``flags``: the epilogue, without a skip connection's bit."""
+        if self.conv_algorithm not in ("winograd", "direct"):
+            raise ValueError("unknown conv_algorithm %r" % (self.conv_algorithm,))
+        cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
+        if direction:
+            cin, cout = cout, cin
+        b, h, w, c = (int(v) for v in shape)
+        # Winograd serves the plain 3x3 convs (bias, ReLU, fused max-pool, ReLU mask); measured faster than the direct kernel for every
+        # DREAM layer with >= 64 output channels (profiles/r02_microbench_wino_b128.txt: 1.5-2.05x), on par at 32.  An input that carries
+        # padded channels (a "wide" first conv, the K -> 16k padded gradient of the last head conv) takes the direct kernel.
+        if (self.conv_algorithm == "direct" or c != cin or cin % 16 or cin < 32 or cout < 64
+                or flags & ~(CONV_RELU | CONV_POOL2 | ops.CONV_RELUMASK)):
+            return "direct", 0
+        return "winograd", ops.winograd_tile(h, w, cin, cout, b)
+
+    def _conv3x3(self, mod, direction, x, bias=None, skip=None, relu_mask=None, flags=0, choice=None, out=None, pool_both=False):
+        """Runs that conv: chooses the kernel (``choice``: what _conv3x3_choice answered, where the caller has asked already), fetches the
+        packed operand, launches.  ``skip``: a skip connection added after the ReLU in the epilogue; ``relu_mask``: y = mask > 0 ? conv : 0
+        (data gradients: the previous layer's ReLU).  On the F(4x4) kernel only: ``out``, a batch slice of a larger tensor to write into,
+        and ``pool_both`` -> (y, max-pooled y) from one launch."""
+        mask_bit = ops.CONV_RELUMASK if relu_mask is not None else 0
+        form, tile = choice or self._conv3x3_choice(mod, direction, x.shape, flags | mask_bit)
+        if form == "winograd":
+            packed, rows = self._packed.get(mod.weight, "winograd", direction, tile)
+        else:
+            packed, rows, _, _ = self._packed.get(mod.weight, "direct", direction)
+        if skip is not None:
+            self._join(tuple(x.shape[:3]) + (rows,), skip)
+        if out is not None or pool_both:
+            assert (form, tile) == ("winograd", 4) and skip is None and relu_mask is None
+            if pool_both:
+                return ops.conv3x3_winograd4_pool_both(x, packed, rows, bias, flags)
+            return ops.conv3x3_winograd4(x, packed, rows, None, bias, None, flags, out=out)
+        if form == "winograd":
+            residual, bit = (skip, ops.CONV_RES_AFTER_RELU) if skip is not None else (relu_mask, mask_bit)
+            return ops.conv3x3_winograd_tile(tile, x, packed, rows, None, bias, residual, flags | bit)
+        if skip is not None:
+            return ops.conv2d(x, packed, rows, 3, 1, None, bias, skip, flags | ops.CONV_RES_AFTER_RELU)
+        return ops.conv3x3(x, packed, bias, rows, flags, relu_mask=relu_mask)
+
+    def _ups_tile(self, mod, direction, x):
+        """The conv that follows nn.Upsample(2) is a 4x4 stride-2 transposed conv of its half-resolution input (4 MACs per output, not 9).
+        Does it (direction 0, ``x`` that input) or its data gradient (direction 1, ``x`` the full-resolution dy) run by minimal filtering
+        on the Winograd kernels (conv_wino.hip PAT: 9/16 of those again)?  -> their tile 4 | 2, or 0: the direct forms."""
+        cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
+        if self.conv_algorithm != "winograd" or cin % 16 or cin < 32 or cout <= 64:
+            return 0
+        if direction == 0:
+            return ops.convT4x4_winograd_tile(x, cout)
+        if cin > 64 and int(x.shape[3]) == cout and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0:
+            return ops.conv4x4s2_winograd_tile_of(x, cin)
+        return 0
+
+    def _ups_conv(self, mod, direction, x, bias=None, flags=0):
+        """Runs the upsample + conv (direction 0) or its data gradient (direction 1): chooses, fetches the packed operand, launches."""
+        tile = self._ups_tile(mod, direction, x)
+        if tile:
+            u4, rows = self._packed.get(mod.weight, "ups_winograd", direction, tile)
+            if direction == 0:
+                return ops.conv_transpose4x4s2_winograd_tile(tile, x, u4, rows, None, bias, flags & CONV_RELU, direct_taps=36)
+            # data gradient of the equivalent transposed conv, straight at half resolution (no full-resolution intermediate, no
+            # upsample2_bwd pass): four phase convs of nine positions each
+            return ops.conv4x4s2_winograd_tile(tile, x, u4, rows)
+        if direction == 0:
+            pk4, rows = self._packed.get(mod.weight, "ups")
+            return ops.conv_transpose4x4s2(x, pk4, rows, None, bias, flags & CONV_RELU, direct_taps=36)
+        return ops.upsample2_bwd(self._conv3x3(mod, 1, x))
+
+    # ---- which plan entries run as one -----------------------------------------------------------------------------------
+    def _fuse_pool(self, layers, li, x_nhwc, split):
         """Inference: fold the 2x2 max-pool that follows conv ``li`` into its epilogue?  Not when the un-pooled tensor is
         a skip source, and only at >= 160 px: the fused kernel needs even tile sides, which costs 25 % more tiles at
         50x50 (13.8 vs 11.3 + 0.15 ms, profiles/r01_pool_fusion.txt) but saves a 1.3 ms pass at 400x400."""
-        if not (li + 1 < len(layers) and layers[li + 1][0] == "pool") or li in self._skip_sources:
+        if li in self._skip_sources:
             return False
-        mod = layers[li][1]
-        if (self.conv_algorithm == "winograd" and self.precision == "fp32" and mod is not None and int(mod.weight.shape[1]) == int(x_nhwc.shape[3])
-                and ops.winograd_tile(int(x_nhwc.shape[1]), int(x_nhwc.shape[2]), int(x_nhwc.shape[3]), int(mod.weight.shape[0]), int(x_nhwc.shape[0])) == 4):
+        _, mod, flags = layers[li]
+        if not split and self._conv3x3_choice(mod, 0, x_nhwc.shape, flags | CONV_POOL2) == ("winograd", 4):
             return True         # F(4x4,3x3) works on whole 4x4 tiles anyway: the pooled store is free at every map size (saves the 100^2 / 50^2 passes)
         return min(int(x_nhwc.shape[1]), int(x_nhwc.shape[2])) >= 160
 
@@ -248,30 +316,38 @@ class DreamHourglass(nn.Module):
         """Frames per sub-batch for the first conv pair of an inference pass (0: run the layers whole).  DREAM_FIRST_SUBBATCH=n; only
         where the second conv runs on the F(4x4,3x3) kernel with the pool fused, is no skip source, and the batch has several sub-batches."""
         n = int(os.environ.get("DREAM_FIRST_SUBBATCH", "0"))
-        if n <= 0 or save or self.precision != "fp32" or self.conv_algorithm != "winograd" or li + 2 >= len(layers):
+        if n <= 0 or save or self.precision != "fp32" or li + 2 >= len(layers):
             return 0
         (k1, m1, f1), (k2, _, _) = layers[li + 1], layers[li + 2]
         b, _, h, w = (int(v) for v in x_nchw.shape)
+        cin = int(m1.weight.shape[1])
         if (k1 != "conv" or k2 != "pool" or f1 != CONV_RELU or any(i in self._skip_sources for i in (li, li + 1, li + 2)) or b <= n
-                or h % 2 or w % 2 or int(m1.weight.shape[1]) != int(layers[li][1].weight.shape[0])):
+                or h % 2 or w % 2 or cin != int(layers[li][1].weight.shape[0])):
             return 0
-        cin, cout = int(m1.weight.shape[1]), int(m1.weight.shape[0])
-        if not self._use_winograd(cin, cout, f1) or ops.winograd_tile(h, w, cin, cout, min(n, b)) != 4:
-            return 0
-        return n
+        return n if self._conv3x3_choice(m1, 0, (n, h, w, cin), f1 | CONV_POOL2) == ("winograd", 4) else 0
 
-    def _use_winograd(self, cin, cout, flags):
-        """Winograd serves the plain 3x3 convs (bias, ReLU, fused max-pool); measured faster than the direct kernel for every
-        DREAM layer with >= 64 output channels (profiles/r02_microbench_wino_b128.txt: 1.5-2.05x), on par at 32."""
-        if self.conv_algorithm != "winograd":
-            if self.conv_algorithm != "direct":
-                raise ValueError("unknown conv_algorithm %r" % (self.conv_algorithm,))
-            return False
-        return cin % 16 == 0 and cin >= 32 and cout >= 64 and not (flags & ~(CONV_RELU | CONV_POOL2 | ops.CONV_RELUMASK))
-
-    def _ups_winograd(self, cin, cout):
-        """The convs that follow nn.Upsample(2), as 4x4 stride-2 transposed convs on the Winograd kernel (conv_wino.hip, PAT)."""
-        return self.conv_algorithm == "winograd" and cin % 16 == 0 and cin >= 32 and cout > 64
+    def _group(self, layers, li, x, save, split):
+        """The plan entries that the conv at ``li`` runs as one -> (name, frames per sub-batch of "pair+pool"):
+          "conv"            the conv alone;
+          "conv+pool"       inference: the 2x2 max-pool that follows, folded into the epilogue (CONV_POOL2);
+          "conv+pool_both"  training: one F(4x4) launch (conv_wino4.hip MODE 4) stores the pooled tensor beside the un-pooled one, which backward needs;
+          "conv+add"        fp32 inference: the skip connection that follows (models.py:774-799: x = x + x_0_k_d) added in the epilogue, after
+                            the ReLU: the sum never round-trips through HBM.  (Training: backward reads the conv's own output as its ReLU mask.)
+          "pair+pool"       fp32 inference: conv1_1 -> conv1_2 + pool over sub-batches (_first_pair_subbatch)."""
+        kind, mod, flags = layers[li]
+        follower = layers[li + 1][0] if li + 1 < len(layers) else None
+        if kind == "first":
+            sub = self._first_pair_subbatch(layers, li, x, save)
+            return ("pair+pool", sub) if sub else ("conv", 0)
+        if kind == "conv" and follower == "pool":
+            if not save:
+                return ("conv+pool" if self._fuse_pool(layers, li, x, split) else "conv"), 0
+            if self.pool_in_training_conv and flags == CONV_RELU and self._conv3x3_choice(mod, 0, x.shape, flags) == ("winograd", 4):
+                return "conv+pool_both", 0
+        if (not save and not split and kind in ("conv", "deconv") and follower == "add"
+                and not (flags & (CONV_UPSAMPLE2X | CONV_OUT_NCHW)) and li not in self._skip_sources):
+            return "conv+add", 0
+        return "conv", 0
 
     @staticmethod
     def _join(a, b):
@@ -280,152 +356,94 @@ class DreamHourglass(nn.Module):
             raise RuntimeError("The size of tensor a %s must match the size of tensor b %s" % (sa, tuple(b.shape)))
 
     # ---- execution -------------------------------------------------------------------------------------
-    def run_forward_f16x3(self, x, params, x_is_nhwc=False, x_amax=None):
-        """Inference plan on the split-precision conv kernel.  Each kernel publishes max|y| of its output (amax side
-        channel) so the next conv can scale its input into fp16 range; pooling cannot raise the maximum."""
-        act, amax = x, x_amax
-        pi = 0
-        layers = self.plan_layers()
-        keep = {}
-        pool_done = False
-        for li, (kind, mod, flags) in enumerate(layers):
-            if kind == "pool":
-                if not pool_done:
-                    act = ops.maxpool2(act)
-                pool_done = False
-            elif kind == "add":
-                self._join(act, keep[flags])
-                act, amax = ops.add(act, keep[flags], want_amax=True)
-            else:
-                w, bias = params[pi], params[pi + 1]
-                pi += 2
-                if kind == "first":
-                    act, amax = ops.conv3x3_first_amax(act, w, bias, relu=bool(flags & CONV_RELU))
-                else:
-                    if kind == "wide" and not x_is_nhwc:
-                        amax = ops.absmax(act)
-                        act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
-                    if self._fuse_pool(layers, li, act):
-                        flags, pool_done = flags | CONV_POOL2, True
-                    if flags & CONV_UPSAMPLE2X:              # upsample + conv == a 4x4 transposed conv (see run_forward)
-                        pk4 = self._packed.get(mod.weight, "ups", f16x3=True)
-                        act, amax = ops.conv_transpose4x4s2_f16x3(act, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
-                    elif kind == "deconv":
-                        p16 = self._packed.get(mod.weight, 1, f16x3=True)
-                        act, amax = ops.conv_transpose3x3s2_f16x3(act, amax, p16, p16[3], bias, relu=bool(flags & CONV_RELU))
-                    else:
-                        p16 = self._packed.get(mod.weight, 0, f16x3=True)
-                        act, amax = ops.conv2d_f16x3(act, amax, p16, p16[3], 3, None, bias, None, flags,
-                                                     want_amax=not (flags & CONV_OUT_NCHW))
-            if li in self._skip_sources:
-                keep[li] = act
-        return act
+    def _conv_fp32(self, kind, mod, x, amax, w, bias, flags, skip=None):
+        """One conv entry of the plan on the fp32 kernels -> (y, None)."""
+        if kind == "first":
+            return ops.conv3x3_first(x, w, bias, relu=bool(flags & CONV_RELU)), None
+        if flags & CONV_UPSAMPLE2X:
+            return self._ups_conv(mod, 0, x, bias, flags), None
+        if kind == "deconv":                         # ConvTranspose weight [Cin,Cout,3,3], mode-1 packing; sub-pixel phases: a
+            packed, rows, _, _ = self._packed.get(mod.weight, "direct", 1)       # quarter of the zero-stuffed MACs
+            if skip is not None:
+                self._join((x.shape[0], 2 * x.shape[1], 2 * x.shape[2], rows), skip)
+            return ops.conv_transpose3x3s2(x, packed, bias, rows, relu=bool(flags & CONV_RELU), skip=skip), None
+        return self._conv3x3(mod, 0, x, bias, skip=skip, flags=flags), None
+
+    def _conv_f16x3(self, kind, mod, x, amax, w, bias, flags, skip=None):
+        """One conv entry of the plan on the split-precision kernels -> (y, amax of y).  Each kernel publishes max|y| of its output (amax
+        side channel) so the next conv can scale its input into fp16 range; skip connections are not folded here."""
+        if kind == "first":
+            return ops.conv3x3_first_amax(x, w, bias, relu=bool(flags & CONV_RELU))
+        if flags & CONV_UPSAMPLE2X:
+            pk4 = self._packed.get(mod.weight, "ups_f16x3")
+            return ops.conv_transpose4x4s2_f16x3(x, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
+        if kind == "deconv":
+            p16 = self._packed.get(mod.weight, "f16x3", 1)
+            return ops.conv_transpose3x3s2_f16x3(x, amax, p16, p16[3], bias, relu=bool(flags & CONV_RELU))
+        p16 = self._packed.get(mod.weight, "f16x3", 0)
+        return ops.conv2d_f16x3(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
+
+    def _first_pair_in_subbatches(self, layers, li, x, params, sub):
+        """conv1_1 -> conv1_2 (+ pool) over sub-batches of ``sub`` frames, so that the 64-channel full-resolution tensor between them
+        (41 MB per frame at 400 x 400: 5.2 GB at 128 frames, written and re-read through HBM) is a ``sub``-frame buffer that is
+        re-used in place and stays in the 256-MB Infinity Cache (dream/models.py:591-599)."""
+        (_, _, f1), (_, mod2, f2) = layers[li], layers[li + 1]
+        k = self._param_slot[li]
+        b, h, w = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        out = torch.empty((b, h // 2, w // 2, int(mod2.weight.shape[0])), dtype=torch.float32, device=x.device)
+        for s0 in range(0, b, sub):
+            a1 = ops.conv3x3_first(x[s0:s0 + sub], params[k], params[k + 1], relu=bool(f1 & CONV_RELU))
+            # F(4x4) as _first_pair_subbatch found for ``sub`` frames, for a shorter last sub-batch as well
+            self._conv3x3(mod2, 0, a1, params[k + 3], flags=f2 | CONV_POOL2, choice=("winograd", 4), out=out[s0:s0 + sub])
+            del a1
+        return out
 
     def run_forward(self, x, params, save, x_is_nhwc=False, x_amax=None):
-        """Executes the plan.  ``params`` is plan_parameters() (possibly autograd-detached).  With
-        ``save`` the per-layer inputs/outputs needed by run_backward are returned as well.  ``x_is_nhwc``: the
-        caller (multi-stage) already built the zero-padded NHWC input of a "wide" first conv."""
+        """Executes the plan.  ``params`` is plan_parameters() (possibly autograd-detached).  With ``save`` the (input, output) pair of
+        every plan entry, which run_backward needs, is returned as well.  ``x_is_nhwc``: the caller (multi-stage) already built the
+        zero-padded NHWC input of a "wide" first conv (``x_amax``: its max|x|, for the split-precision kernels).
+
+        One walk: at each conv the group of entries it heads is resolved (_group) and run, then the walk moves past them.  Inference
+        with precision "fp16x3" is the same walk on the split-precision launches (_conv_f16x3), with the amax side channel threaded
+        through; it folds no skip-adds and runs no sub-batches."""
         self._check_input(x, x_is_nhwc)
-        if self.precision == "fp16x3" and not save:
-            return self.run_forward_f16x3(x, params, x_is_nhwc, x_amax), []
         if self.precision not in ("fp32", "fp16x3"):
             raise ValueError("unknown precision %r" % (self.precision,))
-        saved = []
-        keep = {}
-        act = x
-        pi = 0
+        split = self.precision == "fp16x3" and not save
+        conv = self._conv_f16x3 if split else self._conv_fp32
         layers = self.plan_layers()
-        pool_done = add_done = False
-        pooled_by_conv = None
-        consumed = 0
-        for li, (kind, mod, flags) in enumerate(layers):
-            if consumed > 0:                               # this layer ran inside the sub-batched first pair below
-                consumed -= 1
-                if kind not in ("pool", "add"):
-                    pi += 2
-                continue
-            inp = act
-            skip = None
+        saved, keep = [], {}
+        act, amax, li = x, x_amax, 0
+        while li < len(layers):
+            kind, mod, flags = layers[li]
             if kind == "pool":
-                if pooled_by_conv is not None:             # training: the conv's own launch stored the pooled tensor beside the un-pooled one
-                    act, pooled_by_conv = pooled_by_conv, None
-                elif not pool_done:
-                    act = ops.maxpool2(inp)
-                pool_done = False
+                outs = [ops.maxpool2(act)]                   # (pooling cannot raise the maximum: amax stays)
             elif kind == "add":
-                if not add_done:
-                    self._join(inp, keep[flags])
-                    act, _ = ops.add(inp, keep[flags])
-                add_done = False
+                self._join(act, keep[flags])
+                out, amax = ops.add(act, keep[flags], want_amax=split)
+                outs = [out]
             else:
-                if not save and kind not in ("first", "wide") and self._fuse_pool(layers, li, inp):
-                    flags, pool_done = flags | CONV_POOL2, True
-                # inference: the skip connection that follows this conv (models.py:774-799: x = x + x_0_k_d) is added in its own
-                # epilogue, after the ReLU -- no separate elementwise launch, the sum never round-trips through HBM.  (Training
-                # keeps the separate add: the backward pass reads the conv's own output as its ReLU mask.)
-                if (not save and kind in ("conv", "deconv") and li + 1 < len(layers) and layers[li + 1][0] == "add"
-                        and not (flags & (CONV_POOL2 | CONV_UPSAMPLE2X | CONV_OUT_NCHW)) and li not in self._skip_sources):
-                    skip = keep[layers[li + 1][2]]
-                w, bias = params[pi], params[pi + 1]
-                pi += 2
-                sub = self._first_pair_subbatch(layers, li, inp, save) if kind == "first" else 0
-                if sub:
-                    # inference: conv1_1 -> conv1_2 (+ pool) over sub-batches of `sub` frames, so that the 64-channel full-resolution tensor
-                    # between them (41 MB per frame at 400 x 400: 5.2 GB at 128 frames, written and re-read through HBM) is a
-                    # `sub`-frame buffer that is re-used in place and stays in the 256-MB Infinity Cache (dream/models.py:591-599)
-                    mod2 = layers[li + 1][1]
-                    u2, rows2 = self._packed.get(mod2.weight, "wino4_0")
-                    b_all, h_in, w_in = int(inp.shape[0]), int(inp.shape[2]), int(inp.shape[3])
-                    act = torch.empty((b_all, h_in // 2, w_in // 2, rows2), dtype=torch.float32, device=inp.device)
-                    for s0 in range(0, b_all, sub):
-                        a1 = ops.conv3x3_first(inp[s0:s0 + sub], w, bias, relu=bool(flags & CONV_RELU))
-                        ops.conv3x3_winograd4(a1, u2, rows2, None, params[pi + 1], None, layers[li + 1][2] | CONV_POOL2, out=act[s0:s0 + sub])
-                        del a1
-                    consumed = 2                             # conv1_2 and its pool
-                elif kind == "first":
-                    act = ops.conv3x3_first(inp, w, bias, relu=bool(flags & CONV_RELU))
+                if kind == "wide" and not x_is_nhwc:
+                    if split:
+                        amax = ops.absmax(act)
+                    act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
+                w, bias = params[self._param_slot[li]], params[self._param_slot[li] + 1]
+                group, sub = self._group(layers, li, act, save, split)
+                if group == "pair+pool":
+                    outs = [None, None, self._first_pair_in_subbatches(layers, li, act, params, sub)]
+                elif group == "conv+pool_both":
+                    outs = list(self._conv3x3(mod, 0, act, bias, flags=flags, pool_both=True))
                 else:
-                    if kind == "wide" and not x_is_nhwc:
-                        inp = ops.nchw_to_nhwc(inp, cpad=self.input_channel_pad())
-                    if flags & CONV_UPSAMPLE2X:              # upsample + conv == a 4x4 transposed conv: 4 MACs / output, not 9
-                        if self._ups_winograd(int(inp.shape[3]), int(mod.weight.shape[0])):
-                            # ... and that transposed conv by minimal filtering on the Winograd kernel: 9/16 of those again
-                            tile = ops.convT4x4_winograd_tile(inp, int(mod.weight.shape[0]))
-                            u4, cout4 = self._packed.get(mod.weight, "ups_wino4_0" if tile == 4 else "ups_wino0")
-                            act = ops.conv_transpose4x4s2_winograd_tile(tile, inp, u4, cout4, None, bias, flags & CONV_RELU, direct_taps=36)
-                        else:
-                            pk4, cout4 = self._packed.get(mod.weight, "ups")
-                            act = ops.conv_transpose4x4s2(inp, pk4, cout4, None, bias, flags & CONV_RELU, direct_taps=36)
-                    elif kind == "deconv":                   # ConvTranspose weight [Cin,Cout,3,3], mode-1 packing; sub-pixel
-                        packed, rows, _, _ = self._packed.get(mod.weight, 1)   # phases: a quarter of the zero-stuffed MACs
-                        if skip is not None:
-                            self._join((inp.shape[0], 2 * inp.shape[1], 2 * inp.shape[2], rows), skip)
-                        act = ops.conv_transpose3x3s2(inp, packed, bias, rows, relu=bool(flags & CONV_RELU), skip=skip)
-                        add_done = skip is not None
-                    elif int(mod.weight.shape[1]) == int(inp.shape[3]) and self._use_winograd(int(inp.shape[3]), int(mod.weight.shape[0]), flags):
-                        tile = ops.winograd_tile(int(inp.shape[1]), int(inp.shape[2]), int(inp.shape[3]), int(mod.weight.shape[0]), int(inp.shape[0]))
-                        u, rows = self._packed.get(mod.weight, "wino4_0" if tile == 4 else "wino0")
-                        if skip is not None:
-                            self._join(tuple(inp.shape[:3]) + (rows,), skip)
-                        if (save and tile == 4 and skip is None and self.pool_in_training_conv and flags == CONV_RELU
-                                and li + 1 < len(layers) and layers[li + 1][0] == "pool"):
-                            # training: un-pooled tensor (kept for the backward pass) AND pooled tensor from one launch
-                            act, pooled_by_conv = ops.conv3x3_winograd4_pool_both(inp, u, rows, bias, flags)
-                        else:
-                            act = ops.conv3x3_winograd_tile(tile, inp, u, rows, None, bias, skip, flags | (ops.CONV_RES_AFTER_RELU if skip is not None else 0))
-                        add_done = skip is not None
-                    elif skip is not None:
-                        packed, rows, _, _ = self._packed.get(mod.weight, 0)
-                        self._join(tuple(inp.shape[:3]) + (rows,), skip)
-                        act = ops.conv2d(inp, packed, rows, 3, 1, None, bias, skip, flags | ops.CONV_RES_AFTER_RELU)
-                        add_done = True
-                    else:
-                        packed, rows, _, _ = self._packed.get(mod.weight, 0)
-                        act = ops.conv3x3(inp, packed, bias, rows, flags)
-            if save:
-                saved.append((inp, act))
-            if li in self._skip_sources:
-                keep[li] = act
+                    skip = keep[layers[li + 1][2]] if group == "conv+add" else None
+                    out, amax = conv(kind, mod, act, amax, w, bias, flags | (CONV_POOL2 if group == "conv+pool" else 0), skip)
+                    outs = [out] if group == "conv" else [None, out]
+            # one output per plan entry the group covered (None: folded away, never stored -- and then neither saved nor a skip source)
+            for out in outs:
+                if save:
+                    saved.append((act, out))
+                if li in self._skip_sources:
+                    keep[li] = out
+                act, li = out, li + 1
         return act, saved
 
     def run_backward(self, saved, grad_out_nchw, need_input_grad=False, reducer=None):
@@ -433,14 +451,12 @@ class DreamHourglass(nn.Module):
         multi-stage hourglass, dL/d(NHWC input of the "wide" first conv)).  ``reducer``: overlapped data-parallel
         all-reduce that is fed every gradient as soon as it exists."""
         layers = self.plan_layers()
-        grads = _GradList(2 * sum(1 for k, m, _ in layers if m is not None), reducer)
+        grads = _GradList(2 * len(self._param_slot), reducer)
         # weight gradients are leaves of the data-gradient chain: second stream when the batch is small (see _SideStream)
         sh = saved[0][0].shape                             # NCHW image ("first") or NHWC packed input ("wide")
         input_px = int(sh[0]) * (int(sh[2]) * int(sh[3]) if layers[0][0] == "first" else int(sh[1]) * int(sh[2]))
         side = _SideStream.create(grad_out_nchw, self.overlap_wgrad and input_px <= self.OVERLAP_MAX_PIXELS)
-        pi = len(grads)
-        g = None
-        g_input = None
+        g = g_input = None
         pending = {}                                       # skip source plan index -> gradient that branched off
         masked = False                                     # g already carries the ReLU gradient of layer li
 
@@ -468,7 +484,7 @@ class DreamHourglass(nn.Module):
                 pending[flags] = ops.clone(g)              # later in-place ReLU masks must not touch this copy
                 masked = False
                 continue
-            pi -= 2
+            pi = self._param_slot[li]
             fuse = relu_feeds(li - 1)                      # this layer's data gradient can carry layer li-1's ReLU mask
             if kind == "deconv":
                 # ConvTranspose2d(3,2,1,op 1) + ReLU (models.py:621-686): bias grad = column sums, weight grad over the
@@ -479,7 +495,7 @@ class DreamHourglass(nn.Module):
                     grads[pi] = ops.convT_wgrad(inp, g, 3)
                     grads[pi + 1] = ops.channel_sum(g)
                 _on_side(side, leaf, inp, g)
-                packed_s2, rows_s2, _ = self._packed_aux(mod)
+                packed_s2, rows_s2, _ = self._packed.get(mod.weight, "stride2")
                 g = ops.conv2d(g, packed_s2, rows_s2, 3, 2, None, None, inp if fuse else None,
                                ops.CONV_RELUMASK if fuse else 0)
                 masked = fuse
@@ -498,8 +514,7 @@ class DreamHourglass(nn.Module):
                 dw, db = ops.conv3x3_wgrad(inp, g, cout, int(inp.shape[3]), 0)
                 grads[pi], grads[pi + 1] = dw[:, :cin].contiguous(), db
                 if need_input_grad:
-                    packed_t, rows, _, _ = self._packed.get(mod.weight, 1)
-                    g_input = ops.conv3x3(g, packed_t, None, rows, 0)         # [B,H,W,cin]
+                    g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
                 continue
             def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ups=flags & CONV_UPSAMPLE2X):
@@ -511,30 +526,13 @@ class DreamHourglass(nn.Module):
                 else:
                     grads[pi], grads[pi + 1] = ops.conv3x3_wgrad(inp, g, cout, cin, ups)
             _on_side(side, leaf, inp, g)
-            packed_t, rows, _, cols_pad = self._packed.get(mod.weight, 1)
+            cols_pad = self._packed.get(mod.weight, "direct", 1)[3]
             if int(g.shape[3]) != cols_pad:
                 raise RuntimeError("internal: gradient has %d channels, packed weights expect %d" % (g.shape[3], cols_pad))
             if flags & CONV_UPSAMPLE2X:                    # the mask lives at half resolution: after upsample2_bwd
-                if (self._ups_winograd(cin, cout) and cin > 64 and int(g.shape[3]) == cout
-                        and g.shape[1] % 2 == 0 and g.shape[2] % 2 == 0):
-                    # data gradient of the equivalent transposed conv, straight at half resolution (no full-resolution
-                    # intermediate, no upsample2_bwd pass): four phase convs of nine positions each
-                    tile = ops.conv4x4s2_winograd_tile_of(g, cin)
-                    u4b, rows_b = self._packed.get(mod.weight, "ups_wino4_1" if tile == 4 else "ups_wino1")
-                    g = ops.conv4x4s2_winograd_tile(tile, g, u4b, rows_b)
-                elif self._use_winograd(int(g.shape[3]), cin, 0) and int(g.shape[3]) == cout:
-                    tile = ops.winograd_tile(int(g.shape[1]), int(g.shape[2]), cout, cin, int(g.shape[0]))
-                    u_t, rows_t = self._packed.get(mod.weight, "wino4_1" if tile == 4 else "wino1")
-                    g = ops.upsample2_bwd(ops.conv3x3_winograd_tile(tile, g, u_t, rows_t, None, None, None, 0))
-                else:
-                    g = ops.upsample2_bwd(ops.conv3x3(g, packed_t, None, rows, 0))
-            elif self._use_winograd(int(g.shape[3]), cin, ops.CONV_RELUMASK if fuse else 0) and int(g.shape[3]) == cout:
-                tile = ops.winograd_tile(int(g.shape[1]), int(g.shape[2]), cout, cin, int(g.shape[0]))
-                u_t, rows_t = self._packed.get(mod.weight, "wino4_1" if tile == 4 else "wino1")   # data gradient = conv with the transposed, flipped taps
-                g = ops.conv3x3_winograd_tile(tile, g, u_t, rows_t, None, None, inp if fuse else None, ops.CONV_RELUMASK if fuse else 0)
-                masked = fuse
-            else:
-                g = ops.conv3x3(g, packed_t, None, rows, 0, relu_mask=inp if fuse else None)
+                g = self._ups_conv(mod, 1, g)
+            else:                                          # data gradient = conv with the transposed, flipped taps
+                g = self._conv3x3(mod, 1, g, relu_mask=inp if fuse else None)
                 masked = fuse
         if side is not None:
             side.join()

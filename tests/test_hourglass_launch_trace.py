@@ -1,0 +1,239 @@
+"""DreamHourglass issues a static list of C-ABI calls: this pins that list, launch by launch, without a GPU.
+
+``ops.call`` / ``ops.ptr`` / ``ops.stream`` are replaced by recorders and the network is driven with tensors on the ``meta`` device, so
+every host-side decision (which kernel, which tile, which fusion, which flags, which sizes) runs for real and no kernel does.  Host-side
+size queries go to the built library, which needs no GPU.  Per launch the entry-point name and every scalar argument are recorded
+(pointers dropped), per training pass also the shapes of the saved (input, output) pair of every plan entry.
+
+tests/golden/hourglass_launch_trace.json holds the full traces (one table of distinct launches, one index list per case).  The lazy
+weight-packing launches are compared as a multiset, everything else as an exact ordered sequence.
+
+    python tests/test_hourglass_launch_trace.py --record
+
+rewrites the fixture from the tree it runs in; a change that is meant to keep the launch list is checked against a fixture written
+by the commit before it.
+"""
+import collections
+import json
+import os
+import sys
+import warnings
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from dream_amd import data_parallel, models, ops  # noqa: E402
+
+FIXTURE = os.path.join(ROOT, "tests", "golden", "hourglass_launch_trace.json")
+KEYPOINTS = 7
+VARIANTS = {
+    "vgg_q": {},
+    "vgg_q_skip": dict(skip_connections=True),
+    "vgg_f": dict(deconv_decoder=True),
+    "vgg_f_skip": dict(deconv_decoder=True, skip_connections=True),
+    "vgg_q_full": dict(full_output=True),
+    "wide": dict(n_image_input_channels=10),             # the first conv of a later stage: image + previous maps
+}
+PACK_LAUNCHES = ("dream_upsample_conv3x3_weight_as_convT4x4", "dream_convT4x4_phase_weights")
+
+
+def _is_pack(launch):
+    name = launch.split(" ", 1)[0]
+    return name.startswith("dream_pack_") or name in PACK_LAUNCHES
+
+
+def _base_cases():
+    """(variant, (B, H, W), pass, options) before the conv_algorithm x tile product."""
+    out = [("vgg_q", (128, 400, 400), p, {}) for p in ("inference", "training")]
+    out.append(("vgg_q", (128, 400, 400), "training", dict(pool_in_training_conv=False)))
+    out += [("vgg_q", (8, 400, 400), p, dict(first_subbatch=2)) for p in ("inference", "training")]
+    out += [(v, (16, 400, 400), p, {}) for v in ("vgg_q_skip", "vgg_f", "vgg_f_skip", "vgg_q_full") for p in ("inference", "training")]
+    out += [(v, (2, 70, 93), p, {}) for v in ("vgg_q", "vgg_f") for p in ("inference", "training")]
+    out += [("vgg_q", (1, 320, 320), p, {}) for p in ("inference", "training")]
+    out += [(v, (2, 70, 93), p, dict(raises=True)) for v in ("vgg_q_skip", "vgg_f_skip") for p in ("inference", "training")]
+    out += [("wide", (4, 64, 96), "training", dict(need_input_grad=True)),
+            ("wide", (4, 64, 96), "inference", {}), ("wide", (4, 64, 96), "inference", dict(x_is_nhwc=True))]
+    for shape in ((4, 64, 96), (16, 400, 400)):
+        out += [(v, shape, "inference", dict(precision="fp16x3")) for v in ("vgg_q", "vgg_q_skip", "vgg_f_skip", "wide")]
+        out.append(("wide", shape, "inference", dict(precision="fp16x3", x_is_nhwc=True)))
+    return out
+
+
+def _cases():
+    out = {}
+    for n, (variant, shape, which, opts) in enumerate(_base_cases()):
+        for algo in ("winograd", "direct"):
+            for tile in ((0, 4, 2) if n == 0 else (0, 4)):
+                name = "-".join([variant, "%dx%dx%d" % shape, which] + ["%s=%s" % kv for kv in sorted(opts.items())] + [algo, "tile%d" % tile])
+                out[name] = dict(variant=variant, shape=shape, training=which == "training", algo=algo, tile=tile, **opts)
+    return out
+
+
+CASES = _cases()
+_nets = {}
+
+
+def _net(variant):
+    """One network per variant on the meta device (the cases reset its switches and its packed-weight caches)."""
+    if variant not in _nets:
+        with pytest.MonkeyPatch.context() as mp, warnings.catch_warnings():
+            mp.setenv("DREAM_VGG19_WEIGHTS", os.path.join(ROOT, "tests", "golden", "no-such-weights.pth"))   # default initialisation, no lookup
+            warnings.simplefilter("ignore")
+            net = models.DreamHourglass(KEYPOINTS, internalize_spatial_softmax=False, **VARIANTS[variant])
+        _nets[variant] = net.to("meta")
+    return _nets[variant]
+
+
+class _Recorder:
+    def __init__(self):
+        self.launches = []
+
+    def call(self, name, *args):
+        self.launches.append(" ".join([name] + [repr(a) for a in args if type(a) in (int, float, bool)]))
+
+    @staticmethod
+    def ptr(t):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError("non-contiguous tensor passed to the HIP library")
+        return None if t is None else _Recorder                 # neither int nor float: dropped from the record
+
+    @staticmethod
+    def stream():
+        return None
+
+
+def _shape(t):
+    return "x".join(str(int(v)) for v in t.shape)
+
+
+def run_case(case, mp):
+    """-> {"seq": launches in order, "packs": sorted weight-pack launches, "saved": shapes per plan entry, "error": text or None}."""
+    net = _net(case["variant"])
+    net.precision = case.get("precision", "fp32")
+    net.conv_algorithm = case["algo"]
+    net.pool_in_training_conv = case.get("pool_in_training_conv", True)
+    data_parallel.reset_weight_caches(net)
+    rec = _Recorder()
+    for name in ("call", "ptr", "stream"):
+        mp.setattr(ops, name, getattr(rec, name))
+    mp.setenv("DREAM_FIRST_SUBBATCH", str(case.get("first_subbatch", 0)))
+    b, h, w = case["shape"]
+    nhwc = case.get("x_is_nhwc", False)
+    x = torch.empty((b, h, w, net.input_channel_pad()) if nhwc else (b, net.n_image_input_channels, h, w), device="meta")
+    amax = torch.empty((1,), dtype=torch.int32, device="meta") if nhwc and net.precision == "fp16x3" else None
+    params = [p.detach() for p in net.plan_parameters()]
+    saved, error = [], None
+    forced = ops._WINOGRAD_TILE_FORCED
+    ops.set_winograd_tile(case["tile"])
+    try:
+        out, saved = net.run_forward(x, params, case["training"], x_is_nhwc=nhwc, x_amax=amax)
+        assert tuple(out.shape) == (b, KEYPOINTS) + tuple(net.output_resolution((w, h)))[::-1]
+        if case["training"]:
+            assert len(saved) == len(net.plan_layers())
+            need = case.get("need_input_grad", False)
+            grads = net.run_backward(saved, torch.empty(out.shape, device="meta"), need_input_grad=need)
+            if need:
+                grads, g_input = grads
+                assert tuple(g_input.shape[:3]) == (b, h, w)
+            assert [tuple(g.shape) for g in grads] == [tuple(p.shape) for p in params]
+    except RuntimeError as e:
+        if not case.get("raises"):
+            raise
+        error = str(e)
+    finally:
+        ops.set_winograd_tile(forced)
+    assert (error is not None) == bool(case.get("raises"))
+    return dict(seq=[l for l in rec.launches if not _is_pack(l)], packs=sorted(l for l in rec.launches if _is_pack(l)),
+                saved=["saved %s %s" % (_shape(i), _shape(o)) for i, o in saved], error=error)
+
+
+def _count(trace, name):
+    return sum(1 for l in trace["seq"] if l.split(" ", 1)[0] == name)
+
+
+def check_properties(name, case, trace):
+    """What the paths must show whatever the fixture says."""
+    unforced_wino = case["algo"] == "winograd" and case["tile"] == 0
+    if case["variant"] == "vgg_q" and case["shape"] == (128, 400, 400) and unforced_wino:
+        assert _count(trace, "dream_conv3x3_winograd_nhwc_f32") == 0, name              # every Winograd conv picks F(4x4) on its own
+        if case["training"] and case.get("pool_in_training_conv", True):
+            assert _count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 4 and _count(trace, "dream_maxpool2_nhwc_f32") == 0, name
+        elif case["training"]:
+            assert _count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 0 and _count(trace, "dream_maxpool2_nhwc_f32") == 4, name
+    if "first_subbatch" in case:
+        sub = case["algo"] == "winograd" and case["tile"] != 2 and not case["training"]
+        assert _count(trace, "dream_conv3x3_first_nchw_f32") == (4 if sub else 1), name
+    if case["variant"].endswith("_skip") and not case.get("raises"):
+        adds = _count(trace, "dream_add_f32")
+        folded = not case["training"] and case.get("precision", "fp32") == "fp32"
+        assert (adds == 0) if folded else (adds >= 2), name
+    if case.get("raises"):
+        assert trace["error"].startswith("The size of tensor a (") and "must match the size of tensor b (" in trace["error"], name
+
+
+# ---- fixture: one table of distinct launches, per case the indices into it ---------------------------------------------------------
+def _encode(traces):
+    table = {}
+
+    def idx(items):
+        return [table.setdefault(s, len(table)) for s in items]
+
+    cases = {name: dict(seq=idx(t["seq"]), packs=idx(t["packs"]), saved=idx(t["saved"]), error=t["error"]) for name, t in traces.items()}
+    return dict(launches=list(table), cases=cases)
+
+
+def _decode(fixture, name):
+    t = fixture["cases"][name]
+    return dict(seq=[fixture["launches"][i] for i in t["seq"]], packs=[fixture["launches"][i] for i in t["packs"]],
+                saved=[fixture["launches"][i] for i in t["saved"]], error=t["error"])
+
+
+def _write(fixture, path):
+    with open(path, "w") as f:
+        f.write('{"launches": [\n' + ",\n".join(json.dumps(s) for s in fixture["launches"]) + '\n],\n"cases": {\n')
+        f.write(",\n".join("%s: %s" % (json.dumps(n), json.dumps(c, separators=(",", ":"))) for n, c in fixture["cases"].items()))
+        f.write("\n}}\n")
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
+def test_fixture_covers_exactly_the_cases(fixture):
+    assert sorted(fixture["cases"]) == sorted(CASES)
+
+
+def _first_difference(want, got):
+    n = next((i for i, (a, b) in enumerate(zip(want, got)) if a != b), min(len(want), len(got)))
+    return "launch %d of %d (recorded) / %d (now):\n  recorded: %s\n  now:      %s\n  after:    %s" % (
+        n, len(want), len(got), want[n] if n < len(want) else "<end>", got[n] if n < len(got) else "<end>", want[max(0, n - 3):n])
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_launch_trace(name, fixture, monkeypatch):
+    case = CASES[name]
+    got = run_case(case, monkeypatch)
+    check_properties(name, case, got)
+    want = _decode(fixture, name)
+    assert got["error"] == want["error"]
+    assert got["seq"] == want["seq"], _first_difference(want["seq"], got["seq"])
+    assert collections.Counter(got["packs"]) == collections.Counter(want["packs"])
+    assert got["saved"] == want["saved"], _first_difference(want["saved"], got["saved"])
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: python tests/test_hourglass_launch_trace.py --record")
+    traces = {}
+    for case_name, case_ in CASES.items():
+        with pytest.MonkeyPatch.context() as patch:
+            traces[case_name] = run_case(case_, patch)
+        check_properties(case_name, case_, traces[case_name])
+    _write(_encode(traces), FIXTURE)
+    print("wrote %s: %d cases, %d distinct launches, %d bytes" % (FIXTURE, len(traces), len(_encode(traces)["launches"]), os.path.getsize(FIXTURE)))
