@@ -1491,12 +1491,15 @@ class ResnetSimple(nn.Module):
         return y
 
     # ---- training: train-mode BatchNorm (batch statistics), activations kept for the backward plan --------
-    # One forward walk and one tape-driven backward.  ``bn_fusion`` (round 4, csrc/bn.hip "round 4", csrc/gemm1x1.hip PRE / EPI) chooses
-    # the BatchNorm form of every unit when it is RECORDED: off = the three-launch kernels of rounds 1-3 (bn_train_fwd / bn_train_bwd);
-    # on = statistics finished inside the launch that sums them, BatchNorm + ReLU applied by the consuming 1x1 conv's loader, the backward
-    # reductions in the data-gradient epilogue -- such a record carries ``ab``, and only such records are eligible for the GEMM forms of
-    # round 6 (sub2, col3, the stem on 192 columns, convT on the GEMM, the head behind the BatchNorm loader, materialize=False).  The
-    # backward unwinds every record the way it was recorded, whatever the attribute says by then.
+    # One forward walk and one tape-driven backward.  Fixed when a unit is RECORDED: its BatchNorm form (``bn_fusion``, round 4, csrc/bn.hip
+    # "round 4", csrc/gemm1x1.hip PRE / EPI: off = the three-launch kernels of rounds 1-3, bn_train_fwd / bn_train_bwd; on = statistics
+    # finished inside the launch that sums them, BatchNorm + ReLU applied by the consuming 1x1 conv's loader, the backward reductions in
+    # the data-gradient epilogue -- such a record carries ``ab``, and only such records are eligible for the GEMM forms of round 6), the
+    # form the conv ran in (``sub2``, ``col3``, the stem's ``gemm``, ``pre`` = behind the producer's BatchNorm loader; what ``stem_on_gemm``
+    # and ``ds_on_gemm`` chose), whether it is one of the Winograd convs (``wino``: ``conv_algorithm``), and the graph: ``src``, the record
+    # that produced its input.  Read again in the backward, each once per record by the two choosers (_dgrad_form, _wgrad_form):
+    # ``conv1x1_algorithm``, ``bn_fusion_3x3``, ``bn_fusion_head``, ``convT_algorithm``, the forced Winograd tile and DREAM_CONVT_WGRAD
+    # (ops), and ``overlap_wgrad`` / ``overlap_max_frames`` (run_backward).
     def _ctr(self, device):
         """Allocator of zero ticket words for the BatchNorm launches of this replica (ops.bn_counter_buffer: every launch takes its own
         slice of one persistent buffer and leaves it zero; the cursor restarts with every forward pass)."""
@@ -1527,16 +1530,16 @@ class ResnetSimple(nn.Module):
         if materialize:
             rec["y"] = ops.bn_apply_ab(rec["z"], rec["ab"], residual, rec["relu"])
 
-    def _unit(self, tape, name, x, conv, bn, relu, residual=None, pre=None, materialize=True):
-        """conv -> BatchNorm(batch statistics) (+ residual) (ReLU) -> the tape record (output: rec["y"]).  ``x``: the conv's input tensor,
-        or -- with ``pre`` = the record of the producing unit -- that unit's un-normalised output z, whose BatchNorm + ReLU this conv
-        applies while loading.  ``materialize``: see _bn_fwd."""
+    def _unit(self, tape, name, x, conv, bn, relu, residual=None, src=None, pre=False, materialize=True):
+        """conv -> BatchNorm(batch statistics) (+ residual) (ReLU) -> the tape record (output: rec["y"]).  ``src``: the record of the unit
+        that produced the conv's input (None: no BatchNorm unit did).  ``x``: the input tensor, src["y"] -- or, with ``pre``, src's
+        un-normalised output z, whose BatchNorm + ReLU this conv applies while loading.  ``materialize``: see _bn_fwd."""
         fused = self.bn_fusion
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         bias = conv.bias.detach() if conv.bias is not None else None
         cout = int(conv.weight.shape[0])
         sub2 = col3 = None
-        if (fused and self.ds_on_gemm and stride == 2 and pre is None and self.conv1x1_algorithm == "gemm"
+        if (fused and self.ds_on_gemm and stride == 2 and not pre and self.conv1x1_algorithm == "gemm"
                 and int(conv.weight.shape[1]) == int(x.shape[3]) and int(x.shape[3]) % 64 == 0):
             if k == 1:
                 # Round 6: a stride-2 1x1 conv (the trunk's three downsample branches) reads every second pixel of every second row:
@@ -1552,18 +1555,18 @@ class ResnetSimple(nn.Module):
                 # frames: 2704; 36 TFLOP/s) runs on the GEMM over its patch rows (ops.im2col3s2: [pixels][9 Cin]), in all three directions
                 col3 = (int(x.shape[1]), int(x.shape[2]))
                 x, k, stride = ops.im2col3s2(x), 1, 1
-        rec = dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, pre=pre, k=k, stride=stride, has_res=residual is not None,
-                   y=None, ab=None, sub2=sub2, col3=col3)
+        rec = dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, src=src, pre=pre, k=k, stride=stride,
+                   has_res=residual is not None, y=None, ab=None, sub2=sub2, col3=col3, wino=self._wino_train(conv))
         if col3 is not None or self._gemm1x1(conv, x, k, stride):
             packed, rows = self._g(name, conv, 0, col3 is not None)
             if fused:
                 rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn(
-                    x, packed, rows, bn, self._ctr(x.device), pre_ab=None if pre is None else pre["ab"], shift=bias)
+                    x, packed, rows, bn, self._ctr(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
             else:
                 rec["z"] = ops.conv1x1(x, packed, rows, None, bias, None, 0)
         else:
-            assert pre is None
-            if self._wino_train(conv):
+            assert not pre
+            if rec["wino"]:
                 tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), int(conv.weight.shape[1]), cout, int(x.shape[0]))
                 u, rows = self._wino(name, conv, 0, tile)
                 if fused and self.bn_fusion_3x3 and tile == 2 and cout % 64 == 0:
@@ -1579,7 +1582,7 @@ class ResnetSimple(nn.Module):
         return rec
 
     def _wino_train(self, conv):
-        """Training: the stride-1 3x3 convs of the bottlenecks (forward and data gradient) on the Winograd kernel."""
+        """Training: the stride-1 3x3 convs of the bottlenecks (forward and data gradient) on the Winograd kernel (rec["wino"])."""
         return (self.conv_algorithm == "winograd" and int(conv.kernel_size[0]) == 3 and int(conv.stride[0]) == 1
                 and int(conv.weight.shape[1]) % 16 == 0 and int(conv.weight.shape[0]) % 16 == 0
                 and min(int(conv.weight.shape[0]), int(conv.weight.shape[1])) >= 64)
@@ -1600,16 +1603,16 @@ class ResnetSimple(nn.Module):
             self._ctr_pos = 0
         tape = []
         ho, wo = (int(x.shape[2]) + 6 - 7) // 2 + 1, (int(x.shape[3]) + 6 - 7) // 2 + 1
-        stem = dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, y=None, ab=None)
-        if fused and self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and (int(x.shape[0]) * ho * wo + 64) * 192 * 4 < (1 << 31):
+        stem = dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, has_res=False, y=None, ab=None, k=1, stride=1,
+                    gemm=fused and self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and (int(x.shape[0]) * ho * wo + 64) * 192 * 4 < (1 << 31))
+        stem["x"] = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0" if stem["gemm"] else "w"])
+        if stem["gemm"]:
             # Round 6: the 7x7 stem as a GEMM over im2col rows of 192 columns (147 taps, zero-padded to the 1x1 GEMM's granularity -- 160
             # for the direct kernel): the BatchNorm statistics ride in its epilogue (one pass over the 16 x 200 x 200 x 64 output less) and
             # its weight gradient runs on the GEMM-shaped kernel (0.56 -> ~0.2 ms on the MAIN stream: it is the last launch of a step)
-            stem["x"] = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0"])
             stem["z"], stem["ab"], stem["mean"], stem["invstd"] = ops.conv1x1_bn(
                 stem["x"], self._stem_weight("g0"), 64, self.bn1, self._ctr(stem["x"].device))
         else:
-            stem["x"] = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["w"])
             stem["z"] = ops.conv2d(stem["x"], self._stem_weight("w"), 64, 1, 1)
         self._bn_fwd(stem)
         tape.append(stem)
@@ -1618,245 +1621,259 @@ class ResnetSimple(nn.Module):
         else:
             y, pidx = ops.maxpool3s2(stem["y"]), None
         tape.append(dict(kind="pool", x=stem["y"], idx=pidx))
+        src = None       # the record that produced y (None behind the pool: no BatchNorm whose backward a data gradient could take along)
         for name, blk in self._trunk():
-            ds = hasattr(blk, "downsample")
-            tape.append(dict(kind="block_begin", name=name, ds=ds))
-            idt = y
-            if ds:
-                idt = self._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)["y"]
-            o = self._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True)["y"]
+            ds, idt = None, y
+            if hasattr(blk, "downsample"):
+                ds = self._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False, src=src)
+                idt = ds["y"]
+            r1 = self._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True, src=src)
             # fused: conv2's BatchNorm + ReLU is applied by conv3's loader when conv3 runs on the GEMM kernel (always, for ResNet-101)
-            r2 = self._unit(tape, name + ".2", o, blk.conv2, blk.bn2, relu=True, materialize=not fused)
-            pre = None
+            r2 = self._unit(tape, name + ".2", r1["y"], blk.conv2, blk.bn2, relu=True, src=r1, materialize=not fused)
+            pre = False
             if fused:
                 # ... and when the BACKWARD GEMM applies too: conv3's data gradient (conv1x1_bwd_bnmask) reads dz3, which has 4x the
                 # channels of z2 and crosses the kernel's 2-GB offset limit first; relu(BN(z2)) is never stored on this path, so the
                 # decision has to be made here (round-4 advice: ~210 frames of 400x400 per GPU would pass the forward and raise in the backward)
                 z2 = r2["z"]
                 dz3_fits = int(z2.shape[0]) * int(z2.shape[1]) * int(z2.shape[2]) * int(blk.conv3.weight.shape[0]) * 4 < (1 << 31)
-                if self._gemm1x1(blk.conv3, z2) and dz3_fits:
-                    pre = r2
-                else:
+                pre = self._gemm1x1(blk.conv3, z2) and dz3_fits
+                if not pre:
                     r2["y"] = ops.bn_apply_ab(z2, r2["ab"], None, True)
-            y = self._unit(tape, name + ".3", r2["y"] if pre is None else r2["z"], blk.conv3, blk.bn3, relu=True, residual=idt, pre=pre)["y"]
-            tape.append(dict(kind="block_end", name=name))
+            src = self._unit(tape, name + ".3", r2["z"] if pre else r2["y"], blk.conv3, blk.bn3, relu=True, residual=idt, src=r2, pre=pre)
+            # the Bottleneck, unwound as one by the backward: its units (recorded above) and the record whose output is its input
+            tape.append(dict(kind="block", name=name, ds=ds, u1=r1, u2=r2, u3=src, src=r1["src"]))
+            y = src["y"]
         stages = list(self._decoder())
         for j, (name, m, bn) in enumerate(stages):
             if bn is not None:
                 z = self._convT_forward(name, m, y, None, m.bias.detach() if m.bias is not None else None, 0, gemm=fused)
-                rec = dict(kind="convT", name=name, conv=m, bn=bn, relu=True, x=y, z=z, y=None, ab=None)
+                rec = dict(kind="convT", name=name, conv=m, bn=bn, relu=True, has_res=False, x=y, src=src, z=z, y=None, ab=None)
                 # Round 6: the LAST decoder layer's normalised activation is consumed by the head conv only -- which applies the
                 # BatchNorm + ReLU in its loader (and so do its weight gradient and the mask of its data gradient): never stored
                 head = stages[j + 1][1] if j + 1 < len(stages) else None
                 self._bn_fwd(rec, materialize=not self._head_on_gemm(head, z))
                 tape.append(rec)
-                y = rec["y"]
+                y, src = rec["y"], rec
             elif y is None:                                   # the head conv on the 1x1 GEMM, behind the BatchNorm loader
-                prev = tape[-1]
                 cout = int(m.weight.shape[0])
                 n4 = ops.round_up(cout, 4)
                 packed = self._g_head(name, m, 0, n4)
                 bias4 = self._cached(("g0hb", name), [m.bias], lambda: torch.cat([m.bias.detach(), m.bias.new_zeros((n4 - cout,))]))
-                y = ops.nhwc_to_nchw(ops.conv1x1_pre(prev["z"], packed, n4, prev["ab"], bias4))
+                y = ops.nhwc_to_nchw(ops.conv1x1_pre(src["z"], packed, n4, src["ab"], bias4))
                 if n4 != cout:
                     y = y[:, :cout].contiguous()
-                tape.append(dict(kind="final", name=name, conv=m, x=None))
+                tape.append(dict(kind="final", name=name, conv=m, x=src["z"], src=src, pre=True, k=1, stride=1))
             else:
                 packed, rows, _ = self._packed_w(name, m, 0)
-                tape.append(dict(kind="final", name=name, conv=m, x=y))
+                tape.append(dict(kind="final", name=name, conv=m, x=y, src=src, pre=False, k=1, stride=1))
                 y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
         return y, tape
 
-    def _bn_bwd(self, rec, dy, want_g=False):
-        """BatchNorm backward of a unit -> (dz, g or None, dgamma, dbeta), as the unit was recorded.  Without ``ab``: the three-launch
-        kernel.  With: two launches -- (dgamma, dbeta) finished inside the reduction launch, then dz (and the masked gradient g when the
-        Bottleneck's identity branch needs it); the ReLU mask comes from the stored activation where the forward pass wrote one, else it
-        is recomputed from (z, ab).  ``dy`` = ("masked", g, dgamma, dbeta): the consumer's data-gradient epilogue already masked and
-        summed (conv1x1_bwd_bnmask) -- one launch."""
-        bn = rec["bn"]
-        if rec["ab"] is None:
-            return ops.bn_train_bwd(rec["z"], dy, rec["y"], bn.weight, rec["mean"], rec["invstd"], rec["relu"], want_g=want_g)
-        if isinstance(dy, tuple):
-            _, g, dgam, dbet = dy
-            dz, _ = ops.bn_bwd_apply(rec["z"], g, bn.weight, rec["mean"], rec["invstd"], dgam, dbet)
-            return dz, g, dgam, dbet
-        y_act = rec["y"] if rec["relu"] else None
-        ab = rec["ab"] if (rec["relu"] and y_act is None) else None
-        dgam, dbet = ops.bn_bwd_stats(rec["z"], dy, rec["mean"], rec["invstd"], self._ctr(rec["z"].device), y_act=y_act, ab=ab)
-        dz, g = ops.bn_bwd_apply(rec["z"], dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=want_g)
-        return dz, g, dgam, dbet
+    # ---- the two choosers of the backward plan ------------------------------------------------------------------------------------
+    def _dgrad_form(self, rec, dz, joins=False):
+        """Which form does this record's data gradient take?  -> (form, Winograd tile or 0).  The "_mask" forms: the gradient, the ReLU mask of
+        the BatchNorm that produced the input (rec["src"]) and that BatchNorm's two backward sums in ONE launch.  ``joins``: see _bwd_block."""
+        conv, p = rec["conv"], rec["src"]
+        cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
+        if rec["kind"] == "final":
+            # the head behind the last decoder BatchNorm.  Not _head_on_gemm: the activation may have been stored and no bias is needed, and
+            # the limits are the backward GEMM's -- z and the gradient with its K = 7 (17) keypoint channels zero-padded to 32 below 2^31
+            # (the forward's loader gives up at 47 frames of 400x400)
+            fused = (self.bn_fusion_head and p is not None and p["kind"] == "convT" and p["ab"] is not None and self.conv1x1_algorithm == "gemm"
+                     and cin % 64 == 0 and tuple(p["z"].shape) == tuple(dz.shape[:3]) + (cin,) and p["z"].numel() < (1 << 31)
+                     and (p["z"].numel() // cin) * ops.round_up(cout, 32) * 4 < (1 << 31))
+            return ("gemm_mask" if fused else "direct"), 0
+        if rec["pre"]:                            # a 1x1 conv behind the BatchNorm loader: relu(BN(z)) was never stored
+            return "gemm_mask", 0
+        bn_relu = p is not None and p["kind"] == "conv" and p["ab"] is not None and p["relu"]
+        if rec["wino"]:
+            tile = ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), cout, cin, int(dz.shape[0]))
+            if (self.bn_fusion_3x3 and tile == 2 and cin % 64 == 0 and int(dz.shape[3]) == cout and bn_relu and not p["has_res"]
+                    and p["y"] is not None and not joins):
+                return "wino_mask", 2
+            return "wino", tile
+        if rec["col3"] is not None:               # the conv ran on its patch rows
+            return "col3", 0
+        if not self._gemm1x1(conv, dz, rec["k"], rec["stride"], bwd=True):
+            return "direct", 0
+        # the block's input is the previous Bottleneck's output relu(BN3(z3) + identity): one full pass over three 4x-wide tensors and
+        # one launch fewer per Bottleneck
+        if joins and bn_relu and p["has_res"] and p["y"] is not None and tuple(p["y"].shape) == tuple(dz.shape[:3]) + (cin,):
+            return "gemm_mask", 0
+        return "gemm", 0
 
-    def _bwd_data(self, name, conv, dz, cin, k, stride, in_hw, residual=None):
-        if self._wino_train(conv):
-            tile = ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), int(conv.weight.shape[0]), int(conv.weight.shape[1]), int(dz.shape[0]))
+    def _dgrad(self, rec, dz, residual=None, form=None):
+        """Launches the data gradient of a conv / final record in its form -> the gradient w.r.t. the record's input (+ ``residual``), plain
+        or as ("masked", g, dgamma, dbeta): already masked and summed for the producer's BatchNorm (_unit_bwd)."""
+        form, tile = form or self._dgrad_form(rec, dz, joins=residual is not None)
+        name, conv, p = rec["name"], rec["conv"], rec["src"]
+        cin = int(conv.weight.shape[1])
+        if form == "gemm_mask":
+            # the head's is the same form on another packed operand: the contraction is its keypoint channels, zero-padded (dz: _bwd_final).
+            # The mask: the stored activation where the forward pass wrote one, else recomputed from (z, ab) -- which a residual rules out.
+            packed_t = self._g_head(name, conv, 1, int(dz.shape[3])) if rec["kind"] == "final" else self._g(name, conv, 1)[0]
+            return ("masked",) + ops.conv1x1_bwd_bnmask(dz, packed_t, cin, p["z"], None if p["has_res"] else p["ab"], p["mean"], p["invstd"],
+                                                        self._ctr(dz.device), y_act=p["y"], residual=residual)
+        if form == "wino_mask":
+            # the F(2x2) kernel; the mask is recomputed from the producer's (z, ab) exactly as its apply pass evaluated it
+            u_t, _ = self._wino(name, conv, 1, tile)
+            return ("masked",) + ops.conv3x3_winograd_bwd_bnmask(dz, u_t, cin, p["z"], p["ab"], p["mean"], p["invstd"], self._ctr(dz.device))
+        if form == "wino":
             u_t, rows = self._wino(name, conv, 1, tile)
             return ops.conv3x3_winograd_tile(tile, dz, u_t, rows, None, None, residual, 0)
-        if self._gemm1x1(conv, dz, k, stride, bwd=True):
+        if form == "col3":
+            # the GEMM's data gradient is the gradient of the patch rows, summed back onto the map
+            packed_t, rows = self._g(name, conv, 1, col3=True)
+            return ops.col2im3s2(ops.conv1x1(dz, packed_t, rows, None, None, None, 0), *rec["col3"])
+        if form == "gemm":
             packed_t, rows = self._g(name, conv, 1)
-            return ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
-        packed_t, rows, _ = self._packed_w(name, conv, 1)
-        return ops.conv2d_bwd_data(dz, packed_t, cin, k, stride, in_hw, residual=residual)
+            g = ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
+        else:
+            packed_t, rows, _ = self._packed_w(name, conv, 1)
+            g = ops.conv2d_bwd_data(dz, packed_t, cin, rec["k"], rec["stride"], (int(rec["x"].shape[1]), int(rec["x"].shape[2])), residual=residual)
+        # a conv that ran on the gathered pixels (sub2): its data gradient back on the input's grid
+        return g if rec.get("sub2") is None else ops.scatter2(g, *rec["sub2"])
+
+    def _wgrad_form(self, rec, dz):
+        """Which kernel computes this record's weight gradient, and which tensors does its leaf read?  -> (form, tensors); a third tensor
+        is the producer's ``ab`` where the conv ran behind its BatchNorm loader (so does the weight gradient's)."""
+        kind, x = rec["kind"], rec["x"]
+        cout = int(rec["conv"].weight.shape[0])
+        if kind == "convT":
+            return ("convT_winograd" if ops.convT4x4_wgrad_winograd_applies(x, dz) else "convT"), [x, dz]
+        if kind == "stem":
+            return ("gemm" if rec["gemm"] else "direct"), [x, dz]
+        if kind == "final":
+            return ("gemm", [x, dz, rec["src"]["ab"]]) if rec["pre"] else ("direct", [x, dz])
+        if rec["col3"] is not None:
+            return "gemm", [x, dz]
+        if rec["pre"]:
+            return ("gemm" if ops.conv1x1_wgrad_applies(x, dz, cout) else "apply_direct"), [x, dz, rec["src"]["ab"]]
+        if rec["wino"] and ops.wgrad_winograd_pays(int(dz.shape[0]) * int(dz.shape[1]) * int(dz.shape[2]), int(x.shape[3]), cout):
+            return "winograd", [x, dz]
+        if self.conv1x1_algorithm == "gemm" and rec["k"] == 1 and rec["stride"] == 1 and ops.conv1x1_wgrad_applies(x, dz, cout):
+            return "gemm", [x, dz]
+        return "direct", [x, dz]
+
+    def _wgrad(self, rec, dz, bw):
+        """The weight (and bias) gradient of a stem / conv / convT / final record: one leaf off the data-gradient chain, in _wgrad_form's form."""
+        form, inputs = self._wgrad_form(rec, dz)
+        kind, conv, x, grads = rec["kind"], rec["conv"], rec["x"], bw["grads"]
+        pre_ab = inputs[2] if len(inputs) > 2 else None
+        cout, kin = int(conv.weight.shape[0]), int(x.shape[3])
+
+        def leaf():
+            db = None
+            if form == "convT_winograd":      # nine-position minimal filtering + the bias sums, one launch
+                dw, db = ops.convT4x4_wgrad_winograd(x, dz)
+            elif form == "convT":
+                dw = ops.convT4x4_wgrad(x, dz)
+            elif form == "gemm":              # the GEMM over positions, of the conv as it RAN: 1x1, im2col rows (stem), patch rows (col3)
+                dw = ops.conv1x1_wgrad(x, dz, ops.round_up(cout, 4), kin, pre_ab=pre_ab)
+            elif form == "winograd":
+                dw = ops.conv3x3_wgrad_winograd(x, dz, cout, kin, want_bias=False)[0]
+            else:                             # "direct"; "apply_direct": on the activation the loader would have applied
+                x_in = ops.bn_apply_ab(x, pre_ab, None, True) if form == "apply_direct" else x
+                dw, db = ops.conv2d_wgrad(x_in, dz, cout, kin, rec["k"], rec["stride"], 0, want_bias=kind == "final")
+            # dW of the conv as it ran -> the parameter's layout
+            if kind == "stem":                # [64][147 taps, zero-padded to 160 / 192 columns]
+                dw = dw.reshape(cout, kin)[:, :147].reshape(cout, 3, 7, 7).contiguous()
+            elif kind == "final":             # (rows padded to the GEMM's granularity)
+                dw = dw[:cout]
+            elif kind == "conv" and rec["col3"] is not None:       # [Cout][t Cin + c] -> [Cout][Cin][3][3]
+                dw = dw.reshape(cout, 3, 3, kin // 9).permute(0, 3, 1, 2).contiguous()
+            grads[conv.weight] = dw
+            if kind in ("convT", "final"):
+                grads[conv.bias] = db if db is not None else ops.channel_sum(dz)[:int(conv.bias.shape[0])]
+        if kind == "stem":                    # in the chain: it is the last launch of a step
+            leaf()
+        else:
+            _on_side(bw["side"], leaf, *inputs)
+
+    # ---- the backward plan: one method per kind of record -------------------------------------------------------------------------------
+    def _unit_bwd(self, rec, dy, bw):
+        """The backward of a unit behind its conv, as the unit was recorded: BatchNorm backward, its parameters' gradients, the conv's
+        weight-gradient leaf -> (dz, g = the masked dy of a unit with a residual: the identity branch's gradient).  Without ``ab``: the
+        three-launch kernel.  With: two launches -- (dgamma, dbeta) finished inside the reduction launch, then dz (and g); the ReLU mask
+        comes from the stored activation where the forward pass wrote one, else it is recomputed from (z, ab).  ``dy`` = ("masked", g,
+        dgamma, dbeta): the consumer's data-gradient epilogue already masked and summed (_dgrad) -- one launch."""
+        bn, z, g = rec["bn"], rec["z"], None
+        if rec["ab"] is None:
+            dz, g, dgam, dbet = ops.bn_train_bwd(z, dy, rec["y"], bn.weight, rec["mean"], rec["invstd"], rec["relu"], want_g=rec["has_res"])
+        elif isinstance(dy, tuple):
+            _, g, dgam, dbet = dy
+            dz, _ = ops.bn_bwd_apply(z, g, bn.weight, rec["mean"], rec["invstd"], dgam, dbet)
+        else:
+            y_act = rec["y"] if rec["relu"] else None
+            ab = rec["ab"] if (rec["relu"] and y_act is None) else None
+            dgam, dbet = ops.bn_bwd_stats(z, dy, rec["mean"], rec["invstd"], self._ctr(z.device), y_act=y_act, ab=ab)
+            dz, g = ops.bn_bwd_apply(z, dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=rec["has_res"])
+        bw["grads"][bn.weight], bw["grads"][bn.bias] = dgam, dbet
+        self._wgrad(rec, dz, bw)
+        return dz, g
+
+    def _bwd_final(self, rec, g, bw):
+        cout = int(rec["conv"].weight.shape[0])
+        gy = ops.nchw_to_nhwc(bw["grad_out"], cpad=ops.round_up(cout, 16))
+        self._wgrad(rec, gy, bw)
+        form = self._dgrad_form(rec, gy)
+        if form[0] == "gemm_mask" and int(gy.shape[3]) != ops.round_up(cout, 32):
+            # Round 6: the head's data gradient on the 1x1 GEMM (one launch instead of the direct conv + the stand-alone reduction pass
+            # over two 16 x 208 x 208 x 256 tensors) contracts over the keypoint channels zero-padded to the GEMM's 32
+            gy = ops.nchw_to_nhwc(bw["grad_out"], cpad=ops.round_up(cout, 32))
+        return self._dgrad(rec, gy, form=form)
+
+    def _bwd_convT(self, rec, g, bw):
+        m, name = rec["conv"], rec["name"]
+        dz, _ = self._unit_bwd(rec, g, bw)
+        cin_t, cout_t = int(m.weight.shape[0]), int(m.weight.shape[1])
+        if (self.convT_algorithm == "winograd" and cout_t % 16 == 0 and cout_t >= 32 and cin_t > 64
+                and int(dz.shape[3]) == cout_t and dz.shape[1] % 2 == 0 and dz.shape[2] % 2 == 0):
+            tile = ops.conv4x4s2_winograd_tile_of(dz, cin_t)
+            u4b, rows = self._cached(("wu4b", name, tile), [m.weight], lambda: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile, 1))
+            return ops.conv4x4s2_winograd_tile(tile, dz, u4b, rows)
+        pk, rows = self._cached(("wTb", name), [m.weight], lambda: ops.pack_convT4x4_bwd_weight(m.weight.detach()))
+        return ops.conv4x4s2(dz, pk, rows)
+
+    def _bwd_block(self, blk, g, bw):
+        """A Bottleneck: .3, .2, .1, the downsample branch, then the gradients that meet at the block's input -- conv1's data gradient joins
+        them: the identity (or downsample) branch's rides in as its residual (no separate add kernel)."""
+        dz, g_idt = self._unit_bwd(blk["u3"], g, bw)           # masked block-output gradient == gradient of the identity branch
+        dz, _ = self._unit_bwd(blk["u2"], self._dgrad(blk["u3"], dz), bw)
+        dz1, _ = self._unit_bwd(blk["u1"], self._dgrad(blk["u2"], dz), bw)
+        if blk["ds"] is not None:
+            dz, _ = self._unit_bwd(blk["ds"], g_idt, bw)
+            g_idt = self._dgrad(blk["ds"], dz)
+        g = self._dgrad(blk["u1"], dz1, residual=g_idt)
+        _early_bucket_hook(bw["reducer"], blk["name"], bw["side"], lambda: [bw["grads"][p] for p in self._early_bucket_params()])
+        return g
+
+    def _bwd_conv(self, rec, g, bw):
+        return g                                  # a Bottleneck's unit: unwound from the block's record (_bwd_block)
+
+    def _bwd_pool(self, rec, g, bw):
+        if rec["idx"] is None:
+            return ops.maxpool3s2_bwd(g, rec["x"])
+        return ops.maxpool3s2_idx_bwd(g, rec["idx"], rec["x"].shape)
+
+    def _bwd_stem(self, rec, g, bw):
+        self._unit_bwd(rec, g, bw)
+        return None
 
     def run_backward(self, tape, grad_out_nchw, reducer=None):
-        """-> {parameter: gradient}.  Walks the tape backwards; gradients that meet at a Bottleneck input are summed
-        by the residual input of the data-gradient conv (no separate add kernel).  A gradient that a data-gradient launch already masked
-        and reduced for its producer's BatchNorm travels as ("masked", g, dgamma, dbeta) (_bn_bwd)."""
+        """-> {parameter: gradient}.  Walks the tape backwards, one method per kind of record; ``g``: the gradient w.r.t. the record's output,
+        plain or -- already masked and reduced for its producer's BatchNorm by a data-gradient launch -- ("masked", g, dgamma, dbeta)."""
         grads = _GradDict(reducer)
         # Measured (resnet_h, 400x400, one MI355X): +6.5 / +5.7 / +5.3 % at 16 / 32 / 64 frames, -2.7 % at 128, where
         # every kernel already fills the chip and the two streams only disturb each other's L2.
         stem_x = tape[0]["x"]                                  # im2col of the input: [B, H/2, W/2, 160 or 192]
         input_px = 4 * int(stem_x.shape[0]) * int(stem_x.shape[1]) * int(stem_x.shape[2])
         side = _SideStream.create(grad_out_nchw, self.overlap_wgrad and input_px <= self.overlap_max_frames * 400 * 400)
-        g = None                 # gradient w.r.t. the output of the unit being processed
-        block = None             # state of the Bottleneck being unwound
-        for idx in range(len(tape) - 1, -1, -1):
-            rec = tape[idx]
-            kind = rec["kind"]
-            if kind == "final":
-                m = rec["conv"]
-                cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
-                gy = ops.nchw_to_nhwc(grad_out_nchw, cpad=ops.round_up(cout, 16))
-                prev = tape[idx - 1] if idx >= 1 else None
-                if rec["x"] is None:                              # the head ran behind the BatchNorm loader: so does its weight gradient
-                    def leaf(m=m, prev=prev, gy=gy, cout=cout, cin=cin):
-                        n4 = ops.round_up(cout, 4)
-                        grads[m.weight] = ops.conv1x1_wgrad(prev["z"], gy, n4, cin, pre_ab=prev["ab"])[:cout]
-                        grads[m.bias] = ops.channel_sum(gy)[:cout]
-                    _on_side(side, leaf, prev["z"], gy, prev["ab"])
-                else:
-                    def leaf(m=m, x=rec["x"], gy=gy, cout=cout, cin=cin):
-                        grads[m.weight], grads[m.bias] = ops.conv2d_wgrad(x, gy, cout, cin, 1, 1, 0, want_bias=True)
-                    _on_side(side, leaf, rec["x"], gy)
-                if (self.bn_fusion_head and prev is not None and prev["kind"] == "convT" and prev["y"] is rec["x"] and prev["ab"] is not None
-                        and self.conv1x1_algorithm == "gemm" and int(m.kernel_size[0]) == 1 and cin % 64 == 0
-                        and tuple(prev["z"].shape) == tuple(gy.shape[:3]) + (cin,) and prev["z"].numel() < (1 << 31)
-                        and (prev["z"].numel() // cin) * ops.round_up(cout, 32) * 4 < (1 << 31)):
-                    # Round 6: the head's data gradient on the 1x1 GEMM with the LAST decoder BatchNorm's ReLU mask and its two backward sums
-                    # in the epilogue (the trunk's form, conv1x1_bwd_bnmask): one launch instead of the direct conv + the stand-alone
-                    # reduction pass over two 16 x 208 x 208 x 256 tensors.  The contraction is the K = 7 (17) keypoint channels, zero-padded
-                    # to the GEMM's 32.
-                    kp = ops.round_up(cout, 32)
-                    gy32 = gy if int(gy.shape[3]) == kp else ops.nchw_to_nhwc(grad_out_nchw, cpad=kp)
-                    gmask, dgh, dbh = ops.conv1x1_bwd_bnmask(gy32, self._g_head(rec["name"], m, 1, kp), cin, prev["z"], prev["ab"], prev["mean"],
-                                                             prev["invstd"], self._ctr(gy32.device), y_act=prev["y"])   # (y None: the mask from (z, ab))
-                    g = ("masked", gmask, dgh, dbh)
-                else:
-                    packed_t, rows, _ = self._packed_w(rec["name"], m, 1)
-                    g = ops.conv2d(gy, packed_t, rows, 1, 1)
-            elif kind == "convT":
-                m, bn = rec["conv"], rec["bn"]
-                dz, _, dgam, dbet = self._bn_bwd(rec, g)
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                def leaf(m=m, x=rec["x"], dz=dz):
-                    if ops.convT4x4_wgrad_winograd_applies(x, dz):        # nine-position minimal filtering + the bias sums, one launch
-                        grads[m.weight], grads[m.bias] = ops.convT4x4_wgrad_winograd(x, dz)
-                    else:
-                        grads[m.weight] = ops.convT4x4_wgrad(x, dz)
-                        grads[m.bias] = ops.channel_sum(dz)
-                _on_side(side, leaf, rec["x"], dz)
-                cin_t, cout_t = int(m.weight.shape[0]), int(m.weight.shape[1])
-                if (self.convT_algorithm == "winograd" and cout_t % 16 == 0 and cout_t >= 32 and cin_t > 64
-                        and int(dz.shape[3]) == cout_t and dz.shape[1] % 2 == 0 and dz.shape[2] % 2 == 0):
-                    tile = ops.conv4x4s2_winograd_tile_of(dz, cin_t)
-                    u4b, rows = self._cached(("wu4b", rec["name"], tile), [m.weight], lambda m=m, tile=tile: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile, 1))
-                    g = ops.conv4x4s2_winograd_tile(tile, dz, u4b, rows)
-                else:
-                    pk, rows = self._cached(("wTb", rec["name"]), [m.weight], lambda m=m: ops.pack_convT4x4_bwd_weight(m.weight.detach()))
-                    g = ops.conv4x4s2(dz, pk, rows)
-            elif kind == "block_end":
-                block = dict(g_out=g, g_idt=None, g_ds=None)
-            elif kind == "conv":
-                conv, bn, name = rec["conv"], rec["bn"], rec["name"]
-                cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
-                is_ds = name.endswith(".ds")
-                dy = block["g_idt"] if is_ds else g
-                dz, gm, dgam, dbet = self._bn_bwd(rec, dy, want_g=rec["has_res"])
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                if rec["has_res"]:
-                    block["g_idt"] = gm          # masked block-output gradient == gradient of the identity branch
-                pre = rec["pre"]
-                def leaf(conv=conv, x=rec["x"], dz=dz, cout=cout, cin=cin, k=rec["k"], stride=rec["stride"], pre=pre, col3=rec["col3"]):
-                    if col3 is not None:         # the conv ran on its patch rows: dW [Cout][t Cin + c] -> [Cout][Cin][3][3]
-                        dw2 = ops.conv1x1_wgrad(x, dz, cout, 9 * cin)
-                        grads[conv.weight] = dw2.reshape(cout, 3, 3, cin).permute(0, 3, 1, 2).contiguous()
-                    elif pre is not None:        # the conv's input was relu(BN(x)), applied by its loader: so does the weight gradient's
-                        if not ops.conv1x1_wgrad_applies(x, dz, cout):
-                            y_in = ops.bn_apply_ab(x, pre["ab"], None, True)
-                            grads[conv.weight] = ops.conv2d_wgrad(y_in, dz, cout, cin, k, stride)[0]
-                        else:
-                            grads[conv.weight] = ops.conv1x1_wgrad(x, dz, cout, cin, pre_ab=pre["ab"])
-                    elif self._wino_train(conv) and ops.wgrad_winograd_pays(int(dz.shape[0]) * int(dz.shape[1]) * int(dz.shape[2]), cin, cout):
-                        grads[conv.weight] = ops.conv3x3_wgrad_winograd(x, dz, cout, cin, want_bias=False)[0]
-                    elif self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and ops.conv1x1_wgrad_applies(x, dz, cout):
-                        grads[conv.weight] = ops.conv1x1_wgrad(x, dz, cout, cin)
-                    else:
-                        grads[conv.weight] = ops.conv2d_wgrad(x, dz, cout, cin, k, stride)[0]
-                _on_side(side, leaf, *([rec["x"], dz] + ([pre["ab"]] if pre is not None else [])))
-                in_hw = (int(rec["x"].shape[1]), int(rec["x"].shape[2]))
-                if is_ds:
-                    block["g_ds"] = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-                    if rec["sub2"] is not None:           # the conv ran on the gathered pixels: its data gradient back on the input's grid
-                        block["g_ds"] = ops.scatter2(block["g_ds"], *rec["sub2"])
-                elif name.endswith(".1"):
-                    # block input: main-path gradient + identity / downsample gradient
-                    block["dz1"] = (name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-                elif pre is not None:
-                    # data gradient + the ReLU mask and the two reductions of the producer's BatchNorm in ONE launch
-                    packed_t, rows = self._g(name, conv, 1)
-                    gmask, dg2, db2 = ops.conv1x1_bwd_bnmask(dz, packed_t, cin, pre["z"], pre["ab"], pre["mean"], pre["invstd"],
-                                                            self._ctr(dz.device))
-                    g = ("masked", gmask, dg2, db2)
-                else:
-                    prod = tape[idx - 1]
-                    if (self.bn_fusion_3x3 and self._wino_train(conv) and cin % 64 == 0 and int(dz.shape[3]) == cout
-                            and prod["kind"] == "conv" and prod["ab"] is not None and prod["y"] is rec["x"] and prod["relu"] and not prod["has_res"]
-                            and ops.winograd_tile(int(dz.shape[1]), int(dz.shape[2]), cout, cin, int(dz.shape[0])) == 2):
-                        # data gradient + the ReLU mask and the two reductions of the producer's BatchNorm in ONE launch of the
-                        # F(2x2) kernel (the mask is recomputed from the producer's (z, ab) exactly as its apply pass evaluated it)
-                        u_t, _ = self._wino(name, conv, 1, 2)
-                        gmask, dg1, db1 = ops.conv3x3_winograd_bwd_bnmask(dz, u_t, cin, prod["z"], prod["ab"], prod["mean"], prod["invstd"],
-                                                                         self._ctr(dz.device))
-                        g = ("masked", gmask, dg1, db1)
-                    elif rec["col3"] is not None:
-                        # the conv ran on its patch rows: the GEMM's data gradient is the gradient of those rows, summed back onto the map
-                        packed_t, rows = self._g(name, conv, 1, col3=True)
-                        g = ops.col2im3s2(ops.conv1x1(dz, packed_t, rows, None, None, None, 0), *rec["col3"])
-                    else:
-                        g = self._bwd_data(name, conv, dz, cin, rec["k"], rec["stride"], in_hw)
-            elif kind == "block_begin":
-                name1, conv1, dz, cin, k, stride, in_hw = block["dz1"]
-                other = block["g_ds"] if rec["ds"] else block["g_idt"]
-                # the block's input is the previous Bottleneck's output relu(BN3(z3) + identity): that BatchNorm's ReLU mask and its
-                # two backward reductions ride in the epilogue of this data-gradient GEMM (one full pass over three 4x-wide tensors
-                # and one launch fewer per Bottleneck)
-                prev = tape[idx - 2] if idx >= 2 and tape[idx - 1]["kind"] == "block_end" else None
-                if (prev is not None and prev["kind"] == "conv" and prev["ab"] is not None and prev["has_res"] and prev["relu"]
-                        and prev["y"] is not None and self._gemm1x1(conv1, dz, k, stride, bwd=True)
-                        and tuple(prev["y"].shape) == tuple(dz.shape[:3]) + (cin,)):
-                    packed_t, rows = self._g(name1, conv1, 1)
-                    gmask, dg3, db3 = ops.conv1x1_bwd_bnmask(dz, packed_t, cin, prev["z"], None, prev["mean"], prev["invstd"],
-                                                            self._ctr(dz.device), y_act=prev["y"], residual=other)
-                    g = ("masked", gmask, dg3, db3)
-                else:
-                    g = self._bwd_data(name1, conv1, dz, cin, k, stride, in_hw, residual=other)
-                block = None
-                _early_bucket_hook(reducer, rec["name"], side, lambda: [grads[p] for p in self._early_bucket_params()])
-            elif kind == "pool":
-                if rec["idx"] is None:
-                    g = ops.maxpool3s2_bwd(g, rec["x"])
-                else:
-                    g = ops.maxpool3s2_idx_bwd(g, rec["idx"], rec["x"].shape)
-            elif kind == "stem":
-                bn = rec["bn"]
-                dz, _, dgam, dbet = self._bn_bwd(rec, g)
-                grads[bn.weight], grads[bn.bias] = dgam, dbet
-                kcol = int(rec["x"].shape[3])                   # 192: the stem ran on the 1x1 GEMM (run_forward_train), 160: direct
-                if kcol == 192:
-                    dw = ops.conv1x1_wgrad(rec["x"], dz, 64, 192)
-                else:
-                    dw, _ = ops.conv2d_wgrad(rec["x"], dz, 64, 160, 1, 1)
-                grads[rec["conv"].weight] = dw.reshape(64, kcol)[:, :147].reshape(64, 3, 7, 7).contiguous()
-                g = None
+        bw = dict(grads=grads, side=side, reducer=reducer, grad_out=grad_out_nchw)
+        g = None
+        for rec in reversed(tape):
+            g = getattr(self, "_bwd_" + rec["kind"])(rec, g, bw)
         if side is not None:
             side.join()
         return grads

@@ -26,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import launch_trace as lt  # noqa: E402
 from dream_amd import data_parallel, models, ops  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "hourglass_launch_trace.json")
@@ -38,13 +39,6 @@ VARIANTS = {
     "vgg_q_full": dict(full_output=True),
     "wide": dict(n_image_input_channels=10),             # the first conv of a later stage: image + previous maps
 }
-PACK_LAUNCHES = ("dream_upsample_conv3x3_weight_as_convT4x4", "dream_convT4x4_phase_weights")
-
-
-def _is_pack(launch):
-    name = launch.split(" ", 1)[0]
-    return name.startswith("dream_pack_") or name in PACK_LAUNCHES
-
 
 def _base_cases():
     """(variant, (B, H, W), pass, options) before the conv_algorithm x tile product."""
@@ -88,28 +82,6 @@ def _net(variant):
     return _nets[variant]
 
 
-class _Recorder:
-    def __init__(self):
-        self.launches = []
-
-    def call(self, name, *args):
-        self.launches.append(" ".join([name] + [repr(a) for a in args if type(a) in (int, float, bool)]))
-
-    @staticmethod
-    def ptr(t):
-        if t is not None and not t.is_contiguous():
-            raise RuntimeError("non-contiguous tensor passed to the HIP library")
-        return None if t is None else _Recorder                 # neither int nor float: dropped from the record
-
-    @staticmethod
-    def stream():
-        return None
-
-
-def _shape(t):
-    return "x".join(str(int(v)) for v in t.shape)
-
-
 def run_case(case, mp):
     """-> {"seq": launches in order, "packs": sorted weight-pack launches, "saved": shapes per plan entry, "error": text or None}."""
     net = _net(case["variant"])
@@ -117,9 +89,8 @@ def run_case(case, mp):
     net.conv_algorithm = case["algo"]
     net.pool_in_training_conv = case.get("pool_in_training_conv", True)
     data_parallel.reset_weight_caches(net)
-    rec = _Recorder()
-    for name in ("call", "ptr", "stream"):
-        mp.setattr(ops, name, getattr(rec, name))
+    rec = lt.Recorder()
+    rec.install(mp, ops)
     mp.setenv("DREAM_FIRST_SUBBATCH", str(case.get("first_subbatch", 0)))
     b, h, w = case["shape"]
     nhwc = case.get("x_is_nhwc", False)
@@ -147,56 +118,28 @@ def run_case(case, mp):
     finally:
         ops.set_winograd_tile(forced)
     assert (error is not None) == bool(case.get("raises"))
-    return dict(seq=[l for l in rec.launches if not _is_pack(l)], packs=sorted(l for l in rec.launches if _is_pack(l)),
-                saved=["saved %s %s" % (_shape(i), _shape(o)) for i, o in saved], error=error)
-
-
-def _count(trace, name):
-    return sum(1 for l in trace["seq"] if l.split(" ", 1)[0] == name)
+    return dict(seq=[l for l in rec.launches if not lt.is_pack(l)], packs=sorted(l for l in rec.launches if lt.is_pack(l)),
+                saved=["saved %s %s" % (lt.shape(i), lt.shape(o)) for i, o in saved], error=error)
 
 
 def check_properties(name, case, trace):
     """What the paths must show whatever the fixture says."""
     unforced_wino = case["algo"] == "winograd" and case["tile"] == 0
     if case["variant"] == "vgg_q" and case["shape"] == (128, 400, 400) and unforced_wino:
-        assert _count(trace, "dream_conv3x3_winograd_nhwc_f32") == 0, name              # every Winograd conv picks F(4x4) on its own
+        assert lt.count(trace, "dream_conv3x3_winograd_nhwc_f32") == 0, name              # every Winograd conv picks F(4x4) on its own
         if case["training"] and case.get("pool_in_training_conv", True):
-            assert _count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 4 and _count(trace, "dream_maxpool2_nhwc_f32") == 0, name
+            assert lt.count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 4 and lt.count(trace, "dream_maxpool2_nhwc_f32") == 0, name
         elif case["training"]:
-            assert _count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 0 and _count(trace, "dream_maxpool2_nhwc_f32") == 4, name
+            assert lt.count(trace, "dream_conv3x3_winograd4_pool_both_nhwc_f32") == 0 and lt.count(trace, "dream_maxpool2_nhwc_f32") == 4, name
     if "first_subbatch" in case:
         sub = case["algo"] == "winograd" and case["tile"] != 2 and not case["training"]
-        assert _count(trace, "dream_conv3x3_first_nchw_f32") == (4 if sub else 1), name
+        assert lt.count(trace, "dream_conv3x3_first_nchw_f32") == (4 if sub else 1), name
     if case["variant"].endswith("_skip") and not case.get("raises"):
-        adds = _count(trace, "dream_add_f32")
+        adds = lt.count(trace, "dream_add_f32")
         folded = not case["training"] and case.get("precision", "fp32") == "fp32"
         assert (adds == 0) if folded else (adds >= 2), name
     if case.get("raises"):
         assert trace["error"].startswith("The size of tensor a (") and "must match the size of tensor b (" in trace["error"], name
-
-
-# ---- fixture: one table of distinct launches, per case the indices into it ---------------------------------------------------------
-def _encode(traces):
-    table = {}
-
-    def idx(items):
-        return [table.setdefault(s, len(table)) for s in items]
-
-    cases = {name: dict(seq=idx(t["seq"]), packs=idx(t["packs"]), saved=idx(t["saved"]), error=t["error"]) for name, t in traces.items()}
-    return dict(launches=list(table), cases=cases)
-
-
-def _decode(fixture, name):
-    t = fixture["cases"][name]
-    return dict(seq=[fixture["launches"][i] for i in t["seq"]], packs=[fixture["launches"][i] for i in t["packs"]],
-                saved=[fixture["launches"][i] for i in t["saved"]], error=t["error"])
-
-
-def _write(fixture, path):
-    with open(path, "w") as f:
-        f.write('{"launches": [\n' + ",\n".join(json.dumps(s) for s in fixture["launches"]) + '\n],\n"cases": {\n')
-        f.write(",\n".join("%s: %s" % (json.dumps(n), json.dumps(c, separators=(",", ":"))) for n, c in fixture["cases"].items()))
-        f.write("\n}}\n")
 
 
 @pytest.fixture(scope="module")
@@ -209,22 +152,16 @@ def test_fixture_covers_exactly_the_cases(fixture):
     assert sorted(fixture["cases"]) == sorted(CASES)
 
 
-def _first_difference(want, got):
-    n = next((i for i, (a, b) in enumerate(zip(want, got)) if a != b), min(len(want), len(got)))
-    return "launch %d of %d (recorded) / %d (now):\n  recorded: %s\n  now:      %s\n  after:    %s" % (
-        n, len(want), len(got), want[n] if n < len(want) else "<end>", got[n] if n < len(got) else "<end>", want[max(0, n - 3):n])
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_launch_trace(name, fixture, monkeypatch):
     case = CASES[name]
     got = run_case(case, monkeypatch)
     check_properties(name, case, got)
-    want = _decode(fixture, name)
+    want = lt.decode(fixture, name)
     assert got["error"] == want["error"]
-    assert got["seq"] == want["seq"], _first_difference(want["seq"], got["seq"])
+    assert got["seq"] == want["seq"], lt.first_difference(want["seq"], got["seq"])
     assert collections.Counter(got["packs"]) == collections.Counter(want["packs"])
-    assert got["saved"] == want["saved"], _first_difference(want["saved"], got["saved"])
+    assert got["saved"] == want["saved"], lt.first_difference(want["saved"], got["saved"])
 
 
 if __name__ == "__main__":
@@ -235,5 +172,5 @@ if __name__ == "__main__":
         with pytest.MonkeyPatch.context() as patch:
             traces[case_name] = run_case(case_, patch)
         check_properties(case_name, case_, traces[case_name])
-    _write(_encode(traces), FIXTURE)
-    print("wrote %s: %d cases, %d distinct launches, %d bytes" % (FIXTURE, len(traces), len(_encode(traces)["launches"]), os.path.getsize(FIXTURE)))
+    lt.write(lt.encode(traces), FIXTURE)
+    print("wrote %s: %d cases, %d distinct launches, %d bytes" % (FIXTURE, len(traces), len(lt.encode(traces)["launches"]), os.path.getsize(FIXTURE)))
