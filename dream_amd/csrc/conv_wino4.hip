@@ -89,7 +89,7 @@ namespace {
 
 struct Wino4Params {
     const float *x;          // [B,H,W,Cin]
-    const float *u;          // [Cin/K][36][CoutPad][K] (+ AHEAD zero positions), K = 16 (wide) or 8 (narrow)
+    const float *u;          // [Cin/K][36][CoutPad][K] (+ AHEAD zero positions), K = 16 (wide) or 8 (narrow: positions in pairs, pack_device.h)
     const float *scale;      // per-channel multiplier (eval-mode BatchNorm fold) or null
     const float *shift;      // per-channel addend (bias / BN shift) or null
     const float *residual;   // ReLU mask source (DREAM_CONV_RELUMASK) or addend of the output's shape, or null
@@ -157,10 +157,13 @@ struct W4Cfg {
     static constexpr int QS = NARROW ? 7 : 6;
     static constexpr int SB = W4T * 6 * SROW * 4;        // floats
     // operand registers of the weight stream: position k of the chunk of parity PH lives in bq[(36 PH + k) % RING] (chunks run in
-    // pairs, so RING must divide 72).  NARROW positions take half the time: twice the positions in flight for the same latency.
+    // pairs, so RING must divide 72).  NARROW positions take half the time: twice the positions in flight for the same latency --
+    // and two positions share a register quad and ONE load (PAIRS: the ring is RING / 2 float4s, a pair in bq[((36 PH + k) / 2) % (RING / 2)]).
     static constexpr int RING = NARROW ? DREAM_W4_NARROW_RING : DREAM_W4_RING;
     static constexpr int AHEAD = RING - 2;               // positions the weight stream runs ahead of the MFMAs (two are in use)
     static_assert(72 % RING == 0, "the weight ring must divide two chunks' positions");
+    static constexpr bool PAIRS = NARROW && DREAM_W4_NARROW_PAIRS;     // the weights of positions 2 k, 2 k + 1 side by side (pack_device.h)
+    static_assert(!PAIRS || RING % 2 == 0, "a ring of whole pairs");
     using vec = std::conditional_t<NARROW, f32x2, f32x4>;   // one lane's MFMA operands of a position: KS floats
 };
 // float4 slot of channel quad q in row t of a V plane
@@ -298,7 +301,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
     //      feeds the 4 / 2 MFMAs of a position: MFMA r multiplies channel KS (l >> 4) + r, on both operands)
     const int lt = lane & 15, lg = lane >> 4;
     const int a_off = NARROW ? lt * W4K + 4 * v4_slot<NARROW>(lg >> 1, lt) + 2 * (lg & 1) : lt * W4K + 4 * v4_slot<NARROW>(lg, lt);
-    const unsigned b_lane = (unsigned)(((wave * 16 + lt) * W4K + C::KS * lg) * 4);
+    const unsigned b_lane = C::PAIRS ? (unsigned)(((wave * 16 + lt) * 16 + 4 * lg) * 4) : (unsigned)(((wave * 16 + lt) * W4K + C::KS * lg) * 4);
     const unsigned u_pos_stride = (unsigned)(p.CoutPad * W4K * 4);
     const BufferRsrc ubuf = make_buffer(p.u + (size_t)n0 * W4K, ((size_t)((p.Cin / W4K) * W4P + C::AHEAD) * p.CoutPad - (size_t)n0) * W4K * sizeof(float));
 
@@ -308,13 +311,16 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
 
     // weight stream: the k-th position of the chunk sequence (k counted from the start of the block, 36 per chunk) lives in
     // bq[k % 8]; the chunk loop is unrolled by two so that the ring index is a compile-time constant (72 % 8 == 0)
-    vec bq[W4_RING];
+    // (PAIRS: one register quad and one load per two positions; a pair's stride is two positions')
+    constexpr int BSTEP = C::PAIRS ? 2 : 1;
+    std::conditional_t<C::PAIRS, f32x4, vec> bq[W4_RING / BSTEP];
     auto load_u = [&](unsigned soff) {
-        if constexpr (NARROW) return buffer_load_x2(ubuf, b_lane, soff);
+        if constexpr (C::PAIRS) return buffer_load_x4(ubuf, b_lane, soff);
+        else if constexpr (NARROW) return buffer_load_x2(ubuf, b_lane, soff);
         else return buffer_load_x4_aux<DREAM_W4_WAUX>(ubuf, b_lane, soff);
     };
 #pragma unroll
-    for (int k = 0; k < W4_AHEAD; ++k) bq[k] = load_u((unsigned)pat4_pos(PAT, k) * u_pos_stride);
+    for (int k = 0; k < W4_AHEAD; k += BSTEP) bq[k / BSTEP] = load_u((unsigned)pat4_pos(PAT, k) * u_pos_stride);
     // The full kernel's weight stream is SEQUENTIAL in memory (position k of chunk c sits at (36 c + k) positions): one running
     // wave-uniform byte offset, bumped after every load and reset where the stream wraps around to the next block's chunk 0.  (As
     // `(36 c + k) * stride` hipcc kept the 36 products k * stride in scalar registers it does not have: 18 v_readlane_b32 + their
@@ -410,22 +416,28 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
             const int pp = pat4_pos(PAT, k0), pp1 = pat4_pos(PAT, two ? k0 + 1 : k0);
             auto load_b = [&](int half) {                                    // weight operands of active position k0 + half + AHEAD
                 if ((DREAM_W4_DIAG & 2) || (half && !two)) return;
+                if (C::PAIRS && half) return;                                 // the slot's two positions came with one load
                 const int kn = k0 + half + W4_AHEAD;
                 if constexpr (PAT == 0 && DREAM_W4_RUNNING_WOFF && !(DREAM_W4_DIAG & 32)) {
                     if (kn == NPOS && last) woff = 0u;                        // wave-uniform: s_cselect
-                    bq[(PH * NPOS + kn) % W4_RING] = load_u(woff);
-                    woff += u_pos_stride;
+                    bq[(PH * NPOS + kn) % W4_RING / BSTEP] = load_u(woff);
+                    woff += BSTEP * u_pos_stride;
                     DREAM_OPAQUE_SGPR(woff);                            // opaque: no re-derivation from the chunk counter
                 } else {
                     const int spos = kn >= NPOS ? cnext + pat4_pos(PAT, kn - NPOS) : c * W4P + pat4_pos(PAT, kn);
-                    bq[(PH * NPOS + kn) % W4_RING] = load_u((DREAM_W4_DIAG & 32) ? 0u : (unsigned)spos * u_pos_stride);
+                    bq[(PH * NPOS + kn) % W4_RING / BSTEP] = load_u((DREAM_W4_DIAG & 32) ? 0u : (unsigned)spos * u_pos_stride);
                 }
             };
             auto load_x = [&](int col) { if (!(DREAM_W4_DIAG & 1)) d[col] = buffer_load_x4_aux<DREAM_W4_XAUX>(xbuf, item_offset(col), (DREAM_W4_DIAG & 64) ? 0u : coff); };
             auto pair = [&](int r) {
                 const int i0 = (PH * NPOS + k0) % W4_RING, i1 = (PH * NPOS + k0 + 1) % W4_RING;
-                acc[pp] = mfma_f32_16x16x4(a[s & 1][0][r], bq[i0][r], acc[pp]);
-                if (two) acc[pp1] = mfma_f32_16x16x4(a[s & 1][1][r], bq[i1][r], acc[pp1]);
+                if constexpr (C::PAIRS) {                                    // i0 even, i1 = i0 + 1: the two halves of quad i0 / 2
+                    acc[pp] = mfma_f32_16x16x4(a[s & 1][0][r], bq[i0 / 2][r], acc[pp]);
+                    acc[pp1] = mfma_f32_16x16x4(a[s & 1][1][r], bq[i0 / 2][2 + r], acc[pp1]);
+                } else {
+                    acc[pp] = mfma_f32_16x16x4(a[s & 1][0][r], bq[i0][r], acc[pp]);
+                    if (two) acc[pp1] = mfma_f32_16x16x4(a[s & 1][1][r], bq[i1][r], acc[pp1]);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             };
             // the four interleave points of a slot; the narrow shape has two MFMA pairs per slot: two points behind each
@@ -707,7 +719,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
 
 // OIHW (mode 0) or, for the data-gradient operator, IOHW with flipped taps (mode 1) -> U = G g G^T in fp64, rounded once to fp32,
 // laid out [cols/K][36 positions][RowsPad][K] with (K, RowsPad) = (16, rows up to a multiple of 128), or (8, 64) for rows <= 64
-// (the narrow workgroup shape): pack_device.h (dream_pack::winograd4)
+// (the narrow workgroup shape, positions in pairs): pack_device.h (dream_pack::winograd4)
 static_assert(W4Cfg<false>::K == 16 && W4Cfg<false>::PAD == 128 && W4Cfg<true>::K == 8 && W4Cfg<true>::PAD == 64 && W4P == 36,
               "pack_device.h assumes 16-channel chunks padded to 128 rows / 8-channel chunks padded to 64 rows, 36 positions");
 __global__ void __launch_bounds__(256) wino4_pack_kernel(const float *w, float *u, int Cout, int Cin, int mode) {

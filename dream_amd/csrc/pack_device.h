@@ -104,7 +104,15 @@ DREAM_DEVICE void winograd2(const float *w, float *u, int Cout, int Cin, int mod
 }
 
 // Winograd F(4x4,3x3) (conv_wino4.hip), interpolation points (0, 1, -1, 1/2, -2, inf): [cols/K][36 positions][RowsPad][K] with
-// (K, RowsPad) = (16, rows up to a multiple of 128), or (8, 64) when rows <= 64 (the kernel's narrow workgroup shape)
+// (K, RowsPad) = (16, rows up to a multiple of 128), or (8, 64) when rows <= 64 (the kernel's narrow workgroup shape).
+// The narrow shape's positions are stored in PAIRS: [cols/8][18 pairs][64 rows][4 lane groups][2 positions][2 k] -- element
+// (chunk ch, position pp, row n, channel kk) at ((((ch * 18 + pp / 2) * 64 + n) * 4 + kk / 2) * 2 + pp % 2) * 2 + kk % 2 -- so that
+// the operands of a lane (row n, channels 2 lg, 2 lg + 1) for positions 2 k and 2 k + 1 are 16 contiguous bytes: one
+// buffer_load_dwordx4 per pair of positions instead of two dwordx2.  Same size, same values.  DREAM_W4_NARROW_PAIRS=0: the
+// position-major layout for the narrow shape too (A/B builds, tools/wino4_diag.py; pack_batched.hip and conv_wino4.hip together).
+#ifndef DREAM_W4_NARROW_PAIRS
+#define DREAM_W4_NARROW_PAIRS 1
+#endif
 template <bool CONVT = false>
 DREAM_DEVICE void winograd4(const float *w, float *u, int Cout, int Cin, int mode, int blk, int nblk) {
     const double G[6][3] = {{1.0, 0.0, 0.0},
@@ -135,7 +143,11 @@ DREAM_DEVICE void winograd4(const float *w, float *u, int Cout, int Cin, int mod
 #pragma unroll
             for (int b = 0; b < 6; ++b) {                           // (G g) G^T
                 const double v = t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2];
-                u[(((size_t)ch * 36 + (a * 6 + b)) * RowsPad + n) * K + kk] = (float)v;
+                const int pp = a * 6 + b;
+                if (DREAM_W4_NARROW_PAIRS && K == 8)
+                    u[(((((size_t)ch * 18 + pp / 2) * RowsPad + n) * 4 + kk / 2) * 2 + (pp & 1)) * 2 + (kk & 1)] = (float)v;
+                else
+                    u[(((size_t)ch * 36 + pp) * RowsPad + n) * K + kk] = (float)v;
             }
     }
 }

@@ -250,7 +250,7 @@ def conv3x3_winograd_tile(tile, x_nhwc, packed_u, cout, scale=None, shift=None, 
 
 
 def pack_weight_winograd4(w_oihw, mode=0):
-    """OIHW [Cout,Cin,3,3] -> the transformed weights of the Winograd F(4x4,3x3) kernel ([cols/K][36][rows_pad][K], K = 16 or -- up to 64 rows -- 8); mode as
+    """OIHW [Cout,Cin,3,3] -> the transformed weights of the Winograd F(4x4,3x3) kernel ([cols/16][36][rows_pad][16], or -- up to 64 rows -- [cols/8][18 pairs][64][4][2 positions][2]); mode as
     pack_weight_winograd.  Returns (packed, rows)."""
     w = _f32(w_oihw)
     cout, cin = int(w.shape[0]), int(w.shape[1])

@@ -142,7 +142,7 @@ int dream_conv3x3_winograd_nhwc_f32(const float *x, const float *u_packed, const
  * transformed in fp64 at pack time.  For the stride-1 3x3 layers of dream/models.py:598-615,695-710 behind the first one.
  * Two workgroup shapes, chosen by the number of output channels (rows of the packed operator): more than 64 -- 128 channels per
  * workgroup, Cin a multiple of 32, weights packed [Cin/16][36][rows up to a multiple of 128][16]; up to 64 -- 64 channels per
- * workgroup, Cin a multiple of 16, weights packed [Cin/8][36][64][8].  Packed weights: dream_conv3x3_winograd4_weight_floats(rows,
+ * workgroup, Cin a multiple of 16, weights packed in pairs of positions, [Cin/8][18][64][4][2][2] (csrc/pack_device.h).  Packed weights: dream_conv3x3_winograd4_weight_floats(rows,
  * cols) floats (either shape); mode / flags as above. */
 size_t dream_conv3x3_winograd4_weight_floats(int rows, int cols);
 int dream_pack_conv3x3_winograd4_weight(const float *w_oihw, float *u, int Cout, int Cin, int mode, void *stream);
