@@ -1,0 +1,296 @@
+// Half-precision ("fp16") implicit-GEMM convolution: fp32 in, fp32 out, fp16 operands with fp32 accumulation on the fp16 matrix
+// cores:   y = epilogue( 2^-(ea+ew) * sum fp16(x * 2^ea) * fp16(w * 2^ew) ),   one v_mfma_f32_32x32x16_f16 per 16 k's.
+// The power-of-two scales are those of the split kernel (conv_f16x3.hip): 2^ea puts max|x| (amax side channel of the producing
+// kernel) into [2^13, 2^14), 2^ew the weight maximum; the weight plane IS the `hi` plane that dream_pack_conv_weight_f16x3 /
+// dream_pack_convT4x4_weight_f16x3 write.  Activations stay fp32 in HBM and are rounded once, while the patch is staged into LDS.
+// A product of two halfs is exact in fp32, so the result differs from an exact conv of the rounded operands only by the fp32
+// accumulation; what the mode costs is the operand rounding (2^-11 relative per operand).  Tiling, tap tables, fused upsample /
+// sub-pixel phases and the epilogue are the split kernel's (conv_f16_common.h, conv_f16_epilogue.inc; same reference call sites:
+// dream/models.py:594-615, 695-747).
+//
+// A stage (one tap x 32 channels) is MR*NR*2 MFMAs = 256 cycles on the 2x2 register block -- a third of the split kernel's -- so what
+// the MFMAs used to hide shows: the fp32 patch loads, their conversion and the barriers.  Two loops, chosen per layer by measurement
+// (launch_f16):
+//   SB  the split kernel's loop without its `lo` lines: one patch buffer, fetched one stage ahead, two barriers at a chunk change;
+//   DB  the patch double-buffered in the LDS the `lo` planes occupied: the next 32-channel patch is written into the other buffer
+//       during the last tap of the current one, so a channel-chunk change costs no barrier of its own (one per stage, always), and
+//       its fp32 loads are issued at the FIRST tap of the current chunk and converted at its last (ntaps stages of cover, not one).
+// Per 16 k's a wave reads MR + NR 16-byte fragments for MR*NR MFMAs: one ds_read_b128 per MFMA on the 2x2 block.
+#include "conv_f16_common.h"
+
+namespace {
+
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16Params p) {
+    constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
+    constexpr int BN = 32 * NR * WN;
+    constexpr int Q = KC / 4;                       // float4 pieces per patch row
+    constexpr int NA_IT = (NPM * Q + NT - 1) / NT;
+    constexpr int NB_PIECES = BN * (KC / 8);        // 16-B pieces of the weight tile per stage
+    constexpr int NB_IT = (NB_PIECES + NT - 1) / NT;
+    static_assert(WM * WN == 4 || WM * WN == 8, "4 or 8 wavefronts per workgroup");
+
+    DREAM_DYNAMIC_LDS(_Float16, smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+    const int wm = wave / WN, wn = wave % WN;
+    const int li = lane & 31, lh = lane >> 5;
+    const int PW = p.PW, TW = p.TW, NP = p.PH * PW;
+    _Float16 *sA = smem;                            // [DB ? 2 : 1][NP][S16]
+    _Float16 *sB = sA + (DB ? 2 : 1) * NP * S16;    // [2][BN][S16]
+
+    // XCD-aware placement (see conv_mfma.hip): each XCD works on a contiguous range of tiles so halos meet in its L2
+    int t = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+    if (t >= p.B * p.tiles_x * p.tiles_y) return;
+    const int tix = t % p.tiles_x;
+    t /= p.tiles_x;
+    const int tiy = t % p.tiles_y;
+    const int b = t / p.tiles_y;
+    const int y0 = tiy * p.TH, x0 = tix * TW;
+    const int n0 = blockIdx.y * BN;
+    const bool zst = (p.flags & DREAM_CONV_ZEROSTUFF2X) != 0;
+    const bool ups = (p.flags & DREAM_CONV_UPSAMPLE2X) != 0 || zst;
+    const bool pool = (p.flags & DREAM_CONV_POOL2) != 0;
+    const float *xb = p.x + (size_t)b * p.Hs * p.Ws * p.Cin;
+
+    // input scale: max|x| * 2^ea in [2^13, 2^14)
+    const unsigned abits = *p.amax_in;
+    const int aexp = (int)((abits >> 23) & 255) - 127;
+    int ea = (abits == 0u) ? 0 : 13 - aexp;
+    ea = ea < -100 ? -100 : (ea > 100 ? 100 : ea);
+    const float sa = pow2f(ea);
+    const float inv = pow2f(-(ea + *p.w_exp) < -126 ? -126 : (-(ea + *p.w_exp) > 127 ? 127 : -(ea + *p.w_exp)));
+
+    int a_goff[NA_IT], a_soff[NA_IT];
+#pragma unroll
+    for (int it = 0; it < NA_IT; ++it) {
+        const int idx = tid + it * NT;
+        const int pp = idx / Q, q = idx % Q;
+        a_soff[it] = (pp < NP) ? pp * S16 + q * 4 : -1;
+        const int py = pp / PW, px = pp - py * PW;
+        const int gy = y0 * p.in_scale - p.pad_y + py * p.in_step, gx = x0 * p.in_scale - p.pad_x + px * p.in_step;
+        const bool inb = (pp < NP) && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win && !(zst && ((gy | gx) & 1));
+        const int sy = ups ? (gy >> 1) : gy, sx = ups ? (gx >> 1) : gx;
+        a_goff[it] = inb ? (sy * p.Ws + sx) * p.Cin + q * 4 : -1;
+    }
+    int b_goff[NB_IT], b_soff[NB_IT];
+#pragma unroll
+    for (int it = 0; it < NB_IT; ++it) {
+        const int idx = tid + it * NT;
+        const int n = idx / (KC / 8), q = idx % (KC / 8);
+        b_soff[it] = (idx < NB_PIECES) ? n * S16 + q * 8 : -1;
+        b_goff[it] = (n0 + n) * p.Cin + q * 8;
+    }
+    const size_t w_tap_stride = (size_t)p.CoutPad * p.Cin;
+
+    int a_frag[MR], b_frag[NR];
+#pragma unroll
+    for (int ms = 0; ms < MR; ++ms) {
+        int m = (wm * MR + ms) * 32 + li;
+        if (m >= p.TH * TW) m = 0;
+        int ty, tx;
+        tile_xy(m, TW, p.rcpTW, pool, &ty, &tx);
+        a_frag[ms] = (ty * PW + tx) * p.lane_stride * S16 + lh * 8;
+    }
+#pragma unroll
+    for (int ns = 0; ns < NR; ++ns) b_frag[ns] = ((wn * NR + ns) * 32 + li) * S16 + lh * 8;
+
+    f32x16 acc[MR][NR];
+#pragma unroll
+    for (int ms = 0; ms < MR; ++ms)
+#pragma unroll
+        for (int ns = 0; ns < NR; ++ns)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ms][ns][r] = 0.0f;
+
+    f32x4 a_reg[NA_IT];
+    f16x8 b_reg[NB_IT];
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    auto load_a = [&](int c0) {
+#pragma unroll
+        for (int it = 0; it < NA_IT; ++it)
+            a_reg[it] = (a_goff[it] >= 0) ? *(const f32x4 *)(xb + a_goff[it] + c0) : zero4;
+    };
+    auto store_a = [&](int abuf) {     // the one rounding of the activations: fp16(v * 2^ea), to nearest even
+        _Float16 *d = sA + abuf * NP * S16;
+#pragma unroll
+        for (int it = 0; it < NA_IT; ++it) {
+            if (a_soff[it] >= 0) {
+                f16x4 h;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) h[k] = (_Float16)(a_reg[it][k] * sa);
+                *(f16x4 *)(d + a_soff[it]) = h;
+            }
+        }
+    };
+    auto load_b = [&](int tap, int c0) {
+        const size_t base = (size_t)((p.tap_w >> (4 * tap)) & 15) * w_tap_stride + c0;
+#pragma unroll
+        for (int it = 0; it < NB_IT; ++it)
+            if (b_soff[it] >= 0) b_reg[it] = *(const f16x8 *)(p.w_hi + base + b_goff[it]);
+    };
+    auto store_b = [&](int buf) {
+        _Float16 *d = sB + buf * BN * S16;
+#pragma unroll
+        for (int it = 0; it < NB_IT; ++it)
+            if (b_soff[it] >= 0) *(f16x8 *)(d + b_soff[it]) = b_reg[it];
+    };
+
+    const int nchunks = p.Cin / KC;
+    load_a(0);
+    load_b(0, 0);
+    store_a(0);
+    store_b(0);
+    __syncthreads();
+
+    int buf = 0, abuf = 0, tap = 0, chunk = 0;
+    const int ntaps = p.ntaps, nstages = nchunks * ntaps;
+    for (int st = 0; st < nstages; ++st) {
+        const bool last_tap = (tap == ntaps - 1);
+        const bool more_chunks = (chunk + 1 < nchunks);
+        const bool have_next = (st + 1 < nstages);
+        if (have_next) load_b(last_tap ? 0 : tap + 1, last_tap ? (chunk + 1) * KC : chunk * KC);
+        // DB: the next chunk's patch is fetched at the first tap and held in registers until the last; SB: one stage ahead
+        if ((DB ? tap == 0 : last_tap) && more_chunks) load_a((chunk + 1) * KC);
+
+        const int tdy = (int)((p.tap_dy >> (4 * tap)) & 15), tdx = (int)((p.tap_dx >> (4 * tap)) & 15);
+        const _Float16 *pa = sA + abuf * NP * S16 + (tdy * PW + tdx) * S16;
+        const _Float16 *pb = sB + buf * BN * S16;
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 16) {
+            f16x8 a[MR], w[NR];
+#pragma unroll
+            for (int ms = 0; ms < MR; ++ms) a[ms] = *(const f16x8 *)(pa + a_frag[ms] + kk);
+#pragma unroll
+            for (int ns = 0; ns < NR; ++ns) w[ns] = *(const f16x8 *)(pb + b_frag[ns] + kk);
+            if (PRIO) __builtin_amdgcn_s_setprio(1);     // co-resident waves of the other workgroup are in their load phase
+#pragma unroll
+            for (int ms = 0; ms < MR; ++ms)
+#pragma unroll
+                for (int ns = 0; ns < NR; ++ns) acc[ms][ns] = mfma_f32_32x32x16_f16(a[ms], w[ns], acc[ms][ns]);
+            if (PRIO) __builtin_amdgcn_s_setprio(0);
+        }
+
+        if (have_next) store_b(buf ^ 1);
+        if (last_tap && more_chunks) {
+            if (DB) {
+                // the other patch buffer was last read in the previous chunk: every wave has passed a barrier since
+                store_a(abuf ^ 1);
+                abuf ^= 1;
+            } else {
+                __syncthreads();
+                store_a(0);
+            }
+        }
+        __syncthreads();
+        buf ^= 1;
+        if (last_tap) { tap = 0; ++chunk; } else ++tap;
+    }
+
+#include "conv_f16_epilogue.inc"
+}
+
+struct Variant16h {
+    const char *name;
+    int BM, BN, NP_MAX, threads, abufs;
+    void (*kernel)(const Conv16Params);
+};
+// Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
+const Variant16h kVariantsF16[] = {
+    {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, conv_f16_kernel<2, 2, 2, 2, 192, true>},
+    {"f16 m2n2w4x1 db", 256, 64, 352, 256, 2, conv_f16_kernel<2, 2, 4, 1, 352, true>},
+    {"f16 m2n1w4x1 db", 256, 32, 352, 256, 2, conv_f16_kernel<2, 1, 4, 1, 352, true>},
+    {"f16 m1n2w2x2 db", 64, 128, 128, 256, 2, conv_f16_kernel<1, 2, 2, 2, 128, true>},
+    {"f16 m2n2w4x2 db", 256, 128, 352, 512, 2, conv_f16_kernel<2, 2, 4, 2, 352, true>},             // 8 waves
+    {"f16 m2n2w4x1 sb", 256, 64, 352, 256, 1, conv_f16_kernel<2, 2, 4, 1, 352, false>},            // the split kernel's loop: 64-channel 3x3 convs
+    {"f16 m2n2w4x2 sb", 256, 128, 352, 512, 1, conv_f16_kernel<2, 2, 4, 2, 352, false>},
+    {"f16 m2n2w4x2 db prio", 256, 128, 352, 512, 2, conv_f16_kernel<2, 2, 4, 2, 352, true, true>},  // A/B arm: s_setprio around the MFMAs
+};
+constexpr int kNumF16 = 8;
+int g_forced_f16 = -1;
+
+int launch_f16(const float *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
+               const float *residual, float *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
+               int flags, void *stream) {
+    DREAM_REQUIRE(x && amax_in && w && w_exp && y, "conv_f16: null pointer");
+    DREAM_REQUIRE(Cin % KC == 0, "conv_f16: Cin=%d must be a multiple of %d", Cin, KC);
+    Conv16Params p;
+    p.x = x; p.w_hi = (const _Float16 *)w; p.w_lo = nullptr; p.w_exp = w_exp; p.amax_in = amax_in;
+    p.scale = scale; p.shift = shift; p.residual = residual; p.y = y; p.amax_out = amax_out;
+    p.B = B;
+    p.Cin = Cin; p.Cout = Cout; p.CoutPad = CoutPad;
+    const long pixels = (long)B * g.H * g.W;
+    // the variant rule, measured per layer at 128 frames (profiles/r07_ab_f16_variants.txt): from 128 output channels on
+    // the 128 x 128 tile wins by 5-12 % (160 VGPRs and 51 KB of LDS: three workgroups per CU; the 256-px tiles hold two); a 64-channel
+    // 3x3 conv is 3 % faster on the single-buffered 256 x 64 tile, a 64-channel 1x1 conv (a chunk change per stage) 15 % on the
+    // double-buffered one
+    int v = Cout <= 32 ? 2 : (Cout <= 64 ? (g.ntaps == 1 ? 1 : 5) : 0);
+    // tiny grids: 64-px tiles -- unless the launch is deep (the first decoder conv: 4 taps x 2048 channels on 13 x 13 maps), where the
+    // weight tile is what a workgroup streams and the 256-px tile re-reads it a quarter as often (0.645 against 0.780 ms)
+    if (Cout > 64 && ((pixels + 255) / 256) * ceil_div(Cout, 64) < 512) v = (long)Cin * g.ntaps >= 4096 ? 1 : 3;
+    if (g_forced_f16 >= 0) v = g_forced_f16;
+    const Variant16h &var = kVariantsF16[v];
+    DREAM_REQUIRE(CoutPad % var.BN == 0 && CoutPad >= Cout, "CoutPad=%d must be a multiple of %d", CoutPad, var.BN);
+    const bool pool = (flags & DREAM_CONV_POOL2) != 0;
+    DREAM_REQUIRE(!pool || (!(flags & DREAM_CONV_OUT_NCHW) && residual == nullptr && g.H >= 2 && g.W >= 2 && g.out_scale == 1),
+                  "fused max-pool: NHWC output, no residual");
+    fill_params16(p, g, var.BM, var.NP_MAX, flags);
+    DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
+    const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
+    DREAM_REQUIRE(lds <= 160 * 1024, "LDS request %zu too large", lds);
+    if (dream_allow_full_lds((const void *)var.kernel)) return 2;
+    const dim3 grid((unsigned)(ceil_div((int)((size_t)B * p.tiles_x * p.tiles_y), 8) * 8), (unsigned)ceil_div(Cout, var.BN));
+    hipLaunchKernelGGL(var.kernel, grid, dim3(var.threads), lds, (hipStream_t)stream, p);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int dream_conv_f16_set_variant(int v) {
+    DREAM_REQUIRE(v >= -1 && v < kNumF16, "variant out of range");
+    g_forced_f16 = v;
+    return 0;
+}
+
+// k x k (1 | 3) stride-1 conv, same contract as dream_conv2d_f16x3_nhwc_f32 without the `lo` plane.  Cin % 32 == 0.
+extern "C" int dream_conv2d_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                         const float *scale, const float *shift, const float *residual, float *y,
+                                         unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
+                                         int stride, int flags, void *stream) {
+    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
+    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
+    return launch_f16(x, amax_in, w, w_exp, scale, shift, residual, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+}
+
+// ConvTranspose2d(k=4,s=2,p=1) on the fp16 path: the four 2x2-tap sub-pixel phases of dream_conv_transpose4x4s2_f16x3_nhwc_f32.
+extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                                      const float *scale, const float *shift, float *y, unsigned *amax_out,
+                                                      int B, int H, int W, int Cin, int Cout, int CoutPad, int flags,
+                                                      void *stream) {
+    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
+                  "convT4x4_f16: unsupported flags");
+    for (int ph = 0; ph < 4; ++ph) {
+        const Geom16 g = geom16_convT4_phase(H, W, ph);
+        const size_t off = (size_t)ph * 4 * CoutPad * Cin;
+        if (int rc = launch_f16(x, amax_in, (const _Float16 *)w + off, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout,
+                                CoutPad, g, flags, stream))
+            return rc;
+    }
+    return 0;
+}
+
+// ConvTranspose2d(k=3,s=2,p=1,output_padding 1) on the fp16 path: the phases of dream_conv_transpose3x3s2_f16x3_nhwc_f32.
+extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                                      const float *bias, float *y, unsigned *amax_out, int B, int H, int W,
+                                                      int Cin, int Cout, int CoutPad, int flags, void *stream) {
+    DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16: only the ReLU flag is supported");
+    for (int ph = 0; ph < 4; ++ph) {
+        const Geom16 g = geom16_convT3_phase(H, W, ph);
+        if (int rc = launch_f16(x, amax_in, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
+            return rc;
+    }
+    return 0;
+}

@@ -14,38 +14,9 @@
 // reference call sites: dream/models.py:594-615, 695-747); 3 MFMAs replace 8 fp32 MFMAs per 16 k's: 5.3x the MFMA
 // rate of the fp32 kernel, so the measured error must justify it: tests/parity (fp64 reference) show <= 2e-6
 // relative per layer, i.e. the same class as the fp32 kernel's own summation-order noise.
-#include <dream_cdna4.h>
-#include "common.h"
-#include "../../include/dream_hip.h"
-
-struct Conv16Params {
-    const float *x;
-    const _Float16 *w_hi;    // [ntaps][CoutPad][Cin]
-    const _Float16 *w_lo;
-    const int *w_exp;        // device scalar: weights were multiplied by 2^w_exp before the split
-    const unsigned *amax_in; // device scalar: bit pattern of max|x| of the input tensor
-    const float *scale;
-    const float *shift;
-    const float *residual;
-    float *y;
-    unsigned *amax_out;
-    int B, H, W, Hin, Win, Hs, Ws, Ho, Wo;
-    int Cin, Cout, CoutPad;
-    int TH, TW, PH, PW, tiles_x, tiles_y, rcpTW;
-    int in_scale, in_step, lane_stride, pad_y, pad_x;
-    unsigned long long tap_w;   // 16 x 4-bit: weight slice of each tap of this launch
-    int ntaps;
-    unsigned long long tap_dy, tap_dx;
-    int out_scale, out_oy, out_ox;
-    int flags;
-};
+#include "conv_f16_common.h"
 
 namespace {
-
-constexpr int KC = 32;              // k's per stage (two 32x32x16 MFMA k-steps)
-constexpr int S16 = KC + 8;         // LDS row stride in halfs (80 B: odd number of 16-B slots)
-
-DREAM_DEVICE float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 
 template <int MR, int NR, int WM, int WN, int NPM, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16x3_kernel(const Conv16Params p) {
@@ -228,70 +199,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16x3_kernel(const Conv1
         if (last_tap) { tap = 0; ++chunk; } else ++tap;
     }
 
-    // ---- epilogue -----------------------------------------------------------------------------------------
-    const bool relu = (p.flags & DREAM_CONV_RELU) != 0;
-    const bool nchw = (p.flags & DREAM_CONV_OUT_NCHW) != 0;
-    float scale_v[NR], shift_v[NR];
-    int ncol[NR];
-#pragma unroll
-    for (int ns = 0; ns < NR; ++ns) {
-        ncol[ns] = n0 + (wn * NR + ns) * 32 + li;
-        const bool cok = ncol[ns] < p.Cout;
-        scale_v[ns] = inv * ((p.scale != nullptr && cok) ? p.scale[ncol[ns]] : 1.0f);
-        shift_v[ns] = (p.shift != nullptr && cok) ? p.shift[ncol[ns]] : 0.0f;
-    }
-    const int npix = p.TH * TW;
-    float amax = 0.0f;
-#pragma unroll
-    for (int ms = 0; ms < MR; ++ms) {
-        if (!pool) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = (wm * MR + ms) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const int ty = (m * p.rcpTW) >> 16, tx = m - ty * TW;
-                const int oy = (y0 + ty) * p.out_scale + p.out_oy, ox = (x0 + tx) * p.out_scale + p.out_ox;
-                const bool ok = (m < npix) && (y0 + ty < p.H) && (x0 + tx < p.W) && oy < p.Ho && ox < p.Wo;
-#pragma unroll
-                for (int ns = 0; ns < NR; ++ns) {
-                    if (ok && ncol[ns] < p.Cout) {
-                        const size_t o = nchw
-                            ? (((size_t)b * p.Cout + ncol[ns]) * p.Ho + oy) * p.Wo + ox
-                            : (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
-                        float v = acc[ms][ns][r] * scale_v[ns] + shift_v[ns];
-                        if (p.residual != nullptr) v = v + p.residual[o];
-                        if (relu) v = fmaxf(v, 0.0f);
-                        p.y[o] = v;
-                        amax = fmaxf(amax, fabsf(v));
-                    }
-                }
-            }
-        } else {
-            // fused MaxPool2d(2): registers 4g..4g+3 of a lane are one 2x2 window (window-major tile order)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int m0 = (wm * MR + ms) * 32 + 8 * g4 + 4 * lh;
-                const int q = m0 >> 2, hw = TW >> 1;
-                const int wy = (q * p.rcpTW) >> 16, wx = q - wy * hw;
-                const bool ok = (m0 < npix) && (y0 + 2 * wy + 1 < p.H) && (x0 + 2 * wx + 1 < p.W);
-                const int oy = (y0 >> 1) + wy, ox = (x0 >> 1) + wx;
-#pragma unroll
-                for (int ns = 0; ns < NR; ++ns) {
-                    if (ok && ncol[ns] < p.Cout) {
-                        float best = -__builtin_huge_valf();
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float v = acc[ms][ns][4 * g4 + j] * scale_v[ns] + shift_v[ns];
-                            if (relu) v = fmaxf(v, 0.0f);
-                            best = fmaxf(best, v);
-                        }
-                        p.y[(((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns]] = best;
-                        amax = fmaxf(amax, fabsf(best));
-                    }
-                }
-            }
-        }
-    }
-    if (p.amax_out != nullptr) publish_amax(p.amax_out, amax);
+#include "conv_f16_epilogue.inc"
 }
 
 // ---- weight packing: amax -> exponent -> two fp16 planes ----------------------------------------------------
@@ -345,28 +253,6 @@ const Variant16 kVariants16[] = {
 constexpr int kNum16 = 8;
 int g_forced16 = -1;
 
-void choose_tile16(int H, int W, int BM, int np_max, int lane_stride, int kext, bool even, int *th_out, int *tw_out) {
-    long best_tiles = -1;
-    int best_np = 0, bth = even ? 2 : 1, btw = even ? 2 : 1;
-    const int He = even ? (H + 1) / 2 * 2 : H, We = even ? (W + 1) / 2 * 2 : W;
-    // divisor (tw, or tw/2 with the fused pool) < 128 keeps the (m * rcpTW) >> 16 division exact for m < 512
-    for (int tw = even ? 2 : 1; tw <= BM && tw <= (even ? 254 : 127); tw += even ? 2 : 1) {
-        int th = BM / tw;
-        if (even) th &= ~1;
-        if (th < 1) break;
-        if (th > He) th = He;
-        const int twc = tw > We ? We : tw;
-        const int np = ((th - 1) * lane_stride + kext) * ((twc - 1) * lane_stride + kext);
-        if (np > np_max) continue;
-        const long tiles = (long)ceil_div(H, th) * ceil_div(W, twc);
-        if (best_tiles < 0 || tiles < best_tiles || (tiles == best_tiles && np < best_np)) {
-            best_tiles = tiles; best_np = np; bth = th; btw = twc;
-        }
-    }
-    *th_out = bth;
-    *tw_out = btw;
-}
-
 }  // namespace
 
 extern "C" int dream_conv_f16x3_set_variant(int v) {
@@ -406,14 +292,6 @@ extern "C" int dream_pack_conv_weight_f16x3(const float *w_oihw, void *hi, void 
 }
 
 namespace {
-struct Geom16 {
-    int H, W, Hin, Win, Hs, Ws, Ho, Wo;      // position grid, logical / stored input extent, output extent
-    int pad, kext, ntaps;
-    int tap_dy[16], tap_dx[16];
-    int out_scale, out_oy, out_ox;
-    int tap_w[16] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
-};
-
 int launch16(const float *x, const unsigned *amax_in, const void *w_hi, const void *w_lo, const int *w_exp,
              const float *scale, const float *shift, const float *residual, float *y, unsigned *amax_out, int B, int Cin,
              int Cout, int CoutPad, const Geom16 &g, int flags, void *stream) {
@@ -422,7 +300,7 @@ int launch16(const float *x, const unsigned *amax_in, const void *w_hi, const vo
     Conv16Params p;
     p.x = x; p.w_hi = (const _Float16 *)w_hi; p.w_lo = (const _Float16 *)w_lo; p.w_exp = w_exp; p.amax_in = amax_in;
     p.scale = scale; p.shift = shift; p.residual = residual; p.y = y; p.amax_out = amax_out;
-    p.B = B; p.Hin = g.Hin; p.Win = g.Win; p.Hs = g.Hs; p.Ws = g.Ws; p.Ho = g.Ho; p.Wo = g.Wo; p.H = g.H; p.W = g.W;
+    p.B = B;
     p.Cin = Cin; p.Cout = Cout; p.CoutPad = CoutPad;
     const long pixels = (long)B * g.H * g.W;
     // measured (profiles/r01_microbench_f16x3.txt): the 256-px x 64-cout tile beats 128 x 128 on every layer (the
@@ -438,21 +316,7 @@ int launch16(const float *x, const unsigned *amax_in, const void *w_hi, const vo
     const bool pool = (flags & DREAM_CONV_POOL2) != 0;
     DREAM_REQUIRE(!pool || (!(flags & DREAM_CONV_OUT_NCHW) && residual == nullptr && g.H >= 2 && g.W >= 2 && g.out_scale == 1),
                   "fused max-pool: NHWC output, no residual");
-    choose_tile16(g.H, g.W, var.BM, var.NP_MAX, 1, g.kext, pool, &p.TH, &p.TW);
-    p.PH = p.TH - 1 + g.kext; p.PW = p.TW - 1 + g.kext;
-    p.tiles_x = ceil_div(g.W, p.TW); p.tiles_y = ceil_div(g.H, p.TH);
-    p.rcpTW = pool ? (65536 + p.TW / 2 - 1) / (p.TW / 2) : (65536 + p.TW - 1) / p.TW;
-    if (pool) { p.Ho = g.H / 2; p.Wo = g.W / 2; }
-    p.in_scale = 1; p.in_step = 1; p.lane_stride = 1; p.pad_y = g.pad; p.pad_x = g.pad;
-    p.ntaps = g.ntaps;
-    p.tap_dy = 0; p.tap_dx = 0; p.tap_w = 0;
-    for (int t = 0; t < g.ntaps; ++t) {
-        p.tap_dy |= (unsigned long long)g.tap_dy[t] << (4 * t);
-        p.tap_dx |= (unsigned long long)g.tap_dx[t] << (4 * t);
-        p.tap_w |= (unsigned long long)g.tap_w[t] << (4 * t);
-    }
-    p.out_scale = g.out_scale; p.out_oy = g.out_oy; p.out_ox = g.out_ox;
-    p.flags = flags;
+    fill_params16(p, g, var.BM, var.NP_MAX, flags);
     const size_t lds = ((size_t)2 * p.PH * p.PW + (size_t)4 * var.BN) * S16 * sizeof(_Float16);
     DREAM_REQUIRE(lds <= 160 * 1024, "LDS request %zu too large", lds);
     if (dream_allow_full_lds((const void *)var.kernel)) return 2;
@@ -514,12 +378,7 @@ extern "C" int dream_conv_transpose4x4s2_f16x3_nhwc_f32(const float *x, const un
     DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
                   "convT4x4_f16x3: unsupported flags");
     for (int ph = 0; ph < 4; ++ph) {
-        const int a = ph >> 1, b = ph & 1;
-        Geom16 g;
-        g.H = H; g.W = W; g.Hin = H; g.Win = W; g.Hs = H; g.Ws = W; g.Ho = 2 * H; g.Wo = 2 * W;
-        g.pad = 1; g.kext = 3; g.ntaps = 4;
-        for (int t = 0; t < 4; ++t) { g.tap_dy[t] = (t >> 1) + a; g.tap_dx[t] = (t & 1) + b; }
-        g.out_scale = 2; g.out_oy = a; g.out_ox = b;
+        const Geom16 g = geom16_convT4_phase(H, W, ph);
         const size_t off = (size_t)ph * 4 * CoutPad * Cin;
         if (int rc = launch16(x, amax_in, (const _Float16 *)w_hi + off, (const _Float16 *)w_lo + off, w_exp, scale, shift, nullptr,
                               y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
@@ -536,17 +395,7 @@ extern "C" int dream_conv_transpose3x3s2_f16x3_nhwc_f32(const float *x, const un
                                                         int CoutPad, int flags, void *stream) {
     DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16x3: only the ReLU flag is supported");
     for (int ph = 0; ph < 4; ++ph) {
-        const int a = ph >> 1, b = ph & 1;
-        Geom16 g;
-        g.H = H; g.W = W; g.Hin = H; g.Win = W; g.Hs = H; g.Ws = W; g.Ho = 2 * H; g.Wo = 2 * W;
-        g.pad = 0; g.kext = 2; g.ntaps = 0;
-        for (int iy = 0; iy <= a; ++iy)
-            for (int ix = 0; ix <= b; ++ix) {
-                const int ky = a ? 2 - 2 * iy : 1, kx = b ? 2 - 2 * ix : 1, t = g.ntaps++;
-                g.tap_dy[t] = iy; g.tap_dx[t] = ix;
-                g.tap_w[t] = 8 - (3 * ky + kx);
-            }
-        g.out_scale = 2; g.out_oy = a; g.out_ox = b;
+        const Geom16 g = geom16_convT3_phase(H, W, ph);
         if (int rc = launch16(x, amax_in, w_hi, w_lo, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
             return rc;
     }
@@ -562,13 +411,8 @@ extern "C" int dream_conv2d_f16x3_nhwc_f32(const float *x, const unsigned *amax_
                                            int ksize, int stride, int flags, void *stream) {
     DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16x3: kernel size %d not supported", ksize);
     DREAM_REQUIRE(stride == 1, "conv2d_f16x3: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
-    const bool ups = (flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X)) != 0;
     DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
-    Geom16 g;
-    g.H = H; g.W = W; g.Hin = H; g.Win = W; g.Hs = ups ? (H + 1) / 2 : H; g.Ws = ups ? (W + 1) / 2 : W; g.Ho = H; g.Wo = W;
-    g.pad = ksize / 2; g.kext = ksize; g.ntaps = ksize * ksize;
-    for (int t = 0; t < g.ntaps; ++t) { g.tap_dy[t] = t / ksize; g.tap_dx[t] = t % ksize; }
-    g.out_scale = 1; g.out_oy = 0; g.out_ox = 0;
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
     return launch16(x, amax_in, w_hi, w_lo, w_exp, scale, shift, residual, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
 }
 

@@ -82,7 +82,17 @@ class _PackedCache:
             return ops.pack_conv_weight_f16x3(w, direction)
         if form == "ups_f16x3":
             return ops.pack_convT4x4_weight_f16x3(ops.upsample_conv_weight(w))
+        if form == "f16":                         # half precision: the `hi` plane and the exponent only
+            return ops.pack_conv_weight_f16(w, direction)
+        if form == "ups_f16":
+            return ops.pack_convT4x4_weight_f16(ops.upsample_conv_weight(w))
         raise ValueError("unknown packed form %r" % (form,))
+
+
+# Inference precisions that run on the fp16 matrix cores -> suffix of their ops (ops.conv2d_<suffix>, ops.conv_transpose4x4s2_<suffix>,
+# ops.conv_transpose3x3s2_<suffix>, ops.pack_conv_weight_<suffix>, ops.pack_convT4x4_weight_<suffix>) and of their packed forms.  Both
+# take the same arguments and thread the same amax side channel; what differs is the arithmetic (csrc/conv_f16x3.hip, csrc/conv_f16.hip).
+_HALF_OPS = {"fp16x3": "f16x3", "fp16": "f16"}
 
 
 class DreamHourglass(nn.Module):
@@ -178,7 +188,9 @@ class DreamHourglass(nn.Module):
         self._param_slot = {li: 2 * k for k, li in enumerate(owners)}   # plan index -> index of its weight in plan_parameters() (bias: + 1)
         self._packed = _PackedCache()
         # "fp32": exact fp32 MFMA kernel everywhere.  "fp16x3": inference runs the split-precision kernel
-        # (fp32 in/out, 3 fp16 MFMAs per product, fp32-class error); training always uses the fp32 kernels.
+        # (fp32 in/out, 3 fp16 MFMAs per product, fp32-class error).  "fp16": inference runs the half-precision kernel (fp32 in/out,
+        # operands rounded to fp16, one MFMA per product, fp32 accumulation: belief maps move by about 1e-3 .. 3e-3).
+        # Training always uses the fp32 kernels.
         self.precision = "fp32"
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
@@ -219,8 +231,8 @@ class DreamHourglass(nn.Module):
         return (w, h)
 
     def input_channel_pad(self):
-        """Channel count of the NHWC tensor a "wide" first conv reads (fp32 kernel: multiples of 16; split kernel: 32)."""
-        return ops.round_up(self.n_image_input_channels, 32 if self.precision == "fp16x3" else 16)
+        """Channel count of the NHWC tensor a "wide" first conv reads (fp32 kernel: multiples of 16; split / half kernel: 32)."""
+        return ops.round_up(self.n_image_input_channels, 32 if self.precision in _HALF_OPS else 16)
 
     def _check_input(self, x, x_is_nhwc):
         ok = x.dim() == 4 and (int(x.shape[3]) == self.input_channel_pad() if x_is_nhwc
@@ -369,19 +381,28 @@ class DreamHourglass(nn.Module):
             return ops.conv_transpose3x3s2(x, packed, bias, rows, relu=bool(flags & CONV_RELU), skip=skip), None
         return self._conv3x3(mod, 0, x, bias, skip=skip, flags=flags), None
 
-    def _conv_f16x3(self, kind, mod, x, amax, w, bias, flags, skip=None):
-        """One conv entry of the plan on the split-precision kernels -> (y, amax of y).  Each kernel publishes max|y| of its output (amax
-        side channel) so the next conv can scale its input into fp16 range; skip connections are not folded here."""
+    def _conv_half(self, sfx, kind, mod, x, amax, w, bias, flags):
+        """One conv entry of the plan on the kernels of _HALF_OPS suffix ``sfx`` -> (y, amax of y).  Each kernel publishes max|y| of its
+        output (amax side channel) so the next conv can scale its input into fp16 range; skip connections are not folded here.  The
+        3-channel first conv stays on its fp32 VALU kernel."""
         if kind == "first":
             return ops.conv3x3_first_amax(x, w, bias, relu=bool(flags & CONV_RELU))
         if flags & CONV_UPSAMPLE2X:
-            pk4 = self._packed.get(mod.weight, "ups_f16x3")
-            return ops.conv_transpose4x4s2_f16x3(x, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
+            pk4 = self._packed.get(mod.weight, "ups_" + sfx)
+            return getattr(ops, "conv_transpose4x4s2_" + sfx)(x, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
         if kind == "deconv":
-            p16 = self._packed.get(mod.weight, "f16x3", 1)
-            return ops.conv_transpose3x3s2_f16x3(x, amax, p16, p16[3], bias, relu=bool(flags & CONV_RELU))
-        p16 = self._packed.get(mod.weight, "f16x3", 0)
-        return ops.conv2d_f16x3(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
+            p16 = self._packed.get(mod.weight, sfx, 1)
+            return getattr(ops, "conv_transpose3x3s2_" + sfx)(x, amax, p16, p16[3], bias, relu=bool(flags & CONV_RELU))
+        p16 = self._packed.get(mod.weight, sfx, 0)
+        return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
+
+    def _conv_f16x3(self, kind, mod, x, amax, w, bias, flags, skip=None):
+        """... on the split-precision kernels (three MFMAs per product, fp32-class error)."""
+        return self._conv_half("f16x3", kind, mod, x, amax, w, bias, flags)
+
+    def _conv_f16(self, kind, mod, x, amax, w, bias, flags, skip=None):
+        """... on the half-precision kernel (operands rounded to fp16, one MFMA per product)."""
+        return self._conv_half("f16", kind, mod, x, amax, w, bias, flags)
 
     def _first_pair_in_subbatches(self, layers, li, x, params, sub):
         """conv1_1 -> conv1_2 (+ pool) over sub-batches of ``sub`` frames, so that the 64-channel full-resolution tensor between them
@@ -404,13 +425,13 @@ class DreamHourglass(nn.Module):
         zero-padded NHWC input of a "wide" first conv (``x_amax``: its max|x|, for the split-precision kernels).
 
         One walk: at each conv the group of entries it heads is resolved (_group) and run, then the walk moves past them.  Inference
-        with precision "fp16x3" is the same walk on the split-precision launches (_conv_f16x3), with the amax side channel threaded
-        through; it folds no skip-adds and runs no sub-batches."""
+        with precision "fp16x3" / "fp16" is the same walk on the split- / half-precision launches (_conv_f16x3 / _conv_f16), with the amax
+        side channel threaded through; it folds no skip-adds and runs no sub-batches."""
         self._check_input(x, x_is_nhwc)
-        if self.precision not in ("fp32", "fp16x3"):
+        if self.precision != "fp32" and self.precision not in _HALF_OPS:
             raise ValueError("unknown precision %r" % (self.precision,))
-        split = self.precision == "fp16x3" and not save
-        conv = self._conv_f16x3 if split else self._conv_fp32
+        split = self.precision in _HALF_OPS and not save
+        conv = {"fp16x3": self._conv_f16x3, "fp16": self._conv_f16}[self.precision] if split else self._conv_fp32
         layers = self.plan_layers()
         saved, keep = [], {}
         act, amax, li = x, x_amax, 0
@@ -1022,7 +1043,7 @@ class DreamHourglassMultiStage(nn.Module):
                     # what torch.cat raises in the reference when the pools do not divide the input resolution
                     raise RuntimeError("Sizes of tensors must match except in dimension 1. Expected size %d but got size %d"
                                        % (int(x.shape[2]), int(prev.shape[2]) * up))
-                want_amax = st.precision == "fp16x3" and not save
+                want_amax = st.precision in _HALF_OPS and not save
                 inp, amax = ops.stage_input(x, prev, up, st.input_channel_pad(), want_amax=want_amax)
                 y, sv = st.run_forward(inp, params, save, x_is_nhwc=True, x_amax=amax)
             outs.append(y)
@@ -1153,7 +1174,7 @@ class ResnetSimple(nn.Module):
 
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""
-        self.precision = "fp32"        # "fp16x3": evaluation-mode forward on the split-precision conv kernel
+        self.precision = "fp32"        # "fp16x3" / "fp16": evaluation-mode forward on the split- / half-precision conv kernel
         self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
         # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
         self.conv1x1_algorithm = os.environ.get("DREAM_CONV1X1_ALGORITHM", "gemm")
@@ -1419,50 +1440,53 @@ class ResnetSimple(nn.Module):
         packed, rows = self._cached(("w", name), [m.weight], lambda: ops.pack_convT4x4_weight(m.weight.detach()))
         return ops.conv_transpose4x4s2(y, packed, rows, scale, shift, flags)
 
-    # ---- inference on the split-precision conv kernel (strided convs stay on the fp32 kernel) ------------------
-    def _conv_bn16(self, name, x, amax, conv, bn, relu, residual=None):
-        """-> (y, amax_y).  Stride-1 1x1 / 3x3 convs run on conv_f16x3; the six stride-2 convs of the trunk run on
-        the fp32 kernel, which publishes max|y| all the same."""
+    # ---- inference on the split- / half-precision conv kernels (strided convs stay on the fp32 kernel) ------------------
+    def _conv_bn16(self, sfx, name, x, amax, conv, bn, relu, residual=None):
+        """-> (y, amax_y).  Stride-1 1x1 / 3x3 convs run on the kernel of _HALF_OPS suffix ``sfx``; the six stride-2 convs of the trunk
+        run on the fp32 kernel, which publishes max|y| all the same."""
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         scale, shift = self._fold(name, bn, conv.bias)
         flags = CONV_RELU if relu else 0
         if stride != 1:
             packed, rows, _ = self._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
             return ops.conv2d_amax(x, packed, rows, k, stride, scale, shift, residual, flags)
-        p16 = self._cached(("w16", name), [conv.weight], lambda: ops.pack_conv_weight_f16x3(conv.weight.detach(), 0))
-        return ops.conv2d_f16x3(x, amax, p16, p16[3], k, scale, shift, residual, flags)
+        p16 = self._cached(("w" + sfx, name), [conv.weight], lambda: getattr(ops, "pack_conv_weight_" + sfx)(conv.weight.detach(), 0))
+        return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], k, scale, shift, residual, flags)
 
-    def run_forward_f16x3(self, x):
+    def run_forward_half(self, x, sfx):
+        """The evaluation forward on the ops of _HALF_OPS suffix ``sfx`` ("f16x3" | "f16"): one walk for both."""
+        pack, packT = getattr(ops, "pack_conv_weight_" + sfx), getattr(ops, "pack_convT4x4_weight_" + sfx)
+        conv2d, convT = getattr(ops, "conv2d_" + sfx), getattr(ops, "conv_transpose4x4s2_" + sfx)
         col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
         amax = ops.absmax(x)                               # im2col only rearranges (and zero-pads) the image
-        w1 = self._cached(("w16", "conv1"), [self.conv1.weight],
-                          lambda: ops.pack_conv_weight_f16x3(self.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        w1 = self._cached(("w" + sfx, "conv1"), [self.conv1.weight],
+                          lambda: pack(self.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
         s1, t1 = self._fold("bn1", self.bn1)
-        y, amax = ops.conv2d_f16x3(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
+        y, amax = conv2d(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
         del col
         y = ops.maxpool3s2(y)                              # pooling cannot raise the maximum: amax carries over
         for name, blk in self._trunk():
             idt = y
             if hasattr(blk, "downsample"):
-                idt, _ = self._conv_bn16(name + ".ds", y, amax, blk.downsample[0], blk.downsample[1], relu=False)
-            o, a1 = self._conv_bn16(name + ".1", y, amax, blk.conv1, blk.bn1, relu=True)
-            o, a2 = self._conv_bn16(name + ".2", o, a1, blk.conv2, blk.bn2, relu=True)
-            y, amax = self._conv_bn16(name + ".3", o, a2, blk.conv3, blk.bn3, relu=True, residual=idt)
+                idt, _ = self._conv_bn16(sfx, name + ".ds", y, amax, blk.downsample[0], blk.downsample[1], relu=False)
+            o, a1 = self._conv_bn16(sfx, name + ".1", y, amax, blk.conv1, blk.bn1, relu=True)
+            o, a2 = self._conv_bn16(sfx, name + ".2", o, a1, blk.conv2, blk.bn2, relu=True)
+            y, amax = self._conv_bn16(sfx, name + ".3", o, a2, blk.conv3, blk.bn3, relu=True, residual=idt)
         for name, m, bn in self._decoder():
             if bn is not None:
-                p16 = self._cached(("w16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16x3(m.weight.detach()))
+                p16 = self._cached(("w" + sfx, name), [m.weight], lambda: packT(m.weight.detach()))
                 scale, shift = self._fold(name, bn, m.bias)
-                y, amax = ops.conv_transpose4x4s2_f16x3(y, amax, p16, p16[3], scale, shift, CONV_RELU)
+                y, amax = convT(y, amax, p16, p16[3], scale, shift, CONV_RELU)
             else:
-                p16 = self._cached(("w16", name), [m.weight], lambda: ops.pack_conv_weight_f16x3(m.weight.detach(), 0))
-                y, _ = ops.conv2d_f16x3(y, amax, p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)
+                p16 = self._cached(("w" + sfx, name), [m.weight], lambda: pack(m.weight.detach(), 0))
+                y, _ = conv2d(y, amax, p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)
         return y
 
     def run_forward(self, x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
-        if self.precision == "fp16x3":
-            return self.run_forward_f16x3(x)
+        if self.precision in _HALF_OPS:
+            return self.run_forward_half(x, _HALF_OPS[self.precision])
         # stem: 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused; then MaxPool(3,2,1)
         col = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0e"])           # (= STEM_COLS["w"])
         s1, t1 = self._fold("bn1", self.bn1)

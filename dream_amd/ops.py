@@ -1436,6 +1436,62 @@ def conv_transpose4x4s2_f16x3(x_nhwc, amax_in, packed16, cout, scale=None, shift
     return y, amax_out
 
 
+# ---- half-precision (fp16) inference path: the split path's `hi` plane and scales, one MFMA per product -------------
+def pack_conv_weight_f16(w_oihw, mode=0):
+    """-> (hi, None, exp, rows): the fp16 plane of w*2^exp that pack_conv_weight_f16x3 writes, without its `lo` plane."""
+    hi, _, exp, rows = pack_conv_weight_f16x3(w_oihw, mode)
+    return hi, None, exp, rows
+
+
+def pack_convT4x4_weight_f16(wT):
+    hi, _, exp, cout = pack_convT4x4_weight_f16x3(wT)
+    return hi, None, exp, cout
+
+
+def conv2d_f16(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, residual=None, flags=0, want_amax=True):
+    """Half-precision conv (stride 1, fp16 operands, fp32 accumulation): returns (y, amax_out)."""
+    hi, _, exp, _ = packed16
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv2d_f16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
+        h, w = 2 * h, 2 * w
+    shape = (b, cout, h, w) if flags & CONV_OUT_NCHW else (b, h, w, cout)
+    if flags & CONV_POOL2:
+        shape = (b, h // 2, w // 2, cout)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    amax_out = new_amax(x.device) if want_amax else None
+    call("dream_conv2d_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(residual), ptr(y),
+         ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y, amax_out
+
+
+def conv_transpose3x3s2_f16(x_nhwc, amax_in, packed16_mode1, cout, bias=None, relu=True):
+    """Half-precision ConvTranspose2d(k3,s2,p1,output_padding 1) (+ReLU) by sub-pixel phases -> (y, amax_out)."""
+    hi, _, exp, _ = packed16_mode1
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv_transpose3x3s2_f16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+    amax_out = new_amax(x.device)
+    call("dream_conv_transpose3x3s2_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(bias), ptr(y), ptr(amax_out),
+         b, h, w, cin, cout, int(hi.shape[-2]), CONV_RELU if relu else 0, stream())
+    return y, amax_out
+
+
+def conv_transpose4x4s2_f16(x_nhwc, amax_in, packed16, cout, scale=None, shift=None, flags=0, direct_taps=16):
+    hi, _, exp, _ = packed16
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+    amax_out = new_amax(x.device)
+    call("dream_conv_transpose4x4s2_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y),
+         ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), flags, stream())
+    return y, amax_out
+
+
 def conv2d_amax(x_nhwc, packed, cout, ksize, stride=1, scale=None, shift=None, residual=None, flags=0):
     """fp32 MFMA conv that also publishes max|y| (feeds the split-precision kernel's input scaling)."""
     x = _f32(x_nhwc)

@@ -281,6 +281,29 @@ int dream_conv_transpose3x3s2_f16x3_nhwc_f32(const float *x, const unsigned *ama
                                              const int *w_exp, const float *bias, float *y, unsigned *amax_out, int B,
                                              int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream);
 int dream_conv_f16x3_set_variant(int variant);
+/* ---- half-precision ("fp16") inference path: fp32 in/out, fp16 operands, fp32 accumulation ---------------------------
+ * y = epilogue(2^-(ea+ew) * sum fp16(x*2^ea) * fp16(w*2^ew)): ONE v_mfma_f32_32x32x16_f16 per product, with the split
+ * path's power-of-two scales and amax side channel.  `w` is the `hi` plane written by dream_pack_conv_weight_f16x3 /
+ * dream_pack_convT4x4_weight_f16x3 and `w_exp` their exp_out; every other argument is that of the _f16x3 sibling.
+ * The operands carry 11 significant bits: an inference mode that trades last-digit accuracy for rate, not for training. */
+/* nn.Conv2d(k 1 | 3, stride 1) (+ folded BatchNorm / bias, residual, ReLU, MaxPool2d(2), fused nn.Upsample(2)):
+ * dream/models.py:594-615 (VGG encoder), 695-747 (upsample decoder and heads), 22-32,138-148 (stride-1 ResNet bottleneck convs, head). */
+int dream_conv2d_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                              const float *scale, const float *shift, const float *residual, float *y,
+                              unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
+                              int stride, int flags, void *stream);
+/* nn.ConvTranspose2d(k4,s2,p1) (+ folded BatchNorm, ReLU) of the ResNet decoder (dream/models.py:37-136), and the
+ * nn.Upsample(2) + nn.Conv2d(k3) pairs of the hourglass decoder (dream/models.py:691-733) in their transposed form
+ * (dream_upsample_conv3x3_weight_as_convT4x4). */
+int dream_conv_transpose4x4s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                           const float *scale, const float *shift, float *y, unsigned *amax_out,
+                                           int B, int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream);
+/* nn.ConvTranspose2d(k3,s2,p1,output_padding 1) (+ReLU) of the deconvolution decoder (dream/models.py:618-686);
+ * plane from dream_pack_conv_weight_f16x3(mode 1). */
+int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                           const float *bias, float *y, unsigned *amax_out, int B, int H, int W,
+                                           int Cin, int Cout, int CoutPad, int flags, void *stream);
+int dream_conv_f16_set_variant(int variant);   /* -1 = the measured rule; otherwise index into the fp16 variant table */
 /* variant selection for benchmarking: -1 = heuristic; otherwise index into the variant table */
 int dream_conv3x3_set_variant(int variant);
 int dream_conv3x3_num_variants(void);
