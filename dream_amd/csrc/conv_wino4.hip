@@ -55,35 +55,14 @@
 #ifndef DREAM_W4_DIAG
 #define DREAM_W4_DIAG 0
 #endif
-// (the non-temporal hint on the output stores, buffer_store_f32_nt, measured 0-3 % SLOWER in round-robin A/B: tools/wino4_diag.py)
-#ifndef DREAM_W4_STORE
-#define DREAM_W4_STORE buffer_store_f32
-#endif
-#ifndef DREAM_W4_MIDBARRIER
-#define DREAM_W4_MIDBARRIER 0
-#endif
-#ifndef DREAM_W4_STAGGER_N
-#define DREAM_W4_STAGGER_N 0
-#define DREAM_W4_STAGGER_PCT 0
-#endif
-// patch loads of wavefronts 4-7 (wide shape, plain 3x3 conv) this many slots later than those of wavefronts 0-3 (0: same slots)
-// cache policy of the wide shape's weight stream / of the patch loads (aux bits: 1 sc0, 2 nt, 16 sc1): A/B builds (tools/wino4_diag.py 60xx)
-#ifndef DREAM_W4_WAUX
-#define DREAM_W4_WAUX 0
-#endif
-#ifndef DREAM_W4_XAUX
-#define DREAM_W4_XAUX 0
-#endif
-#ifndef DREAM_W4_STAG_LX
-#define DREAM_W4_STAG_LX 0
-#endif
-#ifndef DREAM_W4_RUNNING_WOFF
-#define DREAM_W4_RUNNING_WOFF 1
-#endif
-// static priority for the second-dispatched half of the workgroup's wavefronts (MI355X_MICROARCH.md "two waves per SIMD", item 4)
-#ifndef DREAM_W4_SETPRIO
-#define DREAM_W4_SETPRIO 0
-#endif
+// Retired experiments: each lost its A/B, its build fork is gone, the finding stays in DESIGN.md 4.2c (summary: 9, item 3).
+//   non-temporal hint on the output stores: 0-3 % slower in round-robin A/B (profiles/r03_wino4_diag.txt)
+//   workgroup barrier between pass 1 and pass 2: unnecessary (see slot S1 + 2 of `chunk`); without it +-0 wide, +1.8 % narrow
+//   weight offset as (36 c + k) * stride: 18 v_readlane_b32 per chunk; the running offset is +1.0 % (profiles/r05_wino4_ab_scalar_setprio_woff.txt)
+//   s_setprio 1 on the second-dispatched half of the workgroup's wavefronts: +-0 (profiles/r05_wino4_ab_scalar_setprio_woff.txt)
+//   patch loads of wavefronts 4-7 some slots behind those of 0-3 (the block loop instantiated twice): no gain at any offset (profiles/r05_wino4_ab_staggered_patch_loads.txt)
+//   sc0 / nt / sc1 cache policy on the weight stream / the patch loads: nt 10-60 % slower, the others +-0 under the bench (profiles/r05_wino4_ab_cache_policy.txt)
+//   start-up stagger compiled in as the default: no layer gains at any spread, the run-time hook stays (profiles/r05_ab_wino4_stagger.txt)
 
 namespace {
 
@@ -130,6 +109,12 @@ constexpr int W4P = 36;       // positions
 #endif
 #ifndef DREAM_W4_PAT_S1OFF
 #define DREAM_W4_PAT_S1OFF 8
+#endif
+// the full kernel's schedule inside a chunk (`chunk` below): pass 1 from slot S1, the staging reads in slot S2, the patch loads in the first LX slots
+#ifndef DREAM_W4_S1
+#define DREAM_W4_S1 10
+#define DREAM_W4_S2 13
+#define DREAM_W4_LX 3
 #endif
 
 
@@ -307,7 +292,6 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
 
     f32x4 acc[W4P];
     const int nchunks = p.Cin / W4K;
-    if (DREAM_W4_SETPRIO && wave >= W4NW / 2) __builtin_amdgcn_s_setprio(1);
 
     // weight stream: the k-th position of the chunk sequence (k counted from the start of the block, 36 per chunk) lives in
     // bq[k % 8]; the chunk loop is unrolled by two so that the ring index is a compile-time constant (72 % 8 == 0)
@@ -317,7 +301,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
     auto load_u = [&](unsigned soff) {
         if constexpr (C::PAIRS) return buffer_load_x4(ubuf, b_lane, soff);
         else if constexpr (NARROW) return buffer_load_x2(ubuf, b_lane, soff);
-        else return buffer_load_x4_aux<DREAM_W4_WAUX>(ubuf, b_lane, soff);
+        else return buffer_load_x4(ubuf, b_lane, soff);
     };
 #pragma unroll
     for (int k = 0; k < W4_AHEAD; k += BSTEP) bq[k / BSTEP] = load_u((unsigned)pat4_pos(PAT, k) * u_pos_stride);
@@ -384,26 +368,15 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
     // the block (chunks run in pairs: the ring index of the weight stream is a compile-time constant, 72 % 8 == 0).  `last`
     // (wave-uniform; only the odd chunk can be the last one): the next chunk is chunk 0 of the NEXT block -- its plan is
     // computed here, the weight stream wraps around.  One instantiation per parity, one call site each: the loop below.
-    auto chunk = [&](auto ph_tag, auto stag_tag, bool last, int c, int tile0n, int b0n) __attribute__((always_inline)) {
+    auto chunk = [&](auto ph_tag, bool last, int c, int tile0n, int b0n) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value;
-        constexpr int STAG = decltype(stag_tag)::value;
-#ifndef DREAM_W4_S1
-#define DREAM_W4_S1 10
-#define DREAM_W4_S2 13
-#define DREAM_W4_LX 3
-#endif
         // NSLOT slots of two active positions (18; 13 with a phase pattern, the last one a single position).  The full kernel's
         // schedule is S1 10 / S2 13 / loads in slots 0..2; a pattern keeps the distances from the END of the chunk (S1 5, S2 8) and
         // issues its six patch loads in slot 0, so that they have four slots to arrive.
         constexpr int NSLOT = (NPOS + 1) / 2;
         constexpr int S1 = PAT ? NSLOT - DREAM_W4_PAT_S1OFF : DREAM_W4_S1, S2 = PAT ? S1 + 3 : DREAM_W4_S2; // pass 1 in slots S1 .. S1 + 2; staging reads in slot S2, pass 2 in S2 + 1 .. S2 + 3
-        constexpr int LX = PAT ? 1 : DREAM_W4_LX;         // patch loads in slots LX0 .. LX0 + LX - 1 (6 / LX per slot)
-        // STAG (wavefronts 4-7 of the wide shape: the SECOND wavefront of every SIMD): the patch loads come DREAM_W4_STAG_LX slots later.  A
-        // patch load misses to HBM, loads return in order, so the weight operands issued behind it stall the wavefront three slots
-        // later -- both wavefronts of a SIMD at the same slots, matrix pipe idle.  Shifted, one wavefront's MFMAs cover the other's stall.
-        // (The whole block loop is instantiated twice, chosen once per wavefront: no branch and no control-flow join inside it.)
-        constexpr int LX0 = STAG ? DREAM_W4_STAG_LX : 0;
-        static_assert(LX0 + LX <= S1, "the patch loads must be issued before pass 1");
+        constexpr int LX = PAT ? 1 : DREAM_W4_LX;         // patch loads in slots 0 .. LX - 1 (6 / LX per slot)
+        static_assert(LX <= S1, "the patch loads must be issued before pass 1");
         const unsigned coff = last ? 0u : (unsigned)((c + 1) * W4K * 4);
         const int cnext = last ? 0 : (c + 1) * W4P;                          // first position of the next chunk in the weight stream
         if (PH == 1 && last) xbuf = block_xbuf(b0n);                        // this block's loads are all issued: from here on the next block's
@@ -418,7 +391,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
                 if ((DREAM_W4_DIAG & 2) || (half && !two)) return;
                 if (C::PAIRS && half) return;                                 // the slot's two positions came with one load
                 const int kn = k0 + half + W4_AHEAD;
-                if constexpr (PAT == 0 && DREAM_W4_RUNNING_WOFF && !(DREAM_W4_DIAG & 32)) {
+                if constexpr (PAT == 0 && !(DREAM_W4_DIAG & 32)) {
                     if (kn == NPOS && last) woff = 0u;                        // wave-uniform: s_cselect
                     bq[(PH * NPOS + kn) % W4_RING / BSTEP] = load_u(woff);
                     woff += BSTEP * u_pos_stride;
@@ -428,7 +401,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
                     bq[(PH * NPOS + kn) % W4_RING / BSTEP] = load_u((DREAM_W4_DIAG & 32) ? 0u : (unsigned)spos * u_pos_stride);
                 }
             };
-            auto load_x = [&](int col) { if (!(DREAM_W4_DIAG & 1)) d[col] = buffer_load_x4_aux<DREAM_W4_XAUX>(xbuf, item_offset(col), (DREAM_W4_DIAG & 64) ? 0u : coff); };
+            auto load_x = [&](int col) { if (!(DREAM_W4_DIAG & 1)) d[col] = buffer_load_x4(xbuf, item_offset(col), (DREAM_W4_DIAG & 64) ? 0u : coff); };
             auto pair = [&](int r) {
                 const int i0 = (PH * NPOS + k0) % W4_RING, i1 = (PH * NPOS + k0 + 1) % W4_RING;
                 if constexpr (C::PAIRS) {                                    // i0 even, i1 = i0 + 1: the two halves of quad i0 / 2
@@ -446,13 +419,13 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
                     load_b(0);
                     if (s + 1 < NSLOT) read_a((s + 1) & 1, k0 + 2, PH);
                     if (PH == 1 && s == 0 && last) plan_item(tile0n, b0n);
-                    if (s >= LX0 && s < LX0 + LX) { for (int c2 = 0; c2 < 3 / LX; ++c2) load_x((6 / LX) * (s - LX0) + c2); }
+                    if (s < LX) { for (int c2 = 0; c2 < 3 / LX; ++c2) load_x((6 / LX) * s + c2); }
                     if (!(DREAM_W4_DIAG & 8) && s >= S1 && s < S1 + 3) pass1_piece(2 * (s - S1));
                     if (!(DREAM_W4_DIAG & 8) && s == S2) { pass2_read(0); pass2_read(1); }
                     if (!(DREAM_W4_DIAG & 8) && s > S2 && s <= S2 + 3) pass2_piece(2 * (s - S2 - 1), 1 - PH);
                 } else if (k == 1) {
                     load_b(1);
-                    if (s >= LX0 && s < LX0 + LX) { for (int c2 = 3 / LX; c2 < 6 / LX; ++c2) load_x((6 / LX) * (s - LX0) + c2); }
+                    if (s < LX) { for (int c2 = 3 / LX; c2 < 6 / LX; ++c2) load_x((6 / LX) * s + c2); }
                     if (!(DREAM_W4_DIAG & 8) && s == S2) { pass2_read(2); pass2_read(3); }
                 } else if (k == 2) {
                     if (!(DREAM_W4_DIAG & 8) && s >= S1 && s < S1 + 3) pass1_piece(2 * (s - S1) + 1);
@@ -479,8 +452,7 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
                 // No workgroup barrier is needed here: the (tile, quad, row) items of pass 1 and the (tile, quad, column) items
                 // of pass 2 of one wavefront cover the SAME tiles (wide: tiles 2w, 2w + 1; narrow: 4w .. 4w + 3), so a
                 // wavefront's pass 2 reads only what that wavefront's pass 1 wrote, and a wavefront's LDS instructions execute
-                // in order.  (DREAM_W4_MIDBARRIER=1 restores the barrier of round 3 for A/B runs.)
-                if (DREAM_W4_MIDBARRIER) __syncthreads();
+                // in order.
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -491,6 +463,8 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
 
     // ---- inverse transform Y = A^T M A (lane-local), scale / shift / residual / ReLU / 2x2 max-pool, store ------------------------
     constexpr bool pool = MODE == 1 || MODE == 4, both = MODE == 4, has_res = MODE == 2 || MODE == 3, mask = MODE == 3;
+    // (load-bearing form: a generic lambda that receives the tag of its one call site.  Checked with tools/isa_same.py: as a non-generic
+    // lambda the register allocation of 10 of this file's 18 kernels changes.)
     auto epilogue = [&](auto site_tag, int tile0e, int b0e) {
         // Everything the epilogue needs is read again from the kernel-argument segment (scalar loads, once per block): kept in
         // SGPRs across the MFMA phases these values push the kernel past its scalar register file (spills through VGPR lanes).
@@ -654,20 +628,20 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) {
                                     const bool inb = ((limf[rp][h] >> i) & (limf[rp][h] >> (4 + jj)) & 1) != 0;
-                                    DREAM_W4_STORE(fbuf, v[i], inb ? basef[rp][h] + (unsigned)i * frow_b + (unsigned)jj * fpx_b : BUFFER_OOB, 0u);
+                                    buffer_store_f32(fbuf, v[i], inb ? basef[rp][h] + (unsigned)i * frow_b + (unsigned)jj * fpx_b : BUFFER_OOB, 0u);
                                 }
                             }
                             if ((jj & 1) == 0) {
                                 keep[h][0] = fmaxf(v[0], v[1]);
                                 keep[h][1] = fmaxf(v[2], v[3]);
                             } else {
-                                DREAM_W4_STORE(ybuf, fmaxf(keep[h][0], fmaxf(v[0], v[1])), voff(h, 0, jj >> 1), soff(0, jj >> 1));
-                                DREAM_W4_STORE(ybuf, fmaxf(keep[h][1], fmaxf(v[2], v[3])), voff(h, 1, jj >> 1), soff(1, jj >> 1));
+                                buffer_store_f32(ybuf, fmaxf(keep[h][0], fmaxf(v[0], v[1])), voff(h, 0, jj >> 1), soff(0, jj >> 1));
+                                buffer_store_f32(ybuf, fmaxf(keep[h][1], fmaxf(v[2], v[3])), voff(h, 1, jj >> 1), soff(1, jj >> 1));
                             }
                         } else {
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
-                                DREAM_W4_STORE(ybuf, finish(o4[i][h], has_res ? rcur[h][i] : 0.0f), voff(h, i, jj), soff(i, jj));
+                                buffer_store_f32(ybuf, finish(o4[i][h], has_res ? rcur[h][i] : 0.0f), voff(h, i, jj), soff(i, jj));
                         }
                     }
                     if (has_res && jj + 1 < 4) {
@@ -690,7 +664,9 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
     };
 
     // ---- the blocks of this workgroup (chunks in pairs: nchunks is even, host side) ----------------------------------------------
-    auto run_blocks = [&](auto stag_tag) __attribute__((always_inline)) {
+    // (load-bearing form: an always_inline lambda called once.  Checked with tools/isa_same.py: written as a plain loop in the kernel's body,
+    // 17 of the 18 kernels get another register allocation.)
+    auto run_blocks = [&]() __attribute__((always_inline)) {
         while (true) {
             const int tile0n = block_tile0(tb + J);
             const int b0n = div_magic40(tile0n, p.magic_tpi);
@@ -699,22 +675,17 @@ __global__ void __launch_bounds__(64 * W4Cfg<NARROW>::NW, 2) conv_wino4_kernel(c
             for (int pp = 0; pp < W4P; ++pp)
                 if (pat4_active(PAT, pp)) acc[pp] = zero;
             for (int c = 0; c < nchunks; c += 2) {
-                chunk(ph0, stag_tag, false, c, tile0n, b0n);
-                chunk(ph1, stag_tag, c + 2 == nchunks, c + 1, tile0n, b0n);
+                chunk(ph0, false, c, tile0n, b0n);
+                chunk(ph1, c + 2 == nchunks, c + 1, tile0n, b0n);
             }
-            epilogue(stag_tag, tile0, b0);
+            epilogue(std::integral_constant<int, 0>{}, tile0, b0);
             tb += J;
             if (tb >= blk_end) break;
             tile0 = tile0n;
             b0 = b0n;
         }
     };
-    if constexpr (!NARROW && PAT == 0 && DREAM_W4_STAG_LX > 0) {
-        if (wave >= W4NW / 2) run_blocks(std::integral_constant<int, 1>{});
-        else run_blocks(std::integral_constant<int, 0>{});
-    } else {
-        run_blocks(std::integral_constant<int, 0>{});
-    }
+    run_blocks();
 }
 
 // OIHW (mode 0) or, for the data-gradient operator, IOHW with flipped taps (mode 1) -> U = G g G^T in fp64, rounded once to fp32,
@@ -855,8 +826,8 @@ int wino4_setup(Wino4Params &p, const float *x, const float *u_packed, const flo
     p.ymap = 0;
     if (g_stagger_n4 < 0) {
         const char *e = getenv("DREAM_W4_STAGGER");
-        int n = DREAM_W4_STAGGER_N, pct = DREAM_W4_STAGGER_PCT;
-        if (e != nullptr && sscanf(e, "%d,%d", &n, &pct) != 2) { n = DREAM_W4_STAGGER_N; pct = DREAM_W4_STAGGER_PCT; }
+        int n = 0, pct = 0;
+        if (e != nullptr && sscanf(e, "%d,%d", &n, &pct) != 2) { n = 0; pct = 0; }
         g_stagger_n4 = n > 1 ? n : 0;
         g_stagger_pct4 = pct;
     }

@@ -110,15 +110,6 @@ DREAM_DEVICE f32x4 buffer_load_x4(BufferRsrc b, unsigned voffset_bytes, unsigned
     const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(b.r, voffset_bytes, soffset_bytes, 0);
     return __builtin_bit_cast(f32x4, v);
 }
-
-// the same with a compile-time cache policy (aux bits on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1) -- A/B builds only
-template <int AUX>
-DREAM_DEVICE f32x4 buffer_load_x4_aux(BufferRsrc b, unsigned voffset_bytes, unsigned soffset_bytes) {
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-    const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(b.r, voffset_bytes, soffset_bytes, AUX);
-    return __builtin_bit_cast(f32x4, v);
-}
-
 DREAM_DEVICE f32x2 buffer_load_x2(BufferRsrc b, unsigned voffset_bytes, unsigned soffset_bytes) {
     typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
     const u32x2_ v = __builtin_amdgcn_raw_buffer_load_b64(b.r, voffset_bytes, soffset_bytes, 0);
@@ -130,10 +121,6 @@ DREAM_DEVICE float buffer_load_f32(BufferRsrc b, unsigned voffset_bytes, unsigne
 // an out-of-range lane (voffset = BUFFER_OOB) stores nothing: masked stores without branches
 DREAM_DEVICE void buffer_store_f32(BufferRsrc b, float v, unsigned voffset_bytes, unsigned soffset_bytes) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), b.r, voffset_bytes, soffset_bytes, 0);
-}
-// the same with the non-temporal hint (aux bit 1 = nt on gfx94x/gfx950): a write-once stream that should not displace L2 residents
-DREAM_DEVICE void buffer_store_f32_nt(BufferRsrc b, float v, unsigned voffset_bytes, unsigned soffset_bytes) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), b.r, voffset_bytes, soffset_bytes, 2);
 }
 DREAM_DEVICE void buffer_store_x4(BufferRsrc b, f32x4 v, unsigned voffset_bytes, unsigned soffset_bytes) {
     typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));

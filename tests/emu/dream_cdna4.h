@@ -81,9 +81,6 @@ constexpr unsigned BUFFER_OOB = 0x80000000u;
 inline BufferRsrc make_buffer(const void *base, size_t bytes) {
     return {(const char *)base, bytes > 0x7fffffffull ? 0x7fffffffu : (unsigned)bytes};
 }
-inline f32x4 buffer_load_x4(BufferRsrc b, unsigned voffset_bytes, unsigned soffset_bytes);
-template <int AUX>
-inline f32x4 buffer_load_x4_aux(BufferRsrc b, unsigned voffset_bytes, unsigned soffset_bytes) { return buffer_load_x4(b, voffset_bytes, soffset_bytes); }
 inline f32x4 buffer_load_x4(BufferRsrc b, unsigned voffset_bytes, unsigned soffset_bytes) {
     f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
     if ((unsigned long long)voffset_bytes + 16ull <= (unsigned long long)b.bytes)
@@ -106,7 +103,6 @@ inline void buffer_store_f32(BufferRsrc b, float v, unsigned voffset_bytes, unsi
     if ((unsigned long long)voffset_bytes + 4ull <= (unsigned long long)b.bytes)
         __builtin_memcpy(const_cast<char *>(b.base) + (size_t)voffset_bytes + soffset_bytes, &v, 4);
 }
-inline void buffer_store_f32_nt(BufferRsrc b, float v, unsigned voffset_bytes, unsigned soffset_bytes) { buffer_store_f32(b, v, voffset_bytes, soffset_bytes); }
 inline void buffer_store_x4(BufferRsrc b, f32x4 v, unsigned voffset_bytes, unsigned soffset_bytes) {
     if ((unsigned long long)voffset_bytes + 16ull <= (unsigned long long)b.bytes)
         __builtin_memcpy(const_cast<char *>(b.base) + (size_t)voffset_bytes + soffset_bytes, &v, 16);

@@ -527,9 +527,9 @@ g6a)
   withlib R5 line rt128_R5 --arch resnet_h --mode train --batch 128 --steps 3 --warmup 2
   ;;
 ab1)
-  # packed vs scalar fp32 VALU beside the MFMAs (verdict round 4, task 1a), running weight offset, s_setprio
+  # packed vs scalar fp32 VALU beside the MFMAs (verdict round 4, task 1a); the s_setprio and table-weight-offset variants (4002-4004) are retired
   echo "== pytest on the scalar build"; withlib SC timeout 900 python -m pytest tests -m gpu -q -x --timeout 600 -k "winograd4 or wino4 or structured or pinned or conv_winograd" > $O/pytest_sc.log 2>&1; echo "rc=$?"; tail -2 $O/pytest_sc.log
-  echo "== wino4 per-layer round-robin"; DREAM_W4_DIAG_KS=4001,4002,4003,4004,4005,15 timeout 400 python tools/wino4_diag.py run --batch 128 2>&1 | grep -v "Warning\|amdgpu.ids" | tee $O/wino4_diag.txt
+  echo "== wino4 per-layer round-robin"; DREAM_W4_DIAG_KS=4001,4005,15 timeout 400 python tools/wino4_diag.py run --batch 128 2>&1 | grep -v "Warning\|amdgpu.ids" | tee $O/wino4_diag.txt
   echo "== headline, library A/B"
   for l in R4 PK SC SCP PK SC R4 SCP; do withlib $l line dflt_$l; done
   echo "== training, library A/B"
@@ -610,6 +610,7 @@ sbatch)
   echo "== pytest"; DREAM_SIDE_BATCH=8 timeout 900 python -m pytest tests -m gpu -q -x --timeout 600 -k "resnet_h_train_step or resnet_f_train_step or vgg_f_train or reference_golden" > $O/pytest.log 2>&1; echo "rc=$?"; tail -2 $O/pytest.log
   ;;
 waux)
+  # history: W1 / W16 were cache-policy builds of the F(4x4) weight loads (sc0 / sc1), a build fork retired after this A/B (no gain)
   for r in a b c; do for l in W0 W1 W16; do withlib $l line dflt_${l}_$r; done; done
   for l in W0 W16 W0 W16; do withlib $l line vt_$l --mode train --steps 4 --warmup 2; done
   ;;

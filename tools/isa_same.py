@@ -1,13 +1,21 @@
 #!/usr/bin/env python
-"""Is a kernel's machine code unchanged by an edit?  Compiles one .hip source of dream_amd/csrc at a git revision and in the working
-tree for gfx950 and compares the assembly kernel by kernel (comments stripped, basic-block labels renumbered).  Runs without a GPU.
+"""Is a kernel's machine code unchanged by an edit?  Compiles one .hip source of dream_amd/csrc (or, with `all`, every one) at a git
+revision and in the working tree for gfx950 and compares the assembly kernel by kernel (comments stripped, basic-block labels
+renumbered).  Runs without a GPU.
 
     python tools/isa_same.py HEAD~1 conv_wino.hip [substring of the mangled kernel names to report]
+    python tools/isa_same.py HEAD~1 all
+
+The revision's source is compiled against the revision's own headers (dream_amd/csrc and include/ extracted into a temporary
+directory), the working tree's source in place, both with the flags the product library is built with (__graft_entry__: plain fp32
+VALU for most units); nothing is written into the source tree.  With `all`: one summary line per file, plus
+every kernel that is not SAME.  Exit status 0 when every kernel of the revision is SAME in the working tree.
 
 Why: kernels written against the edge of the register file (conv_wino_kernel<4,1,0>: 253-255 VGPRs) change their register
 allocation when code is merely PRESENT in the translation unit -- round 4 added a BatchNorm-folding variant of the Winograd kernel
 in the last hours, with no GPU time left to re-measure the plain kernels; this check showed all 15 of them instruction-identical to
 the measured library (the body is included twice, conv_wino_body.inc, instead of being templated on the new feature)."""
+import concurrent.futures
 import hashlib
 import os
 import re
@@ -16,9 +24,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dream_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(CSRC, "include"), "-I", CSRC,
-         "-I", os.path.join(ROOT, "include"), "-Wno-unused-result", "-x", "hip"]
+sys.path.insert(0, ROOT)
+from __graft_entry__ import SCALAR_F32_FLAGS, SCALAR_F32_SOURCES      # noqa: E402  (the product's per-unit flags)
+CSRC_REL = os.path.join("dream_amd", "csrc")
 
 
 def kernels(asm_path):
@@ -32,36 +40,63 @@ def kernels(asm_path):
     return out
 
 
-def compile_to_asm(src_text_dir, name, tmp, tag):
-    # the source must sit next to its headers / included bodies: compile a copy placed in csrc under a scratch name
-    scratch = os.path.join(CSRC, "_isa_%s_%s" % (tag, name))
-    with open(scratch, "w") as f:
-        f.write(src_text_dir)
-    try:
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", scratch, "-save-temps=obj", "-o", os.path.join(tmp, tag + ".o")],
-                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    finally:
-        os.remove(scratch)
-    stem = os.path.splitext(os.path.basename(scratch))[0]
-    return os.path.join(tmp, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")
+def compile_to_asm(root, name, out_dir):
+    """Kernels of root/dream_amd/csrc/name, compiled against root's headers; every product goes to out_dir."""
+    csrc = os.path.join(root, CSRC_REL)
+    os.makedirs(out_dir)
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(csrc, "include"), "-I", csrc,
+             "-I", os.path.join(root, "include"), "-Wno-unused-result", "-x", "hip"] + (SCALAR_F32_FLAGS if name in SCALAR_F32_SOURCES else [])
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join(csrc, name), "-save-temps=obj", "-o", os.path.join(out_dir, "out.o")],
+                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return kernels(os.path.join(out_dir, os.path.splitext(name)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s"))
+
+
+def compare(a, b, want=""):
+    """[(state, kernel)] over the kernels of either side whose name contains `want`, and whether nothing of `a` changed or went."""
+    rows = []
+    for k in sorted(set(a) | set(b)):
+        if want not in k:
+            continue
+        state = "only in %s" % ("old" if k in a else "new") if (k in a) != (k in b) else ("SAME" if a[k] == b[k] else "DIFFERENT")
+        rows.append((state, k))
+    return rows, all(s == "SAME" or s == "only in new" for s, _ in rows)
+
+
+def hip_sources(root):
+    return sorted(f for f in os.listdir(os.path.join(root, CSRC_REL)) if f.endswith(".hip"))
 
 
 def main():
     rev, name = sys.argv[1], sys.argv[2]
     want = sys.argv[3] if len(sys.argv) > 3 else ""
-    old = subprocess.check_output(["git", "-C", ROOT, "show", "%s:dream_amd/csrc/%s" % (rev, name)]).decode()
-    new = open(os.path.join(CSRC, name)).read()
     with tempfile.TemporaryDirectory() as tmp:
-        a = kernels(compile_to_asm(old, name, tmp, "old"))
-        b = kernels(compile_to_asm(new, name, tmp, "new"))
-    same = True
-    for k in sorted(set(a) | set(b)):
-        if want not in k:
-            continue
-        state = "only in %s" % ("old" if k in a else "new") if (k in a) != (k in b) else ("SAME" if a[k] == b[k] else "DIFFERENT")
-        same &= state == "SAME" or state.startswith("only in new")
-        print("%-11s %s" % (state, k))
-    sys.exit(0 if same else 1)
+        old_root = os.path.join(tmp, "old")
+        os.makedirs(old_root)
+        archive = subprocess.Popen(["git", "-C", ROOT, "archive", rev, "dream_amd/csrc", "include"], stdout=subprocess.PIPE)
+        subprocess.check_call(["tar", "-x", "-C", old_root], stdin=archive.stdout)
+        if archive.wait():
+            sys.exit("git archive %s failed" % rev)
+        names = sorted(set(hip_sources(old_root)) | set(hip_sources(ROOT))) if name == "all" else [name]
+        jobs = {}
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+            for n in names:
+                for tag, root in (("old", old_root), ("new", ROOT)):
+                    if os.path.exists(os.path.join(root, CSRC_REL, n)):
+                        jobs[n, tag] = pool.submit(compile_to_asm, root, n, os.path.join(tmp, "obj", tag, n))
+        ok = True
+        for n in names:
+            if (n, "old") not in jobs or (n, "new") not in jobs:
+                print("%-20s only in %s" % (n, "old" if (n, "old") in jobs else "new"))
+                ok &= (n, "new") in jobs
+                continue
+            rows, same = compare(jobs[n, "old"].result(), jobs[n, "new"].result(), want)
+            ok &= same
+            if name == "all":
+                print("%-20s %d kernels, %d SAME" % (n, len(rows), sum(s == "SAME" for s, _ in rows)))
+                rows = [r for r in rows if r[0] != "SAME"]
+            for state, k in rows:
+                print("%-11s %s" % (state, k))
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":
