@@ -174,6 +174,9 @@ _SIGNATURES = {
     "dream_scatter2_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dream_conv3x3_wgrad_workspace": (_SZ, [_I, _I, _I, _I, _I]),
     "dream_conv3x3_wgrad_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv3x3_wgrad_f16_workspace": (_SZ, [_I, _I, _I, _I, _I]),
+    "dream_conv3x3_wgrad_f16_splitk": (_I, [_I, _I, _I, _I, _I]),
+    "dream_conv3x3_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv3x3_wgrad_winograd_workspace": (_SZ, [_I, _I, _I, _I, _I]),
     "dream_conv3x3_wgrad_winograd_nhwc_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv3x3_wgrad_winograd_fuses_bias": (_I, [_I, _I, _I]),

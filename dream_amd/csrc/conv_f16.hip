@@ -22,189 +22,35 @@ namespace {
 
 template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16Params p) {
-    constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
-    constexpr int BN = 32 * NR * WN;
-    constexpr int Q = KC / 4;                       // float4 pieces per patch row
-    constexpr int NA_IT = (NPM * Q + NT - 1) / NT;
-    constexpr int NB_PIECES = BN * (KC / 8);        // 16-B pieces of the weight tile per stage
-    constexpr int NB_IT = (NB_PIECES + NT - 1) / NT;
-    static_assert(WM * WN == 4 || WM * WN == 8, "4 or 8 wavefronts per workgroup");
+    constexpr bool EPI_MASK = false;
+#include "conv_f16_body.inc"
+}
 
-    DREAM_DYNAMIC_LDS(_Float16, smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
-    const int wm = wave / WN, wn = wave % WN;
-    const int li = lane & 31, lh = lane >> 5;
-    const int PW = p.PW, TW = p.TW, NP = p.PH * PW;
-    _Float16 *sA = smem;                            // [DB ? 2 : 1][NP][S16]
-    _Float16 *sB = sA + (DB ? 2 : 1) * NP * S16;    // [2][BN][S16]
-
-    // XCD-aware placement (see conv_mfma.hip): each XCD works on a contiguous range of tiles so halos meet in its L2
-    int t = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-    if (t >= p.B * p.tiles_x * p.tiles_y) return;
-    const int tix = t % p.tiles_x;
-    t /= p.tiles_x;
-    const int tiy = t % p.tiles_y;
-    const int b = t / p.tiles_y;
-    const int y0 = tiy * p.TH, x0 = tix * TW;
-    const int n0 = blockIdx.y * BN;
-    const bool zst = (p.flags & DREAM_CONV_ZEROSTUFF2X) != 0;
-    const bool ups = (p.flags & DREAM_CONV_UPSAMPLE2X) != 0 || zst;
-    const bool pool = (p.flags & DREAM_CONV_POOL2) != 0;
-    const float *xb = p.x + (size_t)b * p.Hs * p.Ws * p.Cin;
-
-    // input scale: max|x| * 2^ea in [2^13, 2^14)
-    const unsigned abits = *p.amax_in;
-    const int aexp = (int)((abits >> 23) & 255) - 127;
-    int ea = (abits == 0u) ? 0 : 13 - aexp;
-    ea = ea < -100 ? -100 : (ea > 100 ? 100 : ea);
-    const float sa = pow2f(ea);
-    const float inv = pow2f(-(ea + *p.w_exp) < -126 ? -126 : (-(ea + *p.w_exp) > 127 ? 127 : -(ea + *p.w_exp)));
-
-    int a_goff[NA_IT], a_soff[NA_IT];
-#pragma unroll
-    for (int it = 0; it < NA_IT; ++it) {
-        const int idx = tid + it * NT;
-        const int pp = idx / Q, q = idx % Q;
-        a_soff[it] = (pp < NP) ? pp * S16 + q * 4 : -1;
-        const int py = pp / PW, px = pp - py * PW;
-        const int gy = y0 * p.in_scale - p.pad_y + py * p.in_step, gx = x0 * p.in_scale - p.pad_x + px * p.in_step;
-        const bool inb = (pp < NP) && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win && !(zst && ((gy | gx) & 1));
-        const int sy = ups ? (gy >> 1) : gy, sx = ups ? (gx >> 1) : gx;
-        a_goff[it] = inb ? (sy * p.Ws + sx) * p.Cin + q * 4 : -1;
-    }
-    int b_goff[NB_IT], b_soff[NB_IT];
-#pragma unroll
-    for (int it = 0; it < NB_IT; ++it) {
-        const int idx = tid + it * NT;
-        const int n = idx / (KC / 8), q = idx % (KC / 8);
-        b_soff[it] = (idx < NB_PIECES) ? n * S16 + q * 8 : -1;
-        b_goff[it] = (n0 + n) * p.Cin + q * 8;
-    }
-    const size_t w_tap_stride = (size_t)p.CoutPad * p.Cin;
-
-    int a_frag[MR], b_frag[NR];
-#pragma unroll
-    for (int ms = 0; ms < MR; ++ms) {
-        int m = (wm * MR + ms) * 32 + li;
-        if (m >= p.TH * TW) m = 0;
-        int ty, tx;
-        tile_xy(m, TW, p.rcpTW, pool, &ty, &tx);
-        a_frag[ms] = (ty * PW + tx) * p.lane_stride * S16 + lh * 8;
-    }
-#pragma unroll
-    for (int ns = 0; ns < NR; ++ns) b_frag[ns] = ((wn * NR + ns) * 32 + li) * S16 + lh * 8;
-
-    f32x16 acc[MR][NR];
-#pragma unroll
-    for (int ms = 0; ms < MR; ++ms)
-#pragma unroll
-        for (int ns = 0; ns < NR; ++ns)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ms][ns][r] = 0.0f;
-
-    f32x4 a_reg[NA_IT];
-    f16x8 b_reg[NB_IT];
-    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-
-    auto load_a = [&](int c0) {
-#pragma unroll
-        for (int it = 0; it < NA_IT; ++it)
-            a_reg[it] = (a_goff[it] >= 0) ? *(const f32x4 *)(xb + a_goff[it] + c0) : zero4;
-    };
-    auto store_a = [&](int abuf) {     // the one rounding of the activations: fp16(v * 2^ea), to nearest even
-        _Float16 *d = sA + abuf * NP * S16;
-#pragma unroll
-        for (int it = 0; it < NA_IT; ++it) {
-            if (a_soff[it] >= 0) {
-                f16x4 h;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) h[k] = (_Float16)(a_reg[it][k] * sa);
-                *(f16x4 *)(d + a_soff[it]) = h;
-            }
-        }
-    };
-    auto load_b = [&](int tap, int c0) {
-        const size_t base = (size_t)((p.tap_w >> (4 * tap)) & 15) * w_tap_stride + c0;
-#pragma unroll
-        for (int it = 0; it < NB_IT; ++it)
-            if (b_soff[it] >= 0) b_reg[it] = *(const f16x8 *)(p.w_hi + base + b_goff[it]);
-    };
-    auto store_b = [&](int buf) {
-        _Float16 *d = sB + buf * BN * S16;
-#pragma unroll
-        for (int it = 0; it < NB_IT; ++it)
-            if (b_soff[it] >= 0) *(f16x8 *)(d + b_soff[it]) = b_reg[it];
-    };
-
-    const int nchunks = p.Cin / KC;
-    load_a(0);
-    load_b(0, 0);
-    store_a(0);
-    store_b(0);
-    __syncthreads();
-
-    int buf = 0, abuf = 0, tap = 0, chunk = 0;
-    const int ntaps = p.ntaps, nstages = nchunks * ntaps;
-    for (int st = 0; st < nstages; ++st) {
-        const bool last_tap = (tap == ntaps - 1);
-        const bool more_chunks = (chunk + 1 < nchunks);
-        const bool have_next = (st + 1 < nstages);
-        if (have_next) load_b(last_tap ? 0 : tap + 1, last_tap ? (chunk + 1) * KC : chunk * KC);
-        // DB: the next chunk's patch is fetched at the first tap and held in registers until the last; SB: one stage ahead
-        if ((DB ? tap == 0 : last_tap) && more_chunks) load_a((chunk + 1) * KC);
-
-        const int tdy = (int)((p.tap_dy >> (4 * tap)) & 15), tdx = (int)((p.tap_dx >> (4 * tap)) & 15);
-        const _Float16 *pa = sA + abuf * NP * S16 + (tdy * PW + tdx) * S16;
-        const _Float16 *pb = sB + buf * BN * S16;
-#pragma unroll
-        for (int kk = 0; kk < KC; kk += 16) {
-            f16x8 a[MR], w[NR];
-#pragma unroll
-            for (int ms = 0; ms < MR; ++ms) a[ms] = *(const f16x8 *)(pa + a_frag[ms] + kk);
-#pragma unroll
-            for (int ns = 0; ns < NR; ++ns) w[ns] = *(const f16x8 *)(pb + b_frag[ns] + kk);
-            if (PRIO) __builtin_amdgcn_s_setprio(1);     // co-resident waves of the other workgroup are in their load phase
-#pragma unroll
-            for (int ms = 0; ms < MR; ++ms)
-#pragma unroll
-                for (int ns = 0; ns < NR; ++ns) acc[ms][ns] = mfma_f32_32x32x16_f16(a[ms], w[ns], acc[ms][ns]);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
-        }
-
-        if (have_next) store_b(buf ^ 1);
-        if (last_tap && more_chunks) {
-            if (DB) {
-                // the other patch buffer was last read in the previous chunk: every wave has passed a barrier since
-                store_a(abuf ^ 1);
-                abuf ^= 1;
-            } else {
-                __syncthreads();
-                store_a(0);
-            }
-        }
-        __syncthreads();
-        buf ^= 1;
-        if (last_tap) { tap = 0; ++chunk; } else ++tap;
-    }
-
-#include "conv_f16_epilogue.inc"
+// The same kernel with the DREAM_CONV_RELUMASK epilogue (y = residual > 0 ? conv : 0: the data gradient of a conv behind a ReLU,
+// train_precision="fp16").  A kernel of its own, from the same text, so that the inference kernels above stay instruction-identical.
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = true;
+#include "conv_f16_body.inc"
 }
 
 struct Variant16h {
     const char *name;
     int BM, BN, NP_MAX, threads, abufs;
     void (*kernel)(const Conv16Params);
+    void (*mask_kernel)(const Conv16Params);
 };
+#define F16_KERNELS(...) conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
-    {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, conv_f16_kernel<2, 2, 2, 2, 192, true>},
-    {"f16 m2n2w4x1 db", 256, 64, 352, 256, 2, conv_f16_kernel<2, 2, 4, 1, 352, true>},
-    {"f16 m2n1w4x1 db", 256, 32, 352, 256, 2, conv_f16_kernel<2, 1, 4, 1, 352, true>},
-    {"f16 m1n2w2x2 db", 64, 128, 128, 256, 2, conv_f16_kernel<1, 2, 2, 2, 128, true>},
-    {"f16 m2n2w4x2 db", 256, 128, 352, 512, 2, conv_f16_kernel<2, 2, 4, 2, 352, true>},             // 8 waves
-    {"f16 m2n2w4x1 sb", 256, 64, 352, 256, 1, conv_f16_kernel<2, 2, 4, 1, 352, false>},            // the split kernel's loop: 64-channel 3x3 convs
-    {"f16 m2n2w4x2 sb", 256, 128, 352, 512, 1, conv_f16_kernel<2, 2, 4, 2, 352, false>},
-    {"f16 m2n2w4x2 db prio", 256, 128, 352, 512, 2, conv_f16_kernel<2, 2, 4, 2, 352, true, true>},  // A/B arm: s_setprio around the MFMAs
+    {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
+    {"f16 m2n2w4x1 db", 256, 64, 352, 256, 2, F16_KERNELS(2, 2, 4, 1, 352, true)},
+    {"f16 m2n1w4x1 db", 256, 32, 352, 256, 2, F16_KERNELS(2, 1, 4, 1, 352, true)},
+    {"f16 m1n2w2x2 db", 64, 128, 128, 256, 2, F16_KERNELS(1, 2, 2, 2, 128, true)},
+    {"f16 m2n2w4x2 db", 256, 128, 352, 512, 2, F16_KERNELS(2, 2, 4, 2, 352, true)},             // 8 waves
+    {"f16 m2n2w4x1 sb", 256, 64, 352, 256, 1, F16_KERNELS(2, 2, 4, 1, 352, false)},            // the split kernel's loop: 64-channel 3x3 convs
+    {"f16 m2n2w4x2 sb", 256, 128, 352, 512, 1, F16_KERNELS(2, 2, 4, 2, 352, false)},
+    {"f16 m2n2w4x2 db prio", 256, 128, 352, 512, 2, F16_KERNELS(2, 2, 4, 2, 352, true, true)},  // A/B arm: s_setprio around the MFMAs
 };
 constexpr int kNumF16 = 8;
 int g_forced_f16 = -1;
@@ -234,13 +80,17 @@ int launch_f16(const float *x, const unsigned *amax_in, const void *w, const int
     const bool pool = (flags & DREAM_CONV_POOL2) != 0;
     DREAM_REQUIRE(!pool || (!(flags & DREAM_CONV_OUT_NCHW) && residual == nullptr && g.H >= 2 && g.W >= 2 && g.out_scale == 1),
                   "fused max-pool: NHWC output, no residual");
+    const bool mask = (flags & DREAM_CONV_RELUMASK) != 0;
+    DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
+                  "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
+    void (*const kernel)(const Conv16Params) = mask ? var.mask_kernel : var.kernel;
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
     DREAM_REQUIRE(lds <= 160 * 1024, "LDS request %zu too large", lds);
-    if (dream_allow_full_lds((const void *)var.kernel)) return 2;
+    if (dream_allow_full_lds((const void *)kernel)) return 2;
     const dim3 grid((unsigned)(ceil_div((int)((size_t)B * p.tiles_x * p.tiles_y), 8) * 8), (unsigned)ceil_div(Cout, var.BN));
-    hipLaunchKernelGGL(var.kernel, grid, dim3(var.threads), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kernel, grid, dim3(var.threads), lds, (hipStream_t)stream, p);
     DREAM_LAUNCH_OK();
     return 0;
 }

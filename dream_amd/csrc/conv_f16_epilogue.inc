@@ -1,6 +1,7 @@
 // Epilogue of the implicit-GEMM kernels on the fp16 matrix cores, included at the end of conv_f16x3_kernel and conv_f16_kernel (one
 // text, and the split kernel's machine code stays what was measured).  In scope: p, acc[MR][NR], inv, wm, wn, li, lh, b, y0, x0, n0,
-// TW, pool.  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes max|y|.
+// TW, pool, EPI_MASK (a bool constant).  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes
+// max|y|.  EPI_MASK (conv_f16_mask_kernel only): `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it.
     // ---- epilogue -----------------------------------------------------------------------------------------
     const bool relu = (p.flags & DREAM_CONV_RELU) != 0;
     const bool nchw = (p.flags & DREAM_CONV_OUT_NCHW) != 0;
@@ -31,7 +32,8 @@
                             ? (((size_t)b * p.Cout + ncol[ns]) * p.Ho + oy) * p.Wo + ox
                             : (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
                         float v = acc[ms][ns][r] * scale_v[ns] + shift_v[ns];
-                        if (p.residual != nullptr) v = v + p.residual[o];
+                        if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
+                        else if (p.residual != nullptr) v = v + p.residual[o];
                         if (relu) v = fmaxf(v, 0.0f);
                         p.y[o] = v;
                         amax = fmaxf(amax, fabsf(v));

@@ -199,6 +199,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16x3_kernel(const Conv1
         if (last_tap) { tap = 0; ++chunk; } else ++tap;
     }
 
+    constexpr bool EPI_MASK = false;                // (the ReLU-mask epilogue is the half-precision kernel's: conv_f16.hip)
 #include "conv_f16_epilogue.inc"
 }
 

@@ -1,0 +1,273 @@
+// Half-precision weight + bias gradient of a 3x3 stride-1 conv (train_precision="fp16"; replaces ATen's conv backward-weight reached
+// from loss.backward(), dream/network.py:335, for the plain Conv2d layers of dream/models.py:594-615, 695-747):
+//
+//   dW[t][co][ci] = 2^-(ex+eg) * sum over (b, y, x) of  fp16(dy[b,y,x,co] * 2^eg) * fp16(x[b, y+dy(t), x+dx(t), ci] * 2^ex)
+//
+// Both operands are fp32 NHWC in HBM and are rounded once, while they are staged into LDS; 2^ex / 2^eg put max|x| / max|dy| (the amax
+// scalars, as in conv_f16.hip) into [2^13, 2^14).  The products run on v_mfma_f32_32x32x16_f16 (a product of two halfs is exact in
+// fp32), accumulation is fp32.  The bias gradient is the channel sum of the UNROUNDED fp32 dy, summed while dy is staged.
+//
+// The contraction runs over POSITIONS, and an MFMA operand is 8 consecutive k's of one row / column in one lane: so LDS holds the
+// TRANSPOSED images, [channel][position].  A position tile is 8 rows x 16 columns; a k-step (16 positions) is one tile row, a lane's 8 k's
+// are 8 consecutive x's of it -- the same order for both operands.
+//   sY[co][ty*16 + tx]                    channel stride 136 halfs (272 B: an odd number of 16-B slots -> ds_read_b128 conflict-free)
+//   sX[dx][ci][py*16 + tx] = x[y0-1+py][x0-1+tx+dx][ci]     THREE copies of the 10-row patch, shifted by the tap's dx = 0 | 1 | 2, so the
+//                                         operand of every tap is an ALIGNED 16-byte read (a tap's dy only selects the row);
+//                                         channel stride 168 halfs (336 B: 21 slots).
+// Staging: a lane loads the same four channels (one float4) of 8 (dy) or 10 (x) consecutive positions, converts, and writes one
+// position-contiguous 16-byte piece per channel (x: per channel and shift).  LDS: 17 + 63 KB = 80 KB, two workgroups per CU.
+// Workgroup: 4 waves as 2 x 2 blocks of 32 co x 32 ci, NINE tap accumulators each (144 VGPRs), as wgrad.hip's <1,1,9,128>.  A patch row is
+// read once per shift and serves the three taps rows that use it (registers, rolling over the k-steps).
+//
+// Split-K over position tiles; partials go to the workspace and a second kernel sums them in a FIXED order (deterministic, no
+// floating-point atomics) and applies 2^-ex * 2^-eg.
+#include <dream_cdna4.h>
+#include "common.h"
+#include "../../include/dream_hip.h"
+
+namespace {
+
+constexpr int TH = 8, TW = 16, PIX = TH * TW;        // position tile
+constexpr int PH = TH + 2;                            // patch rows
+constexpr int RW = 64, CW = 64;                       // dW tile of a workgroup: rows (co) x columns (ci)
+constexpr int SY = PIX + 8;                           // halfs per dy channel
+constexpr int SX = PH * TW + 8;                       // halfs per x channel of one shifted copy
+constexpr size_t LDS_BYTES = ((size_t)RW * SY + (size_t)3 * CW * SX) * sizeof(_Float16);
+
+struct Wgrad16Params {
+    const float *x;          // [B,H,W,Cin]
+    const float *dy;         // [B,H,W,Ct]
+    const unsigned *amax_x, *amax_dy;
+    float *part;             // [splitk][9][RowsPad][Cin]
+    float *bias_part;        // [splitk][RowsPad] or null
+    int B, H, W, Cin, Ct, RowsPad;
+    int tiles_x, tiles_y, tiles_total, splitk, nrb, ncb;
+};
+
+DREAM_DEVICE float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+
+// e with max|t| * 2^e in [2^13, 2^14): 13 - exponent, clamped to +-100; 0 for a zero tensor (conv_f16.hip)
+DREAM_DEVICE int scale_exponent(unsigned amax_bits) {
+    const int e = (amax_bits == 0u) ? 0 : 13 - ((int)((amax_bits >> 23) & 255) - 127);
+    return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+
+__global__ void __launch_bounds__(256, 2) wgrad_f16_kernel(const Wgrad16Params p) {
+    DREAM_DYNAMIC_LDS(_Float16, smem);
+    _Float16 *sY = smem;                  // [RW][SY]
+    _Float16 *sX = smem + RW * SY;        // [3][CW][SX]
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+    const int wo = wave >> 1, wi = wave & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    // XCD-aware placement as in wgrad.hip: the (row block, column block) tiles of one split-K slice share an XCD's L2
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int nblk = p.nrb * p.ncb;
+    const int blk = slot % nblk, ks = (slot / nblk) * 8 + xcd;
+    if (ks >= p.splitk) return;
+    const int rbk = blk % p.nrb, cbk = blk / p.nrb;
+    const int co0 = rbk * RW, ci0 = cbk * CW;
+    const float sx = pow2f(scale_exponent(*p.amax_x)), sg = pow2f(scale_exponent(*p.amax_dy));
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    f32x4 bsum = {0.0f, 0.0f, 0.0f, 0.0f};           // this thread's share of the channel sums of the unrounded dy
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int q = tid & 15;                          // channel quad of the staging
+    const int grp = tid >> 4;                        // dy staging: the 8 positions (ty = grp >> 1, tx = 8 * (grp & 1) ..)
+    const bool y_chan_ok = co0 + q * 4 < p.Ct;       // channel counts are multiples of 4
+    const bool x_chan_ok = ci0 + q * 4 < p.Cin;
+
+    for (int tile = ks; tile < p.tiles_total; tile += p.splitk) {
+        int t = tile;
+        const int tix = t % p.tiles_x;
+        t /= p.tiles_x;
+        const int tiy = t % p.tiles_y;
+        const int b = t / p.tiles_y;
+        const int y0 = tiy * TH, x0 = tix * TW;
+        const float *xb = p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;
+        const float *gb = p.dy + (size_t)b * p.H * p.W * p.Ct + co0 + q * 4;
+
+        __syncthreads();                             // previous tile fully consumed
+        // ---- dy: 8 consecutive positions x 4 channels per thread (loads from clamped, always-legal addresses + a select) -----------
+        {
+            const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
+            f32x4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const bool ok = y_chan_ok && oy < p.H && ox0 + j < p.W;
+                v[j] = *(const f32x4 *)(ok ? gb + ((size_t)oy * p.W + ox0 + j) * p.Ct : p.dy);
+                v[j] = ok ? v[j] : zero4;
+                bsum += v[j];
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f16x8 h;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) h[j] = (_Float16)(v[j][c] * sg);      // the one rounding of dy
+                *(f16x8 *)(sY + (q * 4 + c) * SY + grp * 8) = h;
+            }
+        }
+        // ---- x: 10 consecutive positions of a patch row x 4 channels per unit; three shifted copies ----------------------------------
+        for (int u = tid >> 4; u < PH * 2; u += 16) {
+            const int py = u >> 1, half = u & 1;
+            const int gy = y0 - 1 + py, gx0 = x0 - 1 + half * 8;
+            f16x4 h[10];
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const bool ok = x_chan_ok && gy >= 0 && gy < p.H && gx0 + j >= 0 && gx0 + j < p.W;
+                f32x4 v = *(const f32x4 *)(ok ? xb + ((size_t)gy * p.W + gx0 + j) * p.Cin : p.x);
+                v = ok ? v : zero4;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) h[j][c] = (_Float16)(v[c] * sx);      // the one rounding of x
+            }
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    f16x8 piece;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) piece[j] = h[j + dx][c];
+                    *(f16x8 *)(sX + (dx * CW + q * 4 + c) * SX + py * TW + half * 8) = piece;
+                }
+        }
+        __syncthreads();
+
+        // ---- k-steps: one tile row (16 positions) each; patch row s + dy serves tap row dy -------------------------------------------
+        const _Float16 *aY = sY + (wo * 32 + li) * SY + lh * 8;
+        const _Float16 *bX = sX + (wi * 32 + li) * SX + lh * 8;
+        f16x8 row[3][3];                             // [patch row % 3][shift]
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) row[r][dx] = *(const f16x8 *)(bX + dx * CW * SX + r * TW);
+#pragma unroll
+        for (int s = 0; s < TH; ++s) {
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) row[(s + 2) % 3][dx] = *(const f16x8 *)(bX + dx * CW * SX + (s + 2) * TW);
+            const f16x8 a = *(const f16x8 *)(aY + s * TW);
+#pragma unroll
+            for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) acc[ty * 3 + dx] = mfma_f32_32x32x16_f16(a, row[(s + ty) % 3][dx], acc[ty * 3 + dx]);
+        }
+    }
+
+    // ---- partials (still in the scaled domain) ------------------------------------------------------------------------------------
+#pragma unroll
+    for (int tp = 0; tp < 9; ++tp) {
+        float *part = p.part + ((size_t)ks * 9 + tp) * p.RowsPad * p.Cin;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = co0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int i = ci0 + wi * 32 + li;
+            if (o < p.RowsPad && i < p.Cin) part[(size_t)o * p.Cin + i] = acc[tp][r];
+        }
+    }
+    if (cbk == 0 && p.bias_part != nullptr) {
+        // threads sharing q (the same 4 channels) differ in grp: reduce the 16 groups through LDS, in group order
+        float *red = (float *)smem;
+        __syncthreads();
+        *(f32x4 *)(red + (grp * 16 + q) * 4) = bsum;
+        __syncthreads();
+        if (tid < RW) {
+            float s = 0.0f;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) s += red[(g * 16 + (tid >> 2)) * 4 + (tid & 3)];
+            if (co0 + tid < p.RowsPad) p.bias_part[(size_t)ks * p.RowsPad + co0 + tid] = s;
+        }
+    }
+}
+
+// fixed-order sum over the split-K partials, times 2^-ex * 2^-eg (two exact steps: either factor alone is a normal number)
+__global__ void __launch_bounds__(256) wgrad_f16_reduce_kernel(const float *part, float *out, size_t n, int splitk,
+                                                               const unsigned *amax_x, const unsigned *amax_dy) {
+    const float ix = amax_x ? pow2f(-scale_exponent(*amax_x)) : 1.0f, ig = amax_dy ? pow2f(-scale_exponent(*amax_dy)) : 1.0f;
+    const size_t n4 = n / 4;                         // n is a multiple of 4 (channel counts are)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+        const f32x4 *src = (const f32x4 *)part + i;
+        int k = 0;
+        for (; k + 8 <= splitk; k += 8) {            // eight independent loads in flight, summed in index order
+            f32x4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(k + j) * n4];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[j];
+        }
+        for (; k < splitk; ++k) s += src[(size_t)k * n4];
+        ((f32x4 *)out)[i] = (s * ix) * ig;
+    }
+}
+
+int plan_splitk(int B, int H, int W, int Cin, int RowsPad) {
+    const long tiles = (long)B * ceil_div(H, TH) * ceil_div(W, TW);
+    const long ctiles = (long)ceil_div(RowsPad, RW) * ceil_div(Cin, CW);
+    long sk = wgrad_target_workgroups(512) / ctiles;      // 512 workgroups = 256 CUs x 2 resident (wgrad.hip)
+    if (sk < 1) sk = 1;
+    if (sk > tiles) sk = tiles;
+    if (sk > 1024) sk = 1024;
+    return (int)sk;
+}
+
+bool shape_ok(int B, int H, int W, int Cin, int RowsPad) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 32 == 0 && RowsPad > 0 && RowsPad % 64 == 0;
+}
+
+}  // namespace
+
+// number of position slices the contraction of this problem is split into (a pure host computation: no GPU is touched)
+extern "C" int dream_conv3x3_wgrad_f16_splitk(int B, int H, int W, int Cin, int RowsPad) {
+    return shape_ok(B, H, W, Cin, RowsPad) ? plan_splitk(B, H, W, Cin, RowsPad) : 0;
+}
+
+extern "C" size_t dream_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin, int RowsPad) {
+    if (!shape_ok(B, H, W, Cin, RowsPad)) return 0;
+    const size_t sk = (size_t)plan_splitk(B, H, W, Cin, RowsPad);
+    return (sk * 9 * RowsPad * Cin + (sk + 1) * RowsPad) * sizeof(float);
+}
+
+// x [B,H,W,Cin], dy [B,H,W,Cdy] (fp32 NHWC), amax_x / amax_dy: device scalars, bit patterns of (an upper bound of) max|x| / max|dy|
+// -> dw_packed [9][RowsPad][Cin] (mode-0 layout: dream_unpack_conv3x3_weight), dbias [Cdy] or null.  Cin % 32 == 0, Cdy % 4 == 0,
+// RowsPad >= Cdy a multiple of 64; flags must be 0.
+extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
+                                                float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
+                                                int Cdy, int RowsPad, int flags, void *stream) {
+    DREAM_REQUIRE(x && amax_x && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
+    DREAM_REQUIRE(flags == 0, "wgrad_f16: flags %d not supported (plain 3x3 stride-1 convs only)", flags);
+    DREAM_REQUIRE(shape_ok(B, H, W, Cin, RowsPad) && Cdy > 0 && Cdy % 4 == 0 && RowsPad >= Cdy,
+                  "wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdy %d, pad %d): Cin %% 32, Cdy %% 4, pad %% 64", B, H, W, Cin, Cdy, RowsPad);
+    DREAM_REQUIRE((size_t)B * H * W * (size_t)(Cin > Cdy ? Cin : Cdy) < ((size_t)1 << 40), "wgrad_f16: tensor too large");
+    Wgrad16Params p;
+    p.x = x; p.dy = dy; p.amax_x = amax_x; p.amax_dy = amax_dy;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Ct = Cdy; p.RowsPad = RowsPad;
+    p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
+    p.tiles_total = B * p.tiles_x * p.tiles_y;
+    p.splitk = plan_splitk(B, H, W, Cin, RowsPad);
+    p.nrb = ceil_div(RowsPad, RW); p.ncb = ceil_div(Cin, CW);
+    p.part = (float *)workspace;
+    float *bias_part = p.part + (size_t)p.splitk * 9 * RowsPad * Cin;
+    p.bias_part = dbias ? bias_part : nullptr;
+    if (dream_allow_full_lds((const void *)wgrad_f16_kernel)) return 2;
+    const dim3 grid((unsigned)(p.nrb * p.ncb * ceil_div(p.splitk, 8) * 8));
+    hipLaunchKernelGGL(wgrad_f16_kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
+    DREAM_LAUNCH_OK();
+    const size_t n = (size_t)9 * RowsPad * Cin;
+    size_t gr = (n / 4 + 255) / 256;
+    if (gr > 2048) gr = 2048;
+    hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part, dw_packed,
+                       n, p.splitk, amax_x, amax_dy);
+    DREAM_LAUNCH_OK();
+    if (dbias) {
+        // bias partials are [splitk][RowsPad] of unscaled sums; only the first Cdy entries are wanted
+        float *total = bias_part + (size_t)p.splitk * RowsPad;
+        hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
+                           (size_t)RowsPad, p.splitk, (const unsigned *)nullptr, (const unsigned *)nullptr);
+        DREAM_LAUNCH_OK();
+        if (dream_copy_words(dbias, total, (size_t)Cdy * sizeof(float), (hipStream_t)stream)) return 2;
+    }
+    return 0;
+}

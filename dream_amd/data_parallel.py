@@ -780,6 +780,10 @@ class DreamDataParallel(nn.Module):
         if args or kwargs:
             return self.module(x, *args, **kwargs)
         one = self.n_devices(x.shape[0]) == 1
+        if (one and self.single_device_graphs and self.module.training and torch.is_grad_enabled()
+                and getattr(self.module, "train_precision", "fp32") != "fp32"):
+            raise ValueError("dream_amd: hip_graph_train (DREAM_TRAIN_GRAPH=1) does not replay train_precision=%r steps; switch one of "
+                             "them off" % (self.module.train_precision,))
         if one and not (self.single_device_graphs and self.module.training and torch.is_grad_enabled()):
             return self.module(x)
         params = self.module.dp_parameters()

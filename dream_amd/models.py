@@ -190,8 +190,12 @@ class DreamHourglass(nn.Module):
         # "fp32": exact fp32 MFMA kernel everywhere.  "fp16x3": inference runs the split-precision kernel
         # (fp32 in/out, 3 fp16 MFMAs per product, fp32-class error).  "fp16": inference runs the half-precision kernel (fp32 in/out,
         # operands rounded to fp16, one MFMA per product, fp32 accumulation: belief maps move by about 1e-3 .. 3e-3).
-        # Training always uses the fp32 kernels.
+        # Training uses the fp32 kernels whatever ``precision`` says.
         self.precision = "fp32"
+        # Training: "fp32", or "fp16" = the plain convs (_half_train_entry) run their forward, data-gradient and weight-gradient products
+        # on the fp16 matrix cores (conv_f16.hip, wgrad_f16.hip: fp32 tensors in HBM, operands rounded once while staged, per-tensor
+        # power-of-two scales from the amax side channel); every other plan entry keeps its fp32 launches.  Does not affect inference.
+        self.train_precision = "fp32"
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
         # implicit-GEMM kernel everywhere (csrc/conv_mfma.hip, the reference form)
@@ -312,6 +316,22 @@ class DreamHourglass(nn.Module):
             return ops.conv_transpose4x4s2(x, pk4, rows, None, bias, flags & CONV_RELU, direct_taps=36)
         return ops.upsample2_bwd(self._conv3x3(mod, 1, x))
 
+    def _check_train_precision(self):
+        if self.train_precision not in ("fp32", "fp16"):
+            raise ValueError("unknown train_precision %r (\"fp32\" or \"fp16\")" % (self.train_precision,))
+        return self.train_precision == "fp16"
+
+    @staticmethod
+    def _half_train_entry(kind, mod, flags, in_channels):
+        """The rule of train_precision="fp16", one for the forward pass, the data gradient and the weight gradient: a 3x3 stride-1
+        conv that neither follows an upsample nor writes the NCHW output, whose input carries exactly cin channels, cin and cout
+        multiples of 32 (the "plain" convs: for vgg_q every VGG conv after the first, the decoder and head convs but the two upsample
+        convs and the K-channel output conv)."""
+        if kind != "conv" or flags & (CONV_UPSAMPLE2X | CONV_OUT_NCHW):
+            return False
+        cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
+        return int(in_channels) == cin and cin % 32 == 0 and cout % 32 == 0
+
     # ---- which plan entries run as one -----------------------------------------------------------------------------------
     def _fuse_pool(self, layers, li, x_nhwc, split):
         """Inference: fold the 2x2 max-pool that follows conv ``li`` into its epilogue?  Not when the un-pooled tensor is
@@ -338,7 +358,7 @@ class DreamHourglass(nn.Module):
             return 0
         return n if self._conv3x3_choice(m1, 0, (n, h, w, cin), f1 | CONV_POOL2) == ("winograd", 4) else 0
 
-    def _group(self, layers, li, x, save, split):
+    def _group(self, layers, li, x, save, split, half_train=False):
         """The plan entries that the conv at ``li`` runs as one -> (name, frames per sub-batch of "pair+pool"):
           "conv"            the conv alone;
           "conv+pool"       inference: the 2x2 max-pool that follows, folded into the epilogue (CONV_POOL2);
@@ -354,6 +374,8 @@ class DreamHourglass(nn.Module):
         if kind == "conv" and follower == "pool":
             if not save:
                 return ("conv+pool" if self._fuse_pool(layers, li, x, split) else "conv"), 0
+            if half_train:              # a half-precision training conv folds nothing: backward needs the un-pooled output (its ReLU mask)
+                return "conv", 0
             if self.pool_in_training_conv and flags == CONV_RELU and self._conv3x3_choice(mod, 0, x.shape, flags) == ("winograd", 4):
                 return "conv+pool_both", 0
         if (not save and not split and kind in ("conv", "deconv") and follower == "add"
@@ -432,8 +454,9 @@ class DreamHourglass(nn.Module):
             raise ValueError("unknown precision %r" % (self.precision,))
         split = self.precision in _HALF_OPS and not save
         conv = {"fp16x3": self._conv_f16x3, "fp16": self._conv_f16}[self.precision] if split else self._conv_fp32
+        half = self._check_train_precision() and bool(save)
         layers = self.plan_layers()
-        saved, keep = [], {}
+        saved, keep = _Saved(), {}
         act, amax, li = x, x_amax, 0
         while li < len(layers):
             kind, mod, flags = layers[li]
@@ -441,7 +464,7 @@ class DreamHourglass(nn.Module):
                 outs = [ops.maxpool2(act)]                   # (pooling cannot raise the maximum: amax stays)
             elif kind == "add":
                 self._join(act, keep[flags])
-                out, amax = ops.add(act, keep[flags], want_amax=split)
+                out, amax = ops.add(act, keep[flags], want_amax=split or half)
                 outs = [out]
             else:
                 if kind == "wide" and not x_is_nhwc:
@@ -449,11 +472,19 @@ class DreamHourglass(nn.Module):
                         amax = ops.absmax(act)
                     act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
                 w, bias = params[self._param_slot[li]], params[self._param_slot[li] + 1]
-                group, sub = self._group(layers, li, act, save, split)
-                if group == "pair+pool":
+                half_entry = half and self._half_train_entry(kind, mod, flags, act.shape[3])
+                group, sub = self._group(layers, li, act, save, split, half_entry)
+                if half_entry:
+                    # the amax of the launch that produced ``act`` where it is still that tensor's, one absmax pass otherwise; it travels
+                    # with ``saved`` to the weight gradient
+                    saved.amax[li] = amax = amax if amax is not None else ops.absmax(act)
+                    outs = list(self._conv_f16(kind, mod, act, amax, w, bias, flags))
+                    amax = outs.pop()
+                elif group == "pair+pool":
                     outs = [None, None, self._first_pair_in_subbatches(layers, li, act, params, sub)]
                 elif group == "conv+pool_both":
                     outs = list(self._conv3x3(mod, 0, act, bias, flags=flags, pool_both=True))
+                    amax = None
                 else:
                     skip = keep[layers[li + 1][2]] if group == "conv+add" else None
                     out, amax = conv(kind, mod, act, amax, w, bias, flags | (CONV_POOL2 if group == "conv+pool" else 0), skip)
@@ -472,6 +503,8 @@ class DreamHourglass(nn.Module):
         multi-stage hourglass, dL/d(NHWC input of the "wide" first conv)).  ``reducer``: overlapped data-parallel
         all-reduce that is fed every gradient as soon as it exists."""
         layers = self.plan_layers()
+        self._check_train_precision()
+        g_amax = None                                      # amax scalar of g while g is still the tensor an fp16 launch wrote
         grads = _GradList(2 * len(self._param_slot), reducer)
         # weight gradients are leaves of the data-gradient chain: second stream when the batch is small (see _SideStream)
         sh = saved[0][0].shape                             # NCHW image ("first") or NHWC packed input ("wide")
@@ -496,8 +529,9 @@ class DreamHourglass(nn.Module):
                 _early_bucket_hook(reducer, early, side, lambda: list(grads[k_early:]))
                 early = None
             if li in pending:                              # two consumers of this activation: gradients add
-                g = ops.add_(g, pending.pop(li))
+                g, g_amax = ops.add_(g, pending.pop(li)), None
             if kind == "pool":
+                g_amax = None
                 masked = relu_feeds(li - 1)
                 g = ops.maxpool2_bwd(g, inp, relu=masked)
                 continue
@@ -519,13 +553,13 @@ class DreamHourglass(nn.Module):
                 packed_s2, rows_s2, _ = self._packed.get(mod.weight, "stride2")
                 g = ops.conv2d(g, packed_s2, rows_s2, 3, 2, None, None, inp if fuse else None,
                                ops.CONV_RELUMASK if fuse else 0)
-                masked = fuse
+                masked, g_amax = fuse, None
                 continue
             cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
             if flags & CONV_OUT_NCHW:
                 g = ops.nchw_to_nhwc(grad_out_nchw, cpad=ops.round_up(cout, 16))   # zero-padded K -> 16k channels
             if flags & CONV_RELU and not masked:
-                g = ops.relu_bwd_(g, out)
+                g, g_amax = ops.relu_bwd_(g, out), None
             masked = False
             if kind == "first":
                 grads[pi], grads[pi + 1] = ops.conv3x3_first_wgrad(inp, g)
@@ -538,6 +572,19 @@ class DreamHourglass(nn.Module):
                     g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
                 continue
+            if li in saved.amax:
+                # the forward ran this entry in half precision (it left the input's amax): both products of its backward on the fp16
+                # matrix cores too; one pass over g (or the amax of the launch that wrote it) serves both
+                g_amax = g_amax if g_amax is not None else ops.absmax(g)
+                x_amax = saved.amax[li]
+                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ax=x_amax, ag=g_amax):
+                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16(inp, ax, g, ag, cout, cin)
+                _on_side(side, leaf, inp, g, x_amax, g_amax)
+                p16 = self._packed.get(mod.weight, "f16", 1)       # transposed, flipped taps: the data-gradient operator
+                g, g_amax = ops.conv2d_f16(g, g_amax, p16, p16[3], 3, relu_mask=inp if fuse else None)
+                masked = fuse
+                continue
+            g_amax = None
             def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ups=flags & CONV_UPSAMPLE2X):
                 if (self.conv_algorithm == "winograd" and int(inp.shape[3]) == cin
                         and ops.wgrad_winograd_pays(int(g.shape[0]) * int(g.shape[1]) * int(g.shape[2]), cin, cout)
@@ -608,6 +655,16 @@ class DreamHourglass(nn.Module):
         if self.internalize_spatial_softmax:
             outputs.append(self.softmax[0](out))
         return outputs
+
+
+class _Saved(list):
+    """What DreamHourglass.run_forward hands to run_backward: the (input, output) pair of every plan entry, and ``amax``: plan index ->
+    the amax scalar of the input of each entry that ran in half precision (train_precision="fp16").  The forward decides which entries
+    those are; the backward runs exactly them in half precision."""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.amax = {}
 
 
 class _HourglassFunction(torch.autograd.Function):
@@ -1008,6 +1065,15 @@ class DreamHourglassMultiStage(nn.Module):
             st.precision = value
 
     @property
+    def train_precision(self):
+        return self.stage1.train_precision
+
+    @train_precision.setter
+    def train_precision(self, value):
+        for st in self.stages():
+            st.train_precision = value
+
+    @property
     def conv_algorithm(self):
         return self.stage1.conv_algorithm
 
@@ -1171,6 +1237,16 @@ class ResnetSimple(nn.Module):
         # models.py:22: resnet101(pretrained=pretrained) -- ImageNet trunk when it can be had, one loud warning otherwise.
         # ``freeze`` is accepted and unused, exactly as in the reference (models.py:19: never read).
         self.imagenet_initialised = _pretrained.init_resnet101_trunk(self) if pretrained else False
+
+    @property
+    def train_precision(self):
+        """Always "fp32": BatchNorm training on the fp16 matrix cores is not built (DreamHourglass.train_precision)."""
+        return "fp32"
+
+    @train_precision.setter
+    def train_precision(self, value):
+        if value != "fp32":
+            raise ValueError("ResnetSimple trains in fp32 only: train_precision=%r is not supported" % (value,))
 
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""

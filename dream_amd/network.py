@@ -243,6 +243,9 @@ class DreamNetwork:
                 raise RuntimeError("dream_amd: hip_graph_train needs the model behind DreamDataParallel (what DreamNetwork builds); this "
                                    "network's model is a %s" % type(self.model).__name__)
             return
+        if on and getattr(self.model.module, "train_precision", "fp32") != "fp32":
+            raise ValueError("dream_amd: hip_graph_train does not replay train_precision=%r steps; switch one of them off"
+                             % (self.model.module.train_precision,))
         self.model.single_device_graphs = bool(on)
 
     # ---- small getters (network.py:319-326) ------------------------------------------------------------

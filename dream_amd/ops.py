@@ -1448,13 +1448,20 @@ def pack_convT4x4_weight_f16(wT):
     return hi, None, exp, cout
 
 
-def conv2d_f16(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, residual=None, flags=0, want_amax=True):
-    """Half-precision conv (stride 1, fp16 operands, fp32 accumulation): returns (y, amax_out)."""
+def conv2d_f16(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, residual=None, flags=0, want_amax=True,
+               relu_mask=None):
+    """Half-precision conv (stride 1, fp16 operands, fp32 accumulation): returns (y, amax_out).  ``relu_mask`` (a tensor of the
+    output's shape; not with ``residual``): y = relu_mask > 0 ? conv : 0 and amax_out is taken after the mask -- with the mode-1
+    packed plane (transposed, flipped taps) the data gradient of a conv behind a ReLU."""
     hi, _, exp, _ = packed16
     x = _f32(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
     if cin != hi.shape[-1]:
         raise RuntimeError("conv2d_f16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    if relu_mask is not None:
+        if residual is not None or tuple(relu_mask.shape) != (b, h, w, cout):
+            raise RuntimeError("conv2d_f16: relu_mask must have the output's shape %s and excludes a residual" % ((b, h, w, cout),))
+        residual, flags = _f32(relu_mask), flags | CONV_RELUMASK
     if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
         h, w = 2 * h, 2 * w
     shape = (b, cout, h, w) if flags & CONV_OUT_NCHW else (b, h, w, cout)
@@ -1465,6 +1472,30 @@ def conv2d_f16(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, r
     call("dream_conv2d_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(residual), ptr(y),
          ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
     return y, amax_out
+
+
+def conv3x3_wgrad_f16_splitk(b, h, w, cin, cdy):
+    """Position slices the half-precision weight gradient of this problem is split into (a host computation: no GPU is touched)."""
+    return int(_hip.lib().dream_conv3x3_wgrad_f16_splitk(b, h, w, cin, round_up(cdy, 64)))
+
+
+def conv3x3_wgrad_f16(x_nhwc, amax_x, dy_nhwc, amax_dy, cout, cin, flags=0):
+    """Weight + bias gradient of a 3x3 stride-1 conv on the fp16 matrix cores (csrc/wgrad_f16.hip): both operands rounded once to
+    fp16(v * 2^e), e from their amax scalars, fp32 accumulation -> (dW OIHW [cout,cin,3,3], dbias [cout]), the contract of
+    conv3x3_wgrad.  dbias is the channel sum of the unrounded dy.  cin % 32 == 0; dy may carry padded channels (>= cout)."""
+    x, dy = _f32(x_nhwc), _f32(dy_nhwc)
+    b, h, w, cdy = (int(v) for v in dy.shape)
+    if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
+    rows_pad = round_up(cdy, 64)
+    ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
+    dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
+    dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
+    call("dream_conv3x3_wgrad_f16_nhwc_f32", ptr(x), ptr(amax_x), ptr(dy), ptr(amax_dy), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin,
+         cdy, rows_pad, flags, stream())
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
+    return dw, dbias[:cout].contiguous()
 
 
 def conv_transpose3x3s2_f16(x_nhwc, amax_in, packed16_mode1, cout, bias=None, relu=True):

@@ -285,7 +285,9 @@ int dream_conv_f16x3_set_variant(int variant);
  * y = epilogue(2^-(ea+ew) * sum fp16(x*2^ea) * fp16(w*2^ew)): ONE v_mfma_f32_32x32x16_f16 per product, with the split
  * path's power-of-two scales and amax side channel.  `w` is the `hi` plane written by dream_pack_conv_weight_f16x3 /
  * dream_pack_convT4x4_weight_f16x3 and `w_exp` their exp_out; every other argument is that of the _f16x3 sibling.
- * The operands carry 11 significant bits: an inference mode that trades last-digit accuracy for rate, not for training. */
+ * The operands carry 11 significant bits: last-digit accuracy traded for rate.  With DREAM_CONV_RELUMASK (dream_conv2d_f16_nhwc_f32
+ * only; `residual` is the mask: y = residual > 0 ? conv : 0, amax_out taken after it) and the mode-1 packed plane it is the data
+ * gradient of train_precision="fp16". */
 /* nn.Conv2d(k 1 | 3, stride 1) (+ folded BatchNorm / bias, residual, ReLU, MaxPool2d(2), fused nn.Upsample(2)):
  * dream/models.py:594-615 (VGG encoder), 695-747 (upsample decoder and heads), 22-32,138-148 (stride-1 ResNet bottleneck convs, head). */
 int dream_conv2d_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
@@ -468,6 +470,19 @@ size_t dream_conv3x3_wgrad_workspace(int B, int H, int W, int Cin, int CoutPad);
 int dream_conv3x3_wgrad_nhwc_f32(const float *x, const float *dy, float *dw_packed, float *dbias,
                                  void *workspace, int B, int H, int W, int Cin, int Cout,
                                  int CoutPad, int flags, void *stream);
+/* The same weight gradient on the fp16 matrix cores (train_precision="fp16"; replaces ATen's conv backward-weight reached from
+ * loss.backward(), dream/network.py:335, for the plain 3x3 stride-1 Conv2d layers of dream/models.py:594-615, 695-747):
+ * dW = 2^-(ex+eg) * sum fp16(dy*2^eg) * fp16(x*2^ex) with fp32 accumulation, both operands rounded once while they are staged;
+ * amax_x / amax_dy: device scalars with the bit pattern of (an upper bound of) max|x| / max|dy| (the amax side channel,
+ * dream_absmax_f32).  x [B,H,W,Cin], dy [B,H,W,Cdy] fp32 NHWC -> dw_packed [9][RowsPad][Cin] (mode-0 layout, overwritten),
+ * dbias [Cdy] (overwritten; may be NULL): the channel sums of the UNROUNDED dy.  Cin % 32 == 0, Cdy % 4 == 0, RowsPad >= Cdy a
+ * multiple of 64; flags must be 0.  Deterministic split-K: dream_conv3x3_wgrad_f16_splitk() slices of the positions (a host
+ * computation, no GPU needed), partials in `workspace` (dream_conv3x3_wgrad_f16_workspace() bytes), summed in a fixed order. */
+size_t dream_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin, int RowsPad);
+int dream_conv3x3_wgrad_f16_splitk(int B, int H, int W, int Cin, int RowsPad);
+int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
+                                     float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
+                                     int Cdy, int RowsPad, int flags, void *stream);
 /* The same weight gradient in the Winograd F(2x2,3x3) domain (16 instead of 36 multiplications per 2x2 outputs, fp32
  * throughout): dU_p = sum_tiles (A dY A^T)_p x (B^T d B)_p on the fp32 matrix cores, dW = G^T dU G, deterministic split-K.
  * x [B,H,W,Cin], dy [B,H,W,Cdy] (Cdy >= Cout, both multiples of 16), Cin % 64 == 0 -> dw_oihw [Cout,Cin,3,3] (OIHW,

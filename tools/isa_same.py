@@ -33,7 +33,8 @@ def kernels(asm_path):
     txt = open(asm_path).read()
     out = {}
     for m in re.finditer(r"^(_Z\w+):\s*;\s*@\1\n(.*?)^\.Lfunc_end\d+:", txt, re.S | re.M):
-        body = re.sub(r";.*", "", m.group(2))
+        body = re.sub(r"[ \t]*;.*", "", m.group(2))         # (with the padding in front of it: its width follows the label's digits)
+        body = re.sub(r"[ \t]+$", "", body, flags=re.M)
         body = re.sub(r"\.LBB\d+_", ".LBB_", body)
         body = re.sub(r"\.Ltmp\d+", ".Ltmp", body)
         out[m.group(1)] = (hashlib.md5(body.encode()).hexdigest()[:12], body.count("\n"))
