@@ -184,7 +184,7 @@ _SIGNATURES = {
     "dream_conv3x3_wgrad_winograd_set_version": (_I, [_I]),
     "dream_conv3x3_first_wgrad_workspace": (_SZ, [_I, _I, _I, _I, _I]),
     "dream_conv3x3_first_wgrad_f32": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
-    "dream_adam_step_f32": (_I, [_P, _P, _P, _P, _SZ, _F, _F, _F, _F, _I, _P]),
+    "dream_adam_step_f32": (_I, [_P, _P, _P, _P, _SZ, _F, _D, _D, _F, _I, _P]),
     "dream_sgd_step_f32": (_I, [_P, _P, _SZ, _F, _P]),
 }
 
@@ -227,7 +227,7 @@ def check_symbols():
     unbound = [n for n in declared if n not in _SIGNATURES]
     if missing or unbound:
         raise HipLibraryError("missing exports %s / unbound %s" % (missing, unbound))
-    if handle.dream_hip_abi_version() != 2:
+    if handle.dream_hip_abi_version() != 3:
         raise HipLibraryError("ABI version mismatch")
     return declared
 

@@ -14,6 +14,9 @@ namespace {
 
 constexpr int kMaxBlocks = 256 * 8;
 
+// add_kernel, add_inplace_kernel and relu_bwd_kernel cast their pointers to float4 unconditionally: the entry points refuse others
+inline bool aligned16(const void *a, const void *b, const void *c = nullptr) { return ((((size_t)a) | ((size_t)b) | ((size_t)c)) & 15) == 0; }
+
 inline unsigned grid_for(size_t work_items, int block = 256) {
     size_t g = ceil_div_sz(work_items, (size_t)block);
     if (g > (size_t)kMaxBlocks) g = kMaxBlocks;
@@ -381,11 +384,13 @@ __global__ void __launch_bounds__(256) smoothl1_kernel(const float *o, const flo
 // torch.optim.Adam defaults (no weight decay, no amsgrad):  m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2
 // p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 __global__ void __launch_bounds__(256) adam_kernel(float *p, const float *g, float *m, float *v, size_t n,
-                                                   float step_size, float inv_sqrt_bc2, float b1, float b2, float eps) {
+                                                   float step_size, float inv_sqrt_bc2, float w1, float b2, float w2, float eps) {
+    // w1 = (float)(1 - b1), w2 = (float)(1 - b2), the complements taken in double on the host as torch takes them: 1.0f - 0.999f is
+    // 0.0009999871, 1.3e-5 away from the 0.001f that torch.optim.Adam multiplies g^2 by
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);     // torch: lerp(m, g, 1-b1)
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
+        const float mi = m[i] + (gi - m[i]) * w1;              // torch: lerp(m, g, 1-b1)
+        const float vi = v[i] * b2 + w2 * gi * gi;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
@@ -770,6 +775,7 @@ extern "C" int dream_upsample2_bwd_nhwc_f32(const float *dy, float *dx, int B, i
 }
 extern "C" int dream_relu_bwd_f32(const float *dy, const float *y, float *dx, size_t n, void *stream) {
     DREAM_REQUIRE(dy && y && dx, "relu_bwd: null pointer");
+    DREAM_REQUIRE(aligned16(dy, y, dx), "relu_bwd: pointers must be 16-byte aligned (the kernel moves float4)");
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n);
     DREAM_LAUNCH_OK();
     return 0;
@@ -973,12 +979,14 @@ extern "C" int dream_copy_f32(float *dst, const float *src, size_t n, void *stre
 }
 extern "C" int dream_add_inplace_f32(float *dst, const float *src, size_t n, void *stream) {
     DREAM_REQUIRE(dst && src, "add_inplace: null pointer");
+    DREAM_REQUIRE(aligned16(dst, src), "add_inplace: pointers must be 16-byte aligned (the kernel moves float4)");
     hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
     DREAM_LAUNCH_OK();
     return 0;
 }
 extern "C" int dream_add_f32(const float *a, const float *b, float *out, size_t n, unsigned *amax_out, void *stream) {
     DREAM_REQUIRE(a && b && out, "add: null pointer");
+    DREAM_REQUIRE(aligned16(a, b, out), "add: pointers must be 16-byte aligned (the kernel moves float4)");
     if (amax_out && dream_zero_words(amax_out, sizeof(unsigned), (hipStream_t)stream)) return 2;
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, amax_out);
     DREAM_LAUNCH_OK();
@@ -1026,12 +1034,12 @@ extern "C" int dream_smoothl1_fwd_bwd_f32(const float *out, const float *target,
     DREAM_LAUNCH_OK();
     return 0;
 }
-extern "C" int dream_adam_step_f32(float *p, const float *g, float *m, float *v, size_t n, float lr, float beta1,
-                                   float beta2, float eps, int step, void *stream) {
+extern "C" int dream_adam_step_f32(float *p, const float *g, float *m, float *v, size_t n, float lr, double beta1,
+                                   double beta2, float eps, int step, void *stream) {
     DREAM_REQUIRE(p && g && m && v && step >= 1, "adam: bad arguments");
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps);
+                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
     DREAM_LAUNCH_OK();
     return 0;
 }

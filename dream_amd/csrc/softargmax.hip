@@ -1,10 +1,10 @@
-// SoftArgmaxPavlo.forward (/root/reference/dream/spatial_softmax.py:24-95):
+// SoftArgmaxPavlo.forward (dream/spatial_softmax.py:24-95):
 //   7x7 average pool (stride 1, zero pad 3, always /49) -> subtract the per-map max ->
 //   exp(beta_k * .) -> normalise by (sum + 1e-8) -> expected column (x) and row (y) index.
 // Two streaming kernels: (1) the pooled map, (2) one workgroup per map doing the max and the three
 // sums with wave-shuffle reductions (64-lane xor butterflies, then 4 partials through LDS).
 // fp32 throughout, like the reference; summation order differs from ATen's, so parity is
-// tolerance-based (1e-4 on the coordinates, tests/test_softargmax_gpu.py).
+// tolerance-based (1e-4 on the coordinates, tests/test_gpu_step_kernels.py).
 #include <dream_cdna4.h>
 #include "common.h"
 #include "../../include/dream_hip.h"

@@ -165,7 +165,7 @@ class HipAdam(_FlatStepMixin, torch.optim.Optimizer):
             if plan is not None and plan["span"] is not None and "moments" not in plan and not plan.get("per_tensor"):
                 if not self._adopt_moments(plan, params, plan["span"][1]):
                     plan["per_tensor"] = True
-            if plan is not None and plan["span"] is not None and "moments" in plan:
+            if plan is not None and plan["span"] is not None and "moments" in plan and not plan.get("per_tensor"):
                 flat, offs = plan["span"]
                 plan["step"] += 1
                 grad = self._flat_grad(plan, params)
@@ -179,6 +179,11 @@ class HipAdam(_FlatStepMixin, torch.optim.Optimizer):
                 if replicas_stepped:
                     dp.mark_params_synced()
                 continue
+            held = getattr(self, "_plan", None)
+            if held is not None and "moments" in held:
+                # a step that leaves a parameter out (its .grad is None) after flat steps: from here on the step counts differ, and
+                # the flat launch has ONE count for all -- the plan keeps to this path (the moments stay where they are: the views)
+                held["per_tensor"] = True
             for p in params:
                 if p.grad is None:
                     continue

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DREAM_HIP_ABI_VERSION 2
+#define DREAM_HIP_ABI_VERSION 3
 
 /* conv flags */
 #define DREAM_CONV_RELU        1   /* fuse ReLU into the epilogue (reference: nn.ReLU(inplace) after the conv) */
@@ -435,7 +435,7 @@ int dream_mse_fwd_bwd_f32(const float *out, const float *target, float *grad, fl
 /* SmoothL1Loss(beta 1, mean) = the "huber" loss type (dream/network.py:262-263,290-291): same contract as the MSE */
 int dream_smoothl1_fwd_bwd_f32(const float *out, const float *target, float *grad, float *loss_sum, void *workspace,
                                size_t n, double n_total, void *stream);
-/* elementwise ReLU backward on NHWC tensors: dx = dy * (y > 0) (inplace allowed) */
+/* elementwise ReLU backward on NHWC tensors: dx = dy * (y > 0) (inplace allowed); pointers 16-byte aligned, else an error */
 int dream_relu_bwd_f32(const float *dy, const float *y, float *dx, size_t n, void *stream);
 /* MaxPool2d(2) backward: dy [B,H/2,W/2,C], x [B,H,W,C] (forward input), dx [B,H,W,C];
  * gradient goes to the first maximal element in window scan order (ATen semantics). */
@@ -632,7 +632,7 @@ typedef struct dream_copy_chunk {
 } dream_copy_chunk;
 size_t dream_copy_chunk_bytes(void);
 int dream_multi_copy_f32(const void *srcs, const void *chunks, int nchunks, void *stream);
-/* dst += src (gradient accumulation where two branches meet) */
+/* dst += src (gradient accumulation where two branches meet); pointers 16-byte aligned, else an error */
 int dream_add_inplace_f32(float *dst, const float *src, size_t n, void *stream);
 /* dst[i] = src[i] with a kernel launch -- `tensor.clone()` for code that may be captured into a hipGraph (ATen copies contiguous tensors
  * with hipMemcpyAsync, which becomes a memcpy NODE there; round 6 found a replayed memset node out of order on this runtime and the
@@ -648,7 +648,8 @@ int dream_copy_f32(float *dst, const float *src, size_t n, void *stream);
 int dream_allreduce_sum_f32(int ndev, const int *devices, void *const *bufs, size_t count, void *const *streams);
 int dream_allreduce_uses_rccl(int ndev, const int *devices);
 /* out = a + b: the encoder skip tensors joining the decoder (`x_0_5 + x_0_4_d`, `y_0_5 + x_0_3_d`, ...,
- * dream/models.py:774-807).  amax_out (optional) receives the bit pattern of max|out| for the split-precision kernel. */
+ * dream/models.py:774-807).  amax_out (optional) receives the bit pattern of max|out| for the split-precision kernel.
+ * a, b and out must be 16-byte aligned (an error otherwise). */
 int dream_add_f32(const float *a, const float *b, float *out, size_t n, unsigned *amax_out, void *stream);
 /* Multi-stage hourglass input (dream/models.py:487-493,:500-553): torch.cat([x, F.interpolate(y_prev, scale_factor=up)], 1)
  * written straight into the NHWC layout the MFMA first conv of stage s>1 reads: img NCHW [B,Ci,H,W], maps NCHW
@@ -665,9 +666,10 @@ int dream_conv3x3_first_wgrad_f32(const float *x_nchw, const float *dy_nhwc, flo
                                   float *dbias, void *workspace, size_t workspace_bytes,
                                   int B, int H, int W, int Cin, int Cout, void *stream);
 /* torch.optim.Adam / SGD step with PyTorch defaults (dream/network.py:666-685) on one flat fp32
- * buffer: p, g, m, v of n elements; step is the 1-based step count. */
+ * buffer: p, g, m, v of n elements; step is the 1-based step count.  beta1 / beta2 are doubles (ABI 3): the weights
+ * (float)(1 - beta) of the new gradient are rounded from the double complement, as torch.optim.Adam rounds them. */
 int dream_adam_step_f32(float *p, const float *g, float *m, float *v, size_t n, float lr,
-                        float beta1, float beta2, float eps, int step, void *stream);
+                        double beta1, double beta2, float eps, int step, void *stream);
 int dream_sgd_step_f32(float *p, const float *g, size_t n, float lr, void *stream);
 
 #ifdef __cplusplus
