@@ -97,6 +97,12 @@ _SIGNATURES = {
     "dream_conv_transpose4x4s2_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv_transpose3x3s2_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv_f16_set_variant": (_I, [_I]),
+    "dream_conv2d_f16_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv_transpose4x4s2_f16_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv_transpose3x3s2_f16_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv3x3_first_nchw_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_maxpool2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "dream_add_f16": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "dream_bn_fold_f32": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _P]),
     "dream_im2col_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),

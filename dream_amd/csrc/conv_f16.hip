@@ -23,6 +23,7 @@ namespace {
 template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16Params p) {
     constexpr bool EPI_MASK = false;
+    constexpr bool ACT16 = false;
 #include "conv_f16_body.inc"
 }
 
@@ -31,6 +32,19 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16P
 template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Conv16Params p) {
     constexpr bool EPI_MASK = true;
+    constexpr bool ACT16 = false;
+#include "conv_f16_body.inc"
+}
+
+// The same kernel on activations stored as IEEE half (activation_storage="fp16"; the *_nhwc_f16 entry points): p.x and an NHWC p.y
+// are halfs.  The stored half IS the MFMA operand -- the patch is copied into LDS in 16-byte pieces of 8 halfs (half the load
+// instructions and bytes, no v_cvt, no multiply; on the `db` variants half the registers that hold the next chunk's patch), 2^-ew is
+// the whole output scale and amax_in is not read; the epilogue saturates, rounds and stores halfs (the NCHW output stays fp32).
+// Again a kernel of its own from the same text.
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_act16_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = false;
+    constexpr bool ACT16 = true;
 #include "conv_f16_body.inc"
 }
 
@@ -39,8 +53,9 @@ struct Variant16h {
     int BM, BN, NP_MAX, threads, abufs;
     void (*kernel)(const Conv16Params);
     void (*mask_kernel)(const Conv16Params);
+    void (*act16_kernel)(const Conv16Params);
 };
-#define F16_KERNELS(...) conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>
+#define F16_KERNELS(...) conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -55,14 +70,17 @@ const Variant16h kVariantsF16[] = {
 constexpr int kNumF16 = 8;
 int g_forced_f16 = -1;
 
-int launch_f16(const float *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
-               const float *residual, float *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
-               int flags, void *stream) {
-    DREAM_REQUIRE(x && amax_in && w && w_exp && y, "conv_f16: null pointer");
+// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used
+int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
+               const float *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
+               int flags, void *stream, bool act16 = false) {
+    DREAM_REQUIRE(x && (amax_in || act16) && w && w_exp && y, "conv_f16: null pointer");
+    DREAM_REQUIRE(!act16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
+    DREAM_REQUIRE(!act16 || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
     DREAM_REQUIRE(Cin % KC == 0, "conv_f16: Cin=%d must be a multiple of %d", Cin, KC);
     Conv16Params p;
-    p.x = x; p.w_hi = (const _Float16 *)w; p.w_lo = nullptr; p.w_exp = w_exp; p.amax_in = amax_in;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.y = y; p.amax_out = amax_out;
+    p.x = (const float *)x; p.w_hi = (const _Float16 *)w; p.w_lo = nullptr; p.w_exp = w_exp; p.amax_in = amax_in;
+    p.scale = scale; p.shift = shift; p.residual = residual; p.y = (float *)y; p.amax_out = amax_out;
     p.B = B;
     p.Cin = Cin; p.Cout = Cout; p.CoutPad = CoutPad;
     const long pixels = (long)B * g.H * g.W;
@@ -83,7 +101,7 @@ int launch_f16(const float *x, const unsigned *amax_in, const void *w, const int
     const bool mask = (flags & DREAM_CONV_RELUMASK) != 0;
     DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
-    void (*const kernel)(const Conv16Params) = mask ? var.mask_kernel : var.kernel;
+    void (*const kernel)(const Conv16Params) = act16 ? var.act16_kernel : (mask ? var.mask_kernel : var.kernel);
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
@@ -140,6 +158,47 @@ extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsi
     for (int ph = 0; ph < 4; ++ph) {
         const Geom16 g = geom16_convT3_phase(H, W, ph);
         if (int rc = launch_f16(x, amax_in, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
+            return rc;
+    }
+    return 0;
+}
+
+// ---- activations stored as IEEE half (activation_storage="fp16") -----------------------------------------------------------------
+// The siblings of the three entry points above (and of the 4x4 transposed conv an upsample + conv runs as) on half NHWC tensors:
+// x [B,H,W,Cin] half, y half NHWC -- fp32 NCHW with DREAM_CONV_OUT_NCHW --, same weight plane and exponent, no amax_in.
+// amax_out (optional) is NOT zeroed and may be shared by every launch of a forward pass: max|y| before the saturation.
+extern "C" int dream_conv2d_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                                         void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
+                                         int ksize, int stride, int flags, void *stream) {
+    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
+    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
+    return launch_f16(x, nullptr, w, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream, true);
+}
+
+extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                                      const float *shift, void *y, unsigned *amax_out, int B, int H, int W,
+                                                      int Cin, int Cout, int CoutPad, int flags, void *stream) {
+    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
+                  "convT4x4_f16: unsupported flags");
+    for (int ph = 0; ph < 4; ++ph) {
+        const Geom16 g = geom16_convT4_phase(H, W, ph);
+        const size_t off = (size_t)ph * 4 * CoutPad * Cin;
+        if (int rc = launch_f16(x, nullptr, (const _Float16 *)w + off, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout,
+                                CoutPad, g, flags, stream, true))
+            return rc;
+    }
+    return 0;
+}
+
+extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *bias, void *y,
+                                                      unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
+                                                      int flags, void *stream) {
+    DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16: only the ReLU flag is supported");
+    for (int ph = 0; ph < 4; ++ph) {
+        const Geom16 g = geom16_convT3_phase(H, W, ph);
+        if (int rc = launch_f16(x, nullptr, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream, true))
             return rc;
     }
     return 0;

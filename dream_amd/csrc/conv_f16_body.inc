@@ -1,9 +1,11 @@
 // Body of conv_f16_kernel / conv_f16_mask_kernel (conv_f16.hip), included once per kernel so that the plain kernels keep the machine code
 // that was measured (as conv_wino_body.inc).  In scope: the template parameters MR, NR, WM, WN, NPM, DB, PRIO, the argument p, and
-// EPI_MASK (bool constant: the DREAM_CONV_RELUMASK epilogue).
+// EPI_MASK (bool constant: the DREAM_CONV_RELUMASK epilogue) and ACT16 (bool constant: activations live in HBM as IEEE half --
+// p.x and an NHWC p.y point to halfs; the patch is copied, not converted: 16-byte pieces of 8 halfs, no input scale).
     constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
     constexpr int BN = 32 * NR * WN;
-    constexpr int Q = KC / 4;                       // float4 pieces per patch row
+    constexpr int QW = ACT16 ? 8 : 4;               // elements of a 16-byte piece
+    constexpr int Q = KC / QW;                      // 16-byte pieces per patch row
     constexpr int NA_IT = (NPM * Q + NT - 1) / NT;
     constexpr int NB_PIECES = BN * (KC / 8);        // 16-B pieces of the weight tile per stage
     constexpr int NB_IT = (NB_PIECES + NT - 1) / NT;
@@ -30,12 +32,16 @@
     const bool ups = (p.flags & DREAM_CONV_UPSAMPLE2X) != 0 || zst;
     const bool pool = (p.flags & DREAM_CONV_POOL2) != 0;
     const float *xb = p.x + (size_t)b * p.Hs * p.Ws * p.Cin;
+    const _Float16 *xh = (const _Float16 *)p.x + (size_t)b * p.Hs * p.Ws * p.Cin;     // (ACT16)
 
-    // input scale: max|x| * 2^ea in [2^13, 2^14)
-    const unsigned abits = *p.amax_in;
-    const int aexp = (int)((abits >> 23) & 255) - 127;
-    int ea = (abits == 0u) ? 0 : 13 - aexp;
-    ea = ea < -100 ? -100 : (ea > 100 ? 100 : ea);
+    // input scale: max|x| * 2^ea in [2^13, 2^14); stored halfs (ACT16) are the operand as they are: ea = 0, amax_in is not read
+    int ea = 0;
+    if constexpr (!ACT16) {
+        const unsigned abits = *p.amax_in;
+        const int aexp = (int)((abits >> 23) & 255) - 127;
+        ea = (abits == 0u) ? 0 : 13 - aexp;
+        ea = ea < -100 ? -100 : (ea > 100 ? 100 : ea);
+    }
     const float sa = pow2f(ea);
     const float inv = pow2f(-(ea + *p.w_exp) < -126 ? -126 : (-(ea + *p.w_exp) > 127 ? 127 : -(ea + *p.w_exp)));
 
@@ -44,12 +50,12 @@
     for (int it = 0; it < NA_IT; ++it) {
         const int idx = tid + it * NT;
         const int pp = idx / Q, q = idx % Q;
-        a_soff[it] = (pp < NP) ? pp * S16 + q * 4 : -1;
+        a_soff[it] = (pp < NP) ? pp * S16 + q * QW : -1;
         const int py = pp / PW, px = pp - py * PW;
         const int gy = y0 * p.in_scale - p.pad_y + py * p.in_step, gx = x0 * p.in_scale - p.pad_x + px * p.in_step;
         const bool inb = (pp < NP) && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win && !(zst && ((gy | gx) & 1));
         const int sy = ups ? (gy >> 1) : gy, sx = ups ? (gx >> 1) : gx;
-        a_goff[it] = inb ? (sy * p.Ws + sx) * p.Cin + q * 4 : -1;
+        a_goff[it] = inb ? (sy * p.Ws + sx) * p.Cin + q * QW : -1;
     }
     int b_goff[NB_IT], b_soff[NB_IT];
 #pragma unroll
@@ -81,24 +87,38 @@
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ms][ns][r] = 0.0f;
 
-    f32x4 a_reg[NA_IT];
+    f32x4 a_reg[ACT16 ? 1 : NA_IT];
+    f16x8 a_reg16[ACT16 ? NA_IT : 1];
     f16x8 b_reg[NB_IT];
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
     auto load_a = [&](int c0) {
+        if constexpr (ACT16) {
+            const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int it = 0; it < NA_IT; ++it)
-            a_reg[it] = (a_goff[it] >= 0) ? *(const f32x4 *)(xb + a_goff[it] + c0) : zero4;
+            for (int it = 0; it < NA_IT; ++it)
+                a_reg16[it] = (a_goff[it] >= 0) ? *(const f16x8 *)(xh + a_goff[it] + c0) : zero8;
+        } else {
+#pragma unroll
+            for (int it = 0; it < NA_IT; ++it)
+                a_reg[it] = (a_goff[it] >= 0) ? *(const f32x4 *)(xb + a_goff[it] + c0) : zero4;
+        }
     };
-    auto store_a = [&](int abuf) {     // the one rounding of the activations: fp16(v * 2^ea), to nearest even
+    auto store_a = [&](int abuf) {     // the one rounding of the activations: fp16(v * 2^ea), to nearest even (ACT16: none, a copy)
         _Float16 *d = sA + abuf * NP * S16;
+        if constexpr (ACT16) {
 #pragma unroll
-        for (int it = 0; it < NA_IT; ++it) {
-            if (a_soff[it] >= 0) {
-                f16x4 h;
+            for (int it = 0; it < NA_IT; ++it)
+                if (a_soff[it] >= 0) *(f16x8 *)(d + a_soff[it]) = a_reg16[it];
+        } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) h[k] = (_Float16)(a_reg[it][k] * sa);
-                *(f16x4 *)(d + a_soff[it]) = h;
+            for (int it = 0; it < NA_IT; ++it) {
+                if (a_soff[it] >= 0) {
+                    f16x4 h;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h[k] = (_Float16)(a_reg[it][k] * sa);
+                    *(f16x4 *)(d + a_soff[it]) = h;
+                }
             }
         }
     };

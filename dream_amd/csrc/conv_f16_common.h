@@ -4,6 +4,7 @@
 #pragma once
 #include <dream_cdna4.h>
 #include "common.h"
+#include "half_store.h"
 #include "../../include/dream_hip.h"
 
 struct Conv16Params {

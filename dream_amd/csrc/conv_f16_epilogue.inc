@@ -1,7 +1,10 @@
 // Epilogue of the implicit-GEMM kernels on the fp16 matrix cores, included at the end of conv_f16x3_kernel and conv_f16_kernel (one
 // text, and the split kernel's machine code stays what was measured).  In scope: p, acc[MR][NR], inv, wm, wn, li, lh, b, y0, x0, n0,
-// TW, pool, EPI_MASK (a bool constant).  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes
+// TW, pool, EPI_MASK and ACT16 (bool constants).  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes
 // max|y|.  EPI_MASK (conv_f16_mask_kernel only): `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it.
+// ACT16 (the half-storage kernels of conv_f16.hip): an NHWC y is IEEE half -- the same value, saturated to +-65504 and rounded to
+// nearest even (sat_half); max|y| is taken BEFORE the saturation, so the side channel tells a caller that it happened.  The NCHW
+// output (the K-channel belief maps) stays fp32.
     // ---- epilogue -----------------------------------------------------------------------------------------
     const bool relu = (p.flags & DREAM_CONV_RELU) != 0;
     const bool nchw = (p.flags & DREAM_CONV_OUT_NCHW) != 0;
@@ -16,8 +19,54 @@
     }
     const int npix = p.TH * TW;
     float amax = 0.0f;
+    bool stored = false;
+    // ACT16, NHWC, not pooled, even Cout: a lane owns one channel, so the plain store below is 2 bytes per lane.  Here the two lanes of
+    // a pair (channels 2j, 2j + 1) swap one of every two values (DPP quad_perm [1,0,3,2]): the even lane stores both channels of the
+    // first tile row of the two, the odd lane those of the second -- half the store instructions, 4 bytes per lane (+2 .. +9 % on the
+    // layer; the pooled form, a quarter of the stores to begin with, measured no gain and keeps the plain store:
+    // profiles/ab_act16_store.txt).  Every lane runs every exchange (the validity tests only guard the stores).
+    if constexpr (ACT16) {
+        if (!nchw && !pool && (p.Cout & 1) == 0) {
+            stored = true;
+            typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
+            _Float16 *yh = (_Float16 *)p.y;
+            const int odd = li & 1;
+#pragma unroll
+            for (int ms = 0; ms < MR; ++ms) {
+#pragma unroll
+                for (int r2 = 0; r2 < 8; ++r2) {                 // registers 2 r2, 2 r2 + 1: two tile rows
+                    bool ok[2];
+                    size_t pix[2];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int r = 2 * r2 + j;
+                        const int m = (wm * MR + ms) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int ty = (m * p.rcpTW) >> 16, tx = m - ty * TW;
+                        const int oy = (y0 + ty) * p.out_scale + p.out_oy, ox = (x0 + tx) * p.out_scale + p.out_ox;
+                        ok[j] = (m < npix) && (y0 + ty < p.H) && (x0 + tx < p.W) && oy < p.Ho && ox < p.Wo;
+                        pix[j] = ((size_t)b * p.Ho + oy) * p.Wo + ox;
+                    }
+#pragma unroll
+                    for (int ns = 0; ns < NR; ++ns) {
+                        const bool cok = ncol[ns] < p.Cout;
+                        float v[2];
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            v[j] = acc[ms][ns][2 * r2 + j] * scale_v[ns] + shift_v[ns];
+                            if (relu) v[j] = fmaxf(v[j], 0.0f);
+                            if (ok[j] && cok) amax = fmaxf(amax, fabsf(v[j]));
+                        }
+                        const float got = quad_perm_1032(odd ? v[0] : v[1]);
+                        const f16x2_ h = {sat_half(odd ? got : v[0]), sat_half(odd ? v[1] : got)};
+                        if (ok[odd] && cok) *(f16x2_ *)(yh + pix[odd] * p.Cout + (ncol[ns] & ~1)) = h;
+                    }
+                }
+            }
+        }
+    }
 #pragma unroll
     for (int ms = 0; ms < MR; ++ms) {
+        if (stored) break;
         if (!pool) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -35,7 +84,12 @@
                         if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
                         else if (p.residual != nullptr) v = v + p.residual[o];
                         if (relu) v = fmaxf(v, 0.0f);
-                        p.y[o] = v;
+                        if constexpr (ACT16) {
+                            if (nchw) p.y[o] = v;
+                            else ((_Float16 *)p.y)[o] = sat_half(v);
+                        } else {
+                            p.y[o] = v;
+                        }
                         amax = fmaxf(amax, fabsf(v));
                     }
                 }
@@ -59,7 +113,9 @@
                             if (relu) v = fmaxf(v, 0.0f);
                             best = fmaxf(best, v);
                         }
-                        p.y[(((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns]] = best;
+                        const size_t o = (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
+                        if constexpr (ACT16) ((_Float16 *)p.y)[o] = sat_half(best);
+                        else p.y[o] = best;
                         amax = fmaxf(amax, fabsf(best));
                     }
                 }

@@ -8,6 +8,7 @@
 // torch.optim.Adam / SGD dream/network.py:666-685.
 #include <dream_cdna4.h>
 #include "common.h"
+#include "half_store.h"
 #include "../../include/dream_hip.h"
 
 namespace {
@@ -657,6 +658,51 @@ __global__ void __launch_bounds__(256) add_kernel(const float *a, const float *b
     if (amax) publish_amax(amax, m);
 }
 
+// ---- activations stored as IEEE half (activation_storage="fp16"): 16 bytes = 8 halfs per lane -----------------------------------
+// max-pool 2x2 on halfs: the maximum of four halfs is one of them -- exact, no rounding, nothing to publish
+__global__ void __launch_bounds__(256) maxpool2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8) {
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t total = (size_t)B * Ho * Wo * C8;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        size_t r = i / C8;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const f16x8 *s = x + (((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c;
+        const f16x8 v00 = s[0], v01 = s[C8], v10 = s[(size_t)W * C8], v11 = s[(size_t)W * C8 + C8];
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (_Float16)fmaxf(fmaxf((float)v00[k], (float)v01[k]), fmaxf((float)v10[k], (float)v11[k]));
+        y[i] = o;
+    }
+}
+
+// out = half(a + b): the fp32 sum of two halfs (exact but for the one rounding of the add), saturated to +-65504, rounded to nearest
+// even; publishes max|a + b| before the saturation
+__global__ void __launch_bounds__(256) add_f16_kernel(const _Float16 *a, const _Float16 *b, _Float16 *out, size_t n, unsigned *amax) {
+    const size_t n8 = n / 8;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+        const f16x8 u = ((const f16x8 *)a)[i], v = ((const f16x8 *)b)[i];
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float t = (float)u[k] + (float)v[k];
+            m = fmaxf(m, fabsf(t));
+            o[k] = sat_half(t);
+        }
+        ((f16x8 *)out)[i] = o;
+    }
+    for (size_t i = n8 * 8 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float t = (float)a[i] + (float)b[i];
+        m = fmaxf(m, fabsf(t));
+        out[i] = sat_half(t);
+    }
+    if (amax) publish_amax(amax, m);
+}
+
 // Multi-stage input (dream/models.py:487-493): NHWC [B,H,W,Cpad] <- cat(image NCHW [B,Ci,H,W], maps NCHW [B,K,H/up,W/up]
 // nearest-upsampled by `up`), channels >= Ci+K zero.  One thread per (pixel, channel quad).
 __global__ void __launch_bounds__(256) stage_input_kernel(const float *img, const float *maps, float *out, int B, int H, int W,
@@ -708,6 +754,15 @@ extern "C" int dream_maxpool2_nhwc_f32(const float *x, float *y, int B, int H, i
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                        (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_maxpool2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_f16: bad arguments (C=%d must be a multiple of 8)", C);
+    DREAM_REQUIRE(aligned16(x, y), "maxpool2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
+    hipLaunchKernelGGL(maxpool2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
     DREAM_LAUNCH_OK();
     return 0;
 }
@@ -989,6 +1044,14 @@ extern "C" int dream_add_f32(const float *a, const float *b, float *out, size_t 
     DREAM_REQUIRE(aligned16(a, b, out), "add: pointers must be 16-byte aligned (the kernel moves float4)");
     if (amax_out && dream_zero_words(amax_out, sizeof(unsigned), (hipStream_t)stream)) return 2;
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, amax_out);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_add_f16(const void *a, const void *b, void *out, size_t n, unsigned *amax_out, void *stream) {
+    DREAM_REQUIRE(a && b && out, "add_f16: null pointer");
+    DREAM_REQUIRE(aligned16(a, b, out), "add_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    hipLaunchKernelGGL(add_f16_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream,
+                       (const _Float16 *)a, (const _Float16 *)b, (_Float16 *)out, n, amax_out);
     DREAM_LAUNCH_OK();
     return 0;
 }

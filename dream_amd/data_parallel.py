@@ -130,7 +130,7 @@ def _buffer_stamp(module):
 
 
 def _settings(module):
-    return tuple(getattr(module, a, None) for a in ("precision", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"))
+    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"))
 
 
 class _Busy:
@@ -430,7 +430,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
+            for attr in ("precision", "activation_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))
         src = self.module._dream_flat
@@ -638,6 +638,7 @@ class DreamDataParallel(nn.Module):
         """-> (outs[i] = list of output tensors of replica i (+ post(outs) appended when given), ctxs, chunk sizes)."""
         with self._lock:
             n = self.n_devices(x.shape[0])
+            object.__setattr__(self, "_last_shards", n)
             self._ensure_replicas(n)
             self._sync_replicas(n)
             xs = self._scatter(x, n)
@@ -776,7 +777,14 @@ class DreamDataParallel(nn.Module):
         object.__setattr__(self, "_pstamp", _param_stamp(self.module))
 
     # ---- nn.Module interface ------------------------------------------------------------------------------------------------
+    def half_storage_peak(self):
+        """DreamHourglass.half_storage_peak() of the last forward over every replica that took a chunk of it: the largest value any
+        device wanted to store with activation_storage="fp16" (>= 65504: that forward saturated somewhere)."""
+        n = getattr(self, "_last_shards", 1)
+        return max(m.half_storage_peak() for m in [self.module] + list(self._replicas[:n - 1]))
+
     def forward(self, x, *args, **kwargs):
+        object.__setattr__(self, "_last_shards", 1)
         if args or kwargs:
             return self.module(x, *args, **kwargs)
         one = self.n_devices(x.shape[0]) == 1

@@ -192,6 +192,12 @@ class DreamHourglass(nn.Module):
         # operands rounded to fp16, one MFMA per product, fp32 accumulation: belief maps move by about 1e-3 .. 3e-3).
         # Training uses the fp32 kernels whatever ``precision`` says.
         self.precision = "fp32"
+        # Inference with precision="fp16" only: "fp16" = the activations between the convs live in HBM as plain IEEE half (saturated to
+        # +-65504, round to nearest even; csrc/conv_f16.hip ACT16) -- half the activation traffic and footprint; the
+        # image and the belief maps stay fp32.  "fp32" (default): today's walk.  Training ignores it.  See half_storage_peak().
+        self.activation_storage = "fp32"
+        self._half_peaks = {}                # device -> the walk's peak scalar: ONE persistent tensor, zeroed in place by every half-storage
+        self._half_peak = None               # forward (so every captured hipGraph of this module writes the scalar that is read); the last one used
         # Training: "fp32", or "fp16" = the plain convs (_half_train_entry) run their forward, data-gradient and weight-gradient products
         # on the fp16 matrix cores (conv_f16.hip, wgrad_f16.hip: fp32 tensors in HBM, operands rounded once while staged, per-tensor
         # power-of-two scales from the amax side channel); every other plan entry keeps its fp32 launches.  Does not affect inference.
@@ -418,6 +424,34 @@ class DreamHourglass(nn.Module):
         p16 = self._packed.get(mod.weight, sfx, 0)
         return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
 
+    def _conv_act16(self, kind, mod, x, amax, w, bias, flags, skip=None):
+        """One conv entry of the plan with activation_storage="fp16" -> (y, None): the launches of _conv_half("f16", ...) on half
+        tensors.  Same packed forms ("f16", "ups_f16"); no amax travels (the stored half is the operand), every launch atomicMaxes
+        what it wanted to store into the walk's one peak scalar instead.  The 3-channel first conv keeps its fp32 VALU arithmetic."""
+        peak = self._half_peak
+        if kind == "first":
+            return ops.conv3x3_first_f16(x, w, bias, relu=bool(flags & CONV_RELU), peak=peak), None
+        if kind == "wide":
+            raise ValueError("activation_storage=\"fp16\" is built for the 3-channel first conv only (a multi-stage hourglass stages "
+                             "its later inputs in fp32)")
+        if flags & CONV_UPSAMPLE2X:
+            pk4 = self._packed.get(mod.weight, "ups_f16")
+            return ops.conv_transpose4x4s2_f16_act16(x, pk4, pk4[3], None, bias, flags & CONV_RELU, peak=peak), None
+        if kind == "deconv":
+            p16 = self._packed.get(mod.weight, "f16", 1)
+            return ops.conv_transpose3x3s2_f16_act16(x, p16, p16[3], bias, relu=bool(flags & CONV_RELU), peak=peak), None
+        p16 = self._packed.get(mod.weight, "f16", 0)
+        return ops.conv2d_f16_act16(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
+
+    def half_storage_peak(self):
+        """The largest |value|, before saturation, that any launch of the last forward with activation_storage="fp16" wanted to store
+        as a half (this module's own forward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_storage_peak(), which takes the
+        maximum over the replicas).  >= 65504: that forward saturated -- go back
+        to activation_storage="fp32".  Reading it is the mode's only host synchronisation, and happens only here."""
+        if self._half_peak is None:
+            raise RuntimeError("half_storage_peak(): no forward with activation_storage=\"fp16\" has run")
+        return float(self._half_peak.cpu().view(torch.float32)[0])
+
     def _conv_f16x3(self, kind, mod, x, amax, w, bias, flags, skip=None):
         """... on the split-precision kernels (three MFMAs per product, fp32-class error)."""
         return self._conv_half("f16x3", kind, mod, x, amax, w, bias, flags)
@@ -452,8 +486,22 @@ class DreamHourglass(nn.Module):
         self._check_input(x, x_is_nhwc)
         if self.precision != "fp32" and self.precision not in _HALF_OPS:
             raise ValueError("unknown precision %r" % (self.precision,))
+        if self.activation_storage not in ("fp32", "fp16"):
+            raise ValueError("unknown activation_storage %r (\"fp32\" or \"fp16\")" % (self.activation_storage,))
         split = self.precision in _HALF_OPS and not save
+        act16 = self.activation_storage == "fp16" and not save           # (read once per forward, as ``precision``)
+        if act16 and self.precision != "fp16":
+            raise ValueError("activation_storage=\"fp16\" needs precision=\"fp16\" (precision is %r)" % (self.precision,))
         conv = {"fp16x3": self._conv_f16x3, "fp16": self._conv_f16}[self.precision] if split else self._conv_fp32
+        if act16:
+            if x_is_nhwc:
+                raise ValueError("activation_storage=\"fp16\" takes the NCHW image (precision=\"fp16\"), not a staged NHWC input")
+            conv = self._conv_act16
+            self._half_peak = self._half_peaks.get(x.device)
+            if self._half_peak is None:
+                self._half_peak = self._half_peaks[x.device] = ops.new_amax(x.device)
+            else:
+                self._half_peak.zero_()
         half = self._check_train_precision() and bool(save)
         layers = self.plan_layers()
         saved, keep = _Saved(), {}
@@ -461,13 +509,16 @@ class DreamHourglass(nn.Module):
         while li < len(layers):
             kind, mod, flags = layers[li]
             if kind == "pool":
-                outs = [ops.maxpool2(act)]                   # (pooling cannot raise the maximum: amax stays)
+                outs = [ops.maxpool2_f16(act) if act16 else ops.maxpool2(act)]    # (pooling cannot raise the maximum: amax stays)
             elif kind == "add":
                 self._join(act, keep[flags])
-                out, amax = ops.add(act, keep[flags], want_amax=split or half)
+                if act16:
+                    out = ops.add_f16(act, keep[flags], peak=self._half_peak)
+                else:
+                    out, amax = ops.add(act, keep[flags], want_amax=split or half)
                 outs = [out]
             else:
-                if kind == "wide" and not x_is_nhwc:
+                if kind == "wide" and not x_is_nhwc and not act16:
                     if split:
                         amax = ops.absmax(act)
                     act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
@@ -1065,6 +1116,16 @@ class DreamHourglassMultiStage(nn.Module):
             st.precision = value
 
     @property
+    def activation_storage(self):
+        """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.activation_storage)."""
+        return "fp32"
+
+    @activation_storage.setter
+    def activation_storage(self, value):
+        if value != "fp32":
+            raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
+
+    @property
     def train_precision(self):
         return self.stage1.train_precision
 
@@ -1247,6 +1308,17 @@ class ResnetSimple(nn.Module):
     def train_precision(self, value):
         if value != "fp32":
             raise ValueError("ResnetSimple trains in fp32 only: train_precision=%r is not supported" % (value,))
+
+    @property
+    def activation_storage(self):
+        """Always "fp32": the stride-2 trunk convs, the 3x3 max-pool and the 4x4 transposed convs read and write fp32
+        (DreamHourglass.activation_storage)."""
+        return "fp32"
+
+    @activation_storage.setter
+    def activation_storage(self, value):
+        if value != "fp32":
+            raise ValueError("ResnetSimple stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
 
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""

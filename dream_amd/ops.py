@@ -1523,6 +1523,87 @@ def conv_transpose4x4s2_f16(x_nhwc, amax_in, packed16, cout, scale=None, shift=N
     return y, amax_out
 
 
+# ---- half-precision inference with the activations stored as IEEE half (activation_storage="fp16") -----------------
+# torch.float16 NHWC tensors in and out (the K-channel NCHW output stays fp32); a stored value is half(clamp(v, +-65504)).  ``peak``
+# (optional, new_amax()): ONE scalar every launch of a forward pass atomicMaxes max|v| before the saturation into; never zeroed here.
+def _f16(t):
+    if t.dtype != torch.float16:
+        raise RuntimeError("dream_amd: expected float16, got %s" % t.dtype)
+    return t.contiguous()
+
+
+def conv2d_f16_act16(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flags=0, peak=None):
+    """conv2d_f16 on half activations (stride 1; no residual, no ReLU mask) -> y: torch.float16 NHWC, float32 with CONV_OUT_NCHW."""
+    hi, _, exp, _ = packed16
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv2d_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
+        h, w = 2 * h, 2 * w
+    if flags & CONV_POOL2:
+        y = torch.empty((b, h // 2, w // 2, cout), dtype=torch.float16, device=x.device)
+    elif flags & CONV_OUT_NCHW:
+        y = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device)
+    else:
+        y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv2d_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), b, h, w, cin, cout,
+         int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y
+
+
+def conv_transpose3x3s2_f16_act16(x_nhwc, packed16_mode1, cout, bias=None, relu=True, peak=None):
+    hi, _, exp, _ = packed16_mode1
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv_transpose3x3s2_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv_transpose3x3s2_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(bias), ptr(y), ptr(peak), b, h, w, cin, cout,
+         int(hi.shape[-2]), CONV_RELU if relu else 0, stream())
+    return y
+
+
+def conv_transpose4x4s2_f16_act16(x_nhwc, packed16, cout, scale=None, shift=None, flags=0, peak=None):
+    hi, _, exp, _ = packed16
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv_transpose4x4s2_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv_transpose4x4s2_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), b, h, w, cin,
+         cout, int(hi.shape[-2]), flags, stream())
+    return y
+
+
+def conv3x3_first_f16(x_nchw, w_oihw, bias, relu=True, peak=None):
+    """conv3x3_first (fp32 image, fp32 arithmetic) storing torch.float16 NHWC."""
+    x, w = _f32(x_nchw), _f32(w_oihw)
+    b, cin, h, wd = (int(v) for v in x.shape)
+    cout = int(w.shape[0])
+    y = torch.empty((b, h, wd, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv3x3_first_nchw_f16", ptr(x), ptr(w), ptr(bias), ptr(y), ptr(peak), b, h, wd, cin, cout, 1 if relu else 0, stream())
+    return y
+
+
+def maxpool2_f16(x_nhwc):
+    x = _f16(x_nhwc)
+    b, h, w, c = (int(v) for v in x.shape)
+    y = torch.empty((b, h // 2, w // 2, c), dtype=torch.float16, device=x.device)
+    call("dream_maxpool2_nhwc_f16", ptr(x), ptr(y), b, h, w, c, stream())
+    return y
+
+
+def add_f16(a, b, peak=None):
+    """half(clamp(float(a) + float(b)))."""
+    a, b = _f16(a), _f16(b)
+    if a.shape != b.shape:
+        raise RuntimeError("add_f16: shapes %s and %s differ" % (tuple(a.shape), tuple(b.shape)))
+    out = torch.empty_like(a)
+    call("dream_add_f16", ptr(a), ptr(b), ptr(out), a.numel(), ptr(peak), stream())
+    return out
+
+
 def conv2d_amax(x_nhwc, packed, cout, ksize, stride=1, scale=None, shift=None, residual=None, flags=0):
     """fp32 MFMA conv that also publishes max|y| (feeds the split-precision kernel's input scaling)."""
     x = _f32(x_nhwc)

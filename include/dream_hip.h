@@ -306,6 +306,33 @@ int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsigned *amax_
                                            const float *bias, float *y, unsigned *amax_out, int B, int H, int W,
                                            int Cin, int Cout, int CoutPad, int flags, void *stream);
 int dream_conv_f16_set_variant(int variant);   /* -1 = the measured rule; otherwise index into the fp16 variant table */
+/* ---- half-precision inference with the activations stored as IEEE half (DreamHourglass.activation_storage = "fp16") ---
+ * The storage type is the suffix: x and an NHWC y are halfs [B,H,W,C] (void *: 2 bytes per element, 16-byte aligned), the
+ * belief maps (DREAM_CONV_OUT_NCHW) stay fp32.  A stored value is half(clamp(v, +-65504)): round to nearest even, never
+ * inf, subnormals kept.  The stored half IS the matrix-core operand: no amax_in, no input scale; `w` / `w_exp` are those
+ * of the _nhwc_f32 siblings; accumulation is fp32.  No residual, no ReLU mask.  amax_out (optional) is atomicMax'ed and
+ * NOT zeroed, so every launch of a forward pass may share one scalar: the largest |v| BEFORE the saturation (>= 65504:
+ * the pass saturated).  Same kernels, tiles and variant table (dream_conv_f16_set_variant) as the _nhwc_f32 siblings.
+ * Reference call sites: dream/models.py:594-615, 695-747 (convs, nn.Upsample + conv with DREAM_CONV_UPSAMPLE2X). */
+int dream_conv2d_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                              void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
+                              int ksize, int stride, int flags, void *stream);
+/* nn.Upsample(x2) + 3x3 conv as the equivalent ConvTranspose2d(k4,s2,p1) (dream/models.py:691-705); plane from
+ * dream_pack_convT4x4_weight_f16x3. */
+int dream_conv_transpose4x4s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                           const float *shift, void *y, unsigned *amax_out, int B, int H, int W,
+                                           int Cin, int Cout, int CoutPad, int flags, void *stream);
+/* nn.ConvTranspose2d(k3,s2,p1,output_padding 1) (+ReLU) of the deconvolution decoder (dream/models.py:618-686). */
+int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *bias, void *y,
+                                           unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
+                                           int flags, void *stream);
+/* first encoder conv (dream/models.py:592-597): the fp32 arithmetic of dream_conv3x3_first_nchw_amax_f32, y half NHWC */
+int dream_conv3x3_first_nchw_f16(const float *x_nchw, const float *w_oihw, const float *bias, void *y_nhwc,
+                                 unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int relu, void *stream);
+/* nn.MaxPool2d(2) (dream/models.py:589,765-771) on halfs: exact.  C % 8 == 0 */
+int dream_maxpool2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream);
+/* skip sums (dream/models.py:774-807) on halfs: out = half(clamp(float(a) + float(b))); amax_out as above (not zeroed) */
+int dream_add_f16(const void *a, const void *b, void *out, size_t n, unsigned *amax_out, void *stream);
 /* variant selection for benchmarking: -1 = heuristic; otherwise index into the variant table */
 int dream_conv3x3_set_variant(int variant);
 int dream_conv3x3_num_variants(void);
