@@ -24,6 +24,7 @@ template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16Params p) {
     constexpr bool EPI_MASK = false;
     constexpr bool ACT16 = false;
+    constexpr bool MASK16 = false;
 #include "conv_f16_body.inc"
 }
 
@@ -33,6 +34,7 @@ template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Conv16Params p) {
     constexpr bool EPI_MASK = true;
     constexpr bool ACT16 = false;
+    constexpr bool MASK16 = false;
 #include "conv_f16_body.inc"
 }
 
@@ -45,6 +47,17 @@ template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_act16_kernel(const Conv16Params p) {
     constexpr bool EPI_MASK = false;
     constexpr bool ACT16 = true;
+    constexpr bool MASK16 = false;
+#include "conv_f16_body.inc"
+}
+
+// conv_f16_mask_kernel with the mask tensor stored as IEEE half (train_activation_storage="fp16": the saved output of the conv in
+// front is half): `residual` points to halfs, y = mask > 0 ? conv : 0.  x, y and amax_out are as in conv_f16_mask_kernel.
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask16_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = true;
+    constexpr bool ACT16 = false;
+    constexpr bool MASK16 = true;
 #include "conv_f16_body.inc"
 }
 
@@ -54,8 +67,10 @@ struct Variant16h {
     void (*kernel)(const Conv16Params);
     void (*mask_kernel)(const Conv16Params);
     void (*act16_kernel)(const Conv16Params);
+    void (*mask16_kernel)(const Conv16Params);
 };
-#define F16_KERNELS(...) conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>
+#define F16_KERNELS(...) \
+    conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>, conv_f16_mask16_kernel<__VA_ARGS__>
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -70,10 +85,10 @@ const Variant16h kVariantsF16[] = {
 constexpr int kNumF16 = 8;
 int g_forced_f16 = -1;
 
-// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used
+// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used; mask16: the ReLU mask (`residual`) is a half tensor
 int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
                const float *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
-               int flags, void *stream, bool act16 = false) {
+               int flags, void *stream, bool act16 = false, bool mask16 = false) {
     DREAM_REQUIRE(x && (amax_in || act16) && w && w_exp && y, "conv_f16: null pointer");
     DREAM_REQUIRE(!act16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
     DREAM_REQUIRE(!act16 || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
@@ -101,7 +116,8 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     const bool mask = (flags & DREAM_CONV_RELUMASK) != 0;
     DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
-    void (*const kernel)(const Conv16Params) = act16 ? var.act16_kernel : (mask ? var.mask_kernel : var.kernel);
+    DREAM_REQUIRE(!mask16 || (mask && !act16), "conv_f16: a half mask goes with DREAM_CONV_RELUMASK on fp32 activations");
+    void (*const kernel)(const Conv16Params) = act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel);
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
@@ -131,6 +147,21 @@ extern "C" int dream_conv2d_f16_nhwc_f32(const float *x, const unsigned *amax_in
     DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
     const Geom16 g = geom16_conv(H, W, ksize, flags);
     return launch_f16(x, amax_in, w, w_exp, scale, shift, residual, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+}
+
+// dream_conv2d_f16_nhwc_f32 with DREAM_CONV_RELUMASK (set here) and the mask stored as IEEE half (train_activation_storage="fp16"):
+// y = mask > 0 ? conv : 0, fp32 NHWC; amax_out = max|y| after the mask.  mask [B,H,W,Cout] half.
+extern "C" int dream_conv2d_f16_mask16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                                const float *scale, const float *shift, const void *mask, float *y,
+                                                unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
+                                                int stride, int flags, void *stream) {
+    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
+    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    DREAM_REQUIRE(mask != nullptr && !(flags & DREAM_CONV_UPSAMPLE2X), "conv2d_f16_mask16: needs the mask, takes no upsample");
+    flags |= DREAM_CONV_RELUMASK;
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
+    return launch_f16(x, amax_in, w, w_exp, scale, shift, (const float *)mask, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream,
+                      false, true);
 }
 
 // ConvTranspose2d(k=4,s=2,p=1) on the fp16 path: the four 2x2-tap sub-pixel phases of dream_conv_transpose4x4s2_f16x3_nhwc_f32.

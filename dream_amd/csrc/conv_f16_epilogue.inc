@@ -1,7 +1,8 @@
 // Epilogue of the implicit-GEMM kernels on the fp16 matrix cores, included at the end of conv_f16x3_kernel and conv_f16_kernel (one
 // text, and the split kernel's machine code stays what was measured).  In scope: p, acc[MR][NR], inv, wm, wn, li, lh, b, y0, x0, n0,
 // TW, pool, EPI_MASK and ACT16 (bool constants).  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes
-// max|y|.  EPI_MASK (conv_f16_mask_kernel only): `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it.
+// max|y|.  EPI_MASK (conv_f16_mask_kernel only): `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it;
+// MASK16 (conv_f16_mask16_kernel): that mask is a tensor of IEEE halfs.
 // ACT16 (the half-storage kernels of conv_f16.hip): an NHWC y is IEEE half -- the same value, saturated to +-65504 and rounded to
 // nearest even (sat_half); max|y| is taken BEFORE the saturation, so the side channel tells a caller that it happened.  The NCHW
 // output (the K-channel belief maps) stays fp32.
@@ -81,7 +82,8 @@
                             ? (((size_t)b * p.Cout + ncol[ns]) * p.Ho + oy) * p.Wo + ox
                             : (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
                         float v = acc[ms][ns][r] * scale_v[ns] + shift_v[ns];
-                        if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
+                        if constexpr (EPI_MASK && MASK16) v = (float)((const _Float16 *)p.residual)[o] > 0.0f ? v : 0.0f;
+                        else if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
                         else if (p.residual != nullptr) v = v + p.residual[o];
                         if (relu) v = fmaxf(v, 0.0f);
                         if constexpr (ACT16) {

@@ -703,6 +703,62 @@ __global__ void __launch_bounds__(256) add_f16_kernel(const _Float16 *a, const _
     if (amax) publish_amax(amax, m);
 }
 
+// ---- training with the saved activations stored as IEEE half (train_activation_storage="fp16") -------------------------------------
+// maxpool2_bwd_kernel with a half forward input: dy and dx stay fp32, x is read as four halfs (8 bytes) per lane and window element.
+// A half compares as its fp32 value, so the first maximum in window scan order -- and the RELU mask -- are those of the fp32 kernel on
+// the widened x; leftover rows / columns of odd extents get zero the same way.
+template <bool RELU>
+__global__ void __launch_bounds__(256) maxpool2_bwd_x16_kernel(const f32x4 *dy, const f16x4 *x, f32x4 *dx, int B, int H, int W, int C4) {
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t total = (size_t)B * Ho * Wo * C4;
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        size_t r = i / C4;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c, row = (size_t)W * C4;
+        const f16x4 v[4] = {x[base], x[base + C4], x[base + row], x[base + row + C4]};
+        const f32x4 g = dy[i];
+        f32x4 o[4] = {zero, zero, zero, zero};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int arg = 0;
+            float best = (float)v[0][k];
+#pragma unroll
+            for (int j = 1; j < 4; ++j)
+                if ((float)v[j][k] > best) { best = (float)v[j][k]; arg = j; }
+            const float gk = (!RELU || best > 0.0f) ? g[k] : 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : 0.0f;
+        }
+        dx[base] = o[0];
+        dx[base + C4] = o[1];
+        dx[base + row] = o[2];
+        dx[base + row + C4] = o[3];
+        const bool last_x = (ox == Wo - 1) && (W & 1), last_y = (oy == Ho - 1) && (H & 1);
+        if (last_x) { dx[base + 2 * C4] = zero; dx[base + row + 2 * C4] = zero; }
+        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + C4] = zero; }
+        if (last_x && last_y) dx[base + 2 * row + 2 * C4] = zero;
+    }
+}
+
+// out = float(x): the widening pass behind the last half-storage conv of a training forward (exact); 8 halfs per lane
+__global__ void __launch_bounds__(256) widen_f16_kernel(const _Float16 *x, float *out, size_t n) {
+    const size_t n8 = n / 8;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+        const f16x8 v = ((const f16x8 *)x)[i];
+        f32x4 lo, hi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { lo[k] = (float)v[k]; hi[k] = (float)v[4 + k]; }
+        ((f32x4 *)out)[2 * i] = lo;
+        ((f32x4 *)out)[2 * i + 1] = hi;
+    }
+    for (size_t i = n8 * 8 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = (float)x[i];
+}
+
 // Multi-stage input (dream/models.py:487-493): NHWC [B,H,W,Cpad] <- cat(image NCHW [B,Ci,H,W], maps NCHW [B,K,H/up,W/up]
 // nearest-upsampled by `up`), channels >= Ci+K zero.  One thread per (pixel, channel quad).
 __global__ void __launch_bounds__(256) stage_input_kernel(const float *img, const float *maps, float *out, int B, int H, int W,
@@ -779,6 +835,33 @@ extern "C" int dream_maxpool2_relu_bwd_nhwc_f32(const float *dy, const float *x,
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool2_bwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                        (const f32x4 *)dy, (const f32x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+// ... with the forward input x stored as IEEE half (train_activation_storage="fp16"): dy, dx fp32; x [B,H,W,C] half, 8-byte aligned
+extern "C" int dream_maxpool2_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0, "maxpool2_bwd_x16: bad arguments");
+    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 7) == 0, "maxpool2_bwd_x16: dy, dx must be 16-byte and x 8-byte aligned");
+    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(maxpool2_bwd_x16_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const f32x4 *)dy, (const f16x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_maxpool2_relu_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0, "maxpool2_relu_bwd_x16: bad arguments");
+    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 7) == 0, "maxpool2_relu_bwd_x16: dy, dx must be 16-byte and x 8-byte aligned");
+    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(maxpool2_bwd_x16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const f32x4 *)dy, (const f16x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+// out[i] = float(x[i]), i < n: x half, out fp32, both 16-byte aligned
+extern "C" int dream_widen_f16_f32(const void *x, float *out, size_t n, void *stream) {
+    DREAM_REQUIRE(x && out, "widen_f16: null pointer");
+    DREAM_REQUIRE(aligned16(x, out), "widen_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    hipLaunchKernelGGL(widen_f16_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x, out, n);
     DREAM_LAUNCH_OK();
     return 0;
 }

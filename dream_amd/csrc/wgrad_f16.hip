@@ -53,133 +53,15 @@ DREAM_DEVICE int scale_exponent(unsigned amax_bits) {
 }
 
 __global__ void __launch_bounds__(256, 2) wgrad_f16_kernel(const Wgrad16Params p) {
-    DREAM_DYNAMIC_LDS(_Float16, smem);
-    _Float16 *sY = smem;                  // [RW][SY]
-    _Float16 *sX = smem + RW * SY;        // [3][CW][SX]
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
-    const int wo = wave >> 1, wi = wave & 1;
-    const int li = lane & 31, lh = lane >> 5;
-    // XCD-aware placement as in wgrad.hip: the (row block, column block) tiles of one split-K slice share an XCD's L2
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int nblk = p.nrb * p.ncb;
-    const int blk = slot % nblk, ks = (slot / nblk) * 8 + xcd;
-    if (ks >= p.splitk) return;
-    const int rbk = blk % p.nrb, cbk = blk / p.nrb;
-    const int co0 = rbk * RW, ci0 = cbk * CW;
-    const float sx = pow2f(scale_exponent(*p.amax_x)), sg = pow2f(scale_exponent(*p.amax_dy));
+    constexpr bool X16 = false;
+#include "wgrad_f16_body.inc"
+}
 
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    f32x4 bsum = {0.0f, 0.0f, 0.0f, 0.0f};           // this thread's share of the channel sums of the unrounded dy
-    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-
-    const int q = tid & 15;                          // channel quad of the staging
-    const int grp = tid >> 4;                        // dy staging: the 8 positions (ty = grp >> 1, tx = 8 * (grp & 1) ..)
-    const bool y_chan_ok = co0 + q * 4 < p.Ct;       // channel counts are multiples of 4
-    const bool x_chan_ok = ci0 + q * 4 < p.Cin;
-
-    for (int tile = ks; tile < p.tiles_total; tile += p.splitk) {
-        int t = tile;
-        const int tix = t % p.tiles_x;
-        t /= p.tiles_x;
-        const int tiy = t % p.tiles_y;
-        const int b = t / p.tiles_y;
-        const int y0 = tiy * TH, x0 = tix * TW;
-        const float *xb = p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;
-        const float *gb = p.dy + (size_t)b * p.H * p.W * p.Ct + co0 + q * 4;
-
-        __syncthreads();                             // previous tile fully consumed
-        // ---- dy: 8 consecutive positions x 4 channels per thread (loads from clamped, always-legal addresses + a select) -----------
-        {
-            const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
-            f32x4 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool ok = y_chan_ok && oy < p.H && ox0 + j < p.W;
-                v[j] = *(const f32x4 *)(ok ? gb + ((size_t)oy * p.W + ox0 + j) * p.Ct : p.dy);
-                v[j] = ok ? v[j] : zero4;
-                bsum += v[j];
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                f16x8 h;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) h[j] = (_Float16)(v[j][c] * sg);      // the one rounding of dy
-                *(f16x8 *)(sY + (q * 4 + c) * SY + grp * 8) = h;
-            }
-        }
-        // ---- x: 10 consecutive positions of a patch row x 4 channels per unit; three shifted copies ----------------------------------
-        for (int u = tid >> 4; u < PH * 2; u += 16) {
-            const int py = u >> 1, half = u & 1;
-            const int gy = y0 - 1 + py, gx0 = x0 - 1 + half * 8;
-            f16x4 h[10];
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const bool ok = x_chan_ok && gy >= 0 && gy < p.H && gx0 + j >= 0 && gx0 + j < p.W;
-                f32x4 v = *(const f32x4 *)(ok ? xb + ((size_t)gy * p.W + gx0 + j) * p.Cin : p.x);
-                v = ok ? v : zero4;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) h[j][c] = (_Float16)(v[c] * sx);      // the one rounding of x
-            }
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    f16x8 piece;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) piece[j] = h[j + dx][c];
-                    *(f16x8 *)(sX + (dx * CW + q * 4 + c) * SX + py * TW + half * 8) = piece;
-                }
-        }
-        __syncthreads();
-
-        // ---- k-steps: one tile row (16 positions) each; patch row s + dy serves tap row dy -------------------------------------------
-        const _Float16 *aY = sY + (wo * 32 + li) * SY + lh * 8;
-        const _Float16 *bX = sX + (wi * 32 + li) * SX + lh * 8;
-        f16x8 row[3][3];                             // [patch row % 3][shift]
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) row[r][dx] = *(const f16x8 *)(bX + dx * CW * SX + r * TW);
-#pragma unroll
-        for (int s = 0; s < TH; ++s) {
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) row[(s + 2) % 3][dx] = *(const f16x8 *)(bX + dx * CW * SX + (s + 2) * TW);
-            const f16x8 a = *(const f16x8 *)(aY + s * TW);
-#pragma unroll
-            for (int ty = 0; ty < 3; ++ty)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) acc[ty * 3 + dx] = mfma_f32_32x32x16_f16(a, row[(s + ty) % 3][dx], acc[ty * 3 + dx]);
-        }
-    }
-
-    // ---- partials (still in the scaled domain) ------------------------------------------------------------------------------------
-#pragma unroll
-    for (int tp = 0; tp < 9; ++tp) {
-        float *part = p.part + ((size_t)ks * 9 + tp) * p.RowsPad * p.Cin;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = co0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int i = ci0 + wi * 32 + li;
-            if (o < p.RowsPad && i < p.Cin) part[(size_t)o * p.Cin + i] = acc[tp][r];
-        }
-    }
-    if (cbk == 0 && p.bias_part != nullptr) {
-        // threads sharing q (the same 4 channels) differ in grp: reduce the 16 groups through LDS, in group order
-        float *red = (float *)smem;
-        __syncthreads();
-        *(f32x4 *)(red + (grp * 16 + q) * 4) = bsum;
-        __syncthreads();
-        if (tid < RW) {
-            float s = 0.0f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) s += red[(g * 16 + (tid >> 2)) * 4 + (tid & 3)];
-            if (co0 + tid < p.RowsPad) p.bias_part[(size_t)ks * p.RowsPad + co0 + tid] = s;
-        }
-    }
+// The same kernel on an x stored as IEEE half (train_activation_storage="fp16"; dream_conv3x3_wgrad_f16_x16_nhwc_f32): half the x
+// staging bytes, no v_cvt, no multiply.  A kernel of its own from the same text, so that the one above stays instruction-identical.
+__global__ void __launch_bounds__(256, 2) wgrad_f16_x16_kernel(const Wgrad16Params p) {
+    constexpr bool X16 = true;
+#include "wgrad_f16_body.inc"
 }
 
 // fixed-order sum over the split-K partials, times 2^-ex * 2^-eg (two exact steps: either factor alone is a normal number)
@@ -230,19 +112,19 @@ extern "C" size_t dream_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin
     return (sk * 9 * RowsPad * Cin + (sk + 1) * RowsPad) * sizeof(float);
 }
 
-// x [B,H,W,Cin], dy [B,H,W,Cdy] (fp32 NHWC), amax_x / amax_dy: device scalars, bit patterns of (an upper bound of) max|x| / max|dy|
-// -> dw_packed [9][RowsPad][Cin] (mode-0 layout: dream_unpack_conv3x3_weight), dbias [Cdy] or null.  Cin % 32 == 0, Cdy % 4 == 0,
-// RowsPad >= Cdy a multiple of 64; flags must be 0.
-extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
-                                                float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
-                                                int Cdy, int RowsPad, int flags, void *stream) {
-    DREAM_REQUIRE(x && amax_x && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
+namespace {
+
+// x16: x is IEEE half (wgrad_f16_x16_kernel), amax_x is not used and the reduce takes a null amax_x (factor 1)
+int launch_wgrad16(const void *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy, float *dw_packed, float *dbias,
+                   void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad, int flags, void *stream, bool x16) {
+    DREAM_REQUIRE(x && (amax_x || x16) && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
     DREAM_REQUIRE(flags == 0, "wgrad_f16: flags %d not supported (plain 3x3 stride-1 convs only)", flags);
     DREAM_REQUIRE(shape_ok(B, H, W, Cin, RowsPad) && Cdy > 0 && Cdy % 4 == 0 && RowsPad >= Cdy,
                   "wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdy %d, pad %d): Cin %% 32, Cdy %% 4, pad %% 64", B, H, W, Cin, Cdy, RowsPad);
     DREAM_REQUIRE((size_t)B * H * W * (size_t)(Cin > Cdy ? Cin : Cdy) < ((size_t)1 << 40), "wgrad_f16: tensor too large");
+    DREAM_REQUIRE(!x16 || ((size_t)x & 15) == 0, "wgrad_f16: a half x must be 16-byte aligned");
     Wgrad16Params p;
-    p.x = x; p.dy = dy; p.amax_x = amax_x; p.amax_dy = amax_dy;
+    p.x = (const float *)x; p.dy = dy; p.amax_x = x16 ? nullptr : amax_x; p.amax_dy = amax_dy;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Ct = Cdy; p.RowsPad = RowsPad;
     p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
     p.tiles_total = B * p.tiles_x * p.tiles_y;
@@ -251,15 +133,16 @@ extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *
     p.part = (float *)workspace;
     float *bias_part = p.part + (size_t)p.splitk * 9 * RowsPad * Cin;
     p.bias_part = dbias ? bias_part : nullptr;
-    if (dream_allow_full_lds((const void *)wgrad_f16_kernel)) return 2;
+    void (*const kernel)(const Wgrad16Params) = x16 ? wgrad_f16_x16_kernel : wgrad_f16_kernel;
+    if (dream_allow_full_lds((const void *)kernel)) return 2;
     const dim3 grid((unsigned)(p.nrb * p.ncb * ceil_div(p.splitk, 8) * 8));
-    hipLaunchKernelGGL(wgrad_f16_kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
     DREAM_LAUNCH_OK();
     const size_t n = (size_t)9 * RowsPad * Cin;
     size_t gr = (n / 4 + 255) / 256;
     if (gr > 2048) gr = 2048;
     hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part, dw_packed,
-                       n, p.splitk, amax_x, amax_dy);
+                       n, p.splitk, p.amax_x, amax_dy);
     DREAM_LAUNCH_OK();
     if (dbias) {
         // bias partials are [splitk][RowsPad] of unscaled sums; only the first Cdy entries are wanted
@@ -270,4 +153,23 @@ extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *
         if (dream_copy_words(dbias, total, (size_t)Cdy * sizeof(float), (hipStream_t)stream)) return 2;
     }
     return 0;
+}
+
+}  // namespace
+
+// x [B,H,W,Cin], dy [B,H,W,Cdy] (fp32 NHWC), amax_x / amax_dy: device scalars, bit patterns of (an upper bound of) max|x| / max|dy|
+// -> dw_packed [9][RowsPad][Cin] (mode-0 layout: dream_unpack_conv3x3_weight), dbias [Cdy] or null.  Cin % 32 == 0, Cdy % 4 == 0,
+// RowsPad >= Cdy a multiple of 64; flags must be 0.
+extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
+                                                float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
+                                                int Cdy, int RowsPad, int flags, void *stream) {
+    return launch_wgrad16(x, amax_x, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, false);
+}
+
+// The same with x stored as IEEE half (train_activation_storage="fp16"): x [B,H,W,Cin] half, 16-byte aligned, is the operand as it is
+// (no scale, no amax_x); dy, the outputs, the workspace (dream_conv3x3_wgrad_f16_workspace) and the split are unchanged.
+extern "C" int dream_conv3x3_wgrad_f16_x16_nhwc_f32(const void *x, const float *dy, const unsigned *amax_dy, float *dw_packed,
+                                                    float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
+                                                    int RowsPad, int flags, void *stream) {
+    return launch_wgrad16(x, nullptr, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, true);
 }

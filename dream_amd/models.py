@@ -202,6 +202,11 @@ class DreamHourglass(nn.Module):
         # on the fp16 matrix cores (conv_f16.hip, wgrad_f16.hip: fp32 tensors in HBM, operands rounded once while staged, per-tensor
         # power-of-two scales from the amax side channel); every other plan entry keeps its fp32 launches.  Does not affect inference.
         self.train_precision = "fp32"
+        # Training with train_precision="fp16" only: "fp16" = the saved activations of the encoder's half run (_half_storage_plan: for
+        # vgg_q the outputs of conv1_1 .. conv5_3 and the pooled tensors) live in HBM as IEEE half, written by the half-storage inference
+        # launches and read as half by the backward (wgrad_f16.hip X16, conv_f16.hip MASK16, elementwise.hip).  "fp32"
+        # (default): every saved activation is fp32.  Read once per training forward; inference ignores it.  See half_storage_peak().
+        self.train_activation_storage = "fp32"
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
         # implicit-GEMM kernel everywhere (csrc/conv_mfma.hip, the reference form)
@@ -338,6 +343,37 @@ class DreamHourglass(nn.Module):
         cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
         return int(in_channels) == cin and cin % 32 == 0 and cout % 32 == 0
 
+    def _half_storage_plan(self):
+        """The rule of train_activation_storage="fp16", evaluated on the plan -> the set of plan indices whose OUTPUT is stored as IEEE
+        half.  A tensor may be half if and only if (1) its producer is the 3-channel "first" conv, a plain conv (_half_train_entry)
+        whose input is half, or a "pool" whose input is half; (2) every entry that reads it is a plain conv or a "pool" whose own output
+        may be half; (3) it is not a skip source.  (The largest such set: candidates are struck until nothing changes.)  The run
+        starts at conv1_1 and ends at the first reader that is not half-capable; a "wide" first conv starts none."""
+        layers = self.plan_layers()
+        channels, plain = [], []                      # per entry: channels of its output; is it a plain conv (on its actual input)
+        for li, (kind, mod, flags) in enumerate(layers):
+            cin = channels[li - 1] if li else self.n_image_input_channels
+            plain.append(li > 0 and self._half_train_entry(kind, mod, flags, cin))
+            channels.append(int(mod.weight.shape[1 if kind == "deconv" else 0]) if mod is not None else cin)
+        half = {li for li, (kind, _, _) in enumerate(layers)
+                if (kind == "first" or kind == "pool" or plain[li]) and li not in self._skip_sources and li + 1 < len(layers)}
+        while True:
+            keep = {li for li in half
+                    if (layers[li][0] == "first" or li - 1 in half)
+                    and (plain[li + 1] or (layers[li + 1][0] == "pool" and li + 1 in half))}
+            if keep == half:
+                return half
+            half = keep
+
+    def _zeroed_half_peak(self, device):
+        """The walk's one peak scalar on ``device``, zeroed in place (created on first use)."""
+        self._half_peak = self._half_peaks.get(device)
+        if self._half_peak is None:
+            self._half_peak = self._half_peaks[device] = ops.new_amax(device)
+        else:
+            self._half_peak.zero_()
+        return self._half_peak
+
     # ---- which plan entries run as one -----------------------------------------------------------------------------------
     def _fuse_pool(self, layers, li, x_nhwc, split):
         """Inference: fold the 2x2 max-pool that follows conv ``li`` into its epilogue?  Not when the un-pooled tensor is
@@ -444,7 +480,8 @@ class DreamHourglass(nn.Module):
         return ops.conv2d_f16_act16(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
 
     def half_storage_peak(self):
-        """The largest |value|, before saturation, that any launch of the last forward with activation_storage="fp16" wanted to store
+        """The largest |value|, before saturation, that any launch of the last forward with activation_storage="fp16" -- or the last
+        training forward with train_activation_storage="fp16" -- wanted to store
         as a half (this module's own forward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_storage_peak(), which takes the
         maximum over the replicas).  >= 65504: that forward saturated -- go back
         to activation_storage="fp32".  Reading it is the mode's only host synchronisation, and happens only here."""
@@ -497,19 +534,26 @@ class DreamHourglass(nn.Module):
             if x_is_nhwc:
                 raise ValueError("activation_storage=\"fp16\" takes the NCHW image (precision=\"fp16\"), not a staged NHWC input")
             conv = self._conv_act16
-            self._half_peak = self._half_peaks.get(x.device)
-            if self._half_peak is None:
-                self._half_peak = self._half_peaks[x.device] = ops.new_amax(x.device)
-            else:
-                self._half_peak.zero_()
+            self._zeroed_half_peak(x.device)
         half = self._check_train_precision() and bool(save)
         layers = self.plan_layers()
         saved, keep = _Saved(), {}
+        store16 = set()                                # plan entries whose output this (training) forward stores as half
+        if save:                                       # (read once per training forward, as ``train_precision``)
+            if self.train_activation_storage not in ("fp32", "fp16"):
+                raise ValueError("unknown train_activation_storage %r (\"fp32\" or \"fp16\")" % (self.train_activation_storage,))
+            if self.train_activation_storage == "fp16":
+                if not half:
+                    raise ValueError("train_activation_storage=\"fp16\" needs train_precision=\"fp16\" (train_precision is %r)"
+                                     % (self.train_precision,))
+                store16 = self._half_storage_plan()
+                self._zeroed_half_peak(x.device)
         act, amax, li = x, x_amax, 0
         while li < len(layers):
             kind, mod, flags = layers[li]
             if kind == "pool":
-                outs = [ops.maxpool2_f16(act) if act16 else ops.maxpool2(act)]    # (pooling cannot raise the maximum: amax stays)
+                # (pooling cannot raise the maximum: amax stays.)  A half tensor of a training forward is pooled as half
+                outs = [ops.maxpool2_f16(act) if act16 or act.dtype == torch.float16 else ops.maxpool2(act)]
             elif kind == "add":
                 self._join(act, keep[flags])
                 if act16:
@@ -525,7 +569,16 @@ class DreamHourglass(nn.Module):
                 w, bias = params[self._param_slot[li]], params[self._param_slot[li] + 1]
                 half_entry = half and self._half_train_entry(kind, mod, flags, act.shape[3])
                 group, sub = self._group(layers, li, act, save, split, half_entry)
-                if half_entry:
+                if kind == "first" and li in store16:
+                    outs, amax = [ops.conv3x3_first_f16(act, w, bias, relu=bool(flags & CONV_RELU), peak=self._half_peak)], None
+                elif half_entry and act.dtype == torch.float16:
+                    # train_activation_storage="fp16": the stored half is the operand (no amax travels), the half-storage inference
+                    # launch; the conv that ends the run stores half as well and a widening pass (exact) follows: its saved output is fp32
+                    saved.half_in.add(li)
+                    p16 = self._packed.get(mod.weight, "f16", 0)
+                    out = ops.conv2d_f16_act16(act, p16, p16[3], 3, None, bias, flags, peak=self._half_peak)
+                    outs, amax = [out if li in store16 else ops.widen_f16(out)], None
+                elif half_entry:
                     # the amax of the launch that produced ``act`` where it is still that tensor's, one absmax pass otherwise; it travels
                     # with ``saved`` to the weight gradient
                     saved.amax[li] = amax = amax if amax is not None else ops.absmax(act)
@@ -584,7 +637,7 @@ class DreamHourglass(nn.Module):
             if kind == "pool":
                 g_amax = None
                 masked = relu_feeds(li - 1)
-                g = ops.maxpool2_bwd(g, inp, relu=masked)
+                g = (ops.maxpool2_bwd_x16 if inp.dtype == torch.float16 else ops.maxpool2_bwd)(g, inp, relu=masked)
                 continue
             if kind == "add":
                 pending[flags] = ops.clone(g)              # later in-place ReLU masks must not touch this copy
@@ -610,6 +663,8 @@ class DreamHourglass(nn.Module):
             if flags & CONV_OUT_NCHW:
                 g = ops.nchw_to_nhwc(grad_out_nchw, cpad=ops.round_up(cout, 16))   # zero-padded K -> 16k channels
             if flags & CONV_RELU and not masked:
+                # (a half output is read by a plain conv or a pool only, _half_storage_plan: its ReLU mask was applied by their launches)
+                assert out.dtype == torch.float32, "internal: the element-wise ReLU backward has no half-mask form"
                 g, g_amax = ops.relu_bwd_(g, out), None
             masked = False
             if kind == "first":
@@ -622,6 +677,20 @@ class DreamHourglass(nn.Module):
                 if need_input_grad:
                     g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
+                continue
+            if li in saved.half_in:
+                # the forward read a half input here (train_activation_storage="fp16"): the weight gradient takes the stored half as its
+                # operand, the data gradient masks with the half output of the conv in front
+                g_amax = g_amax if g_amax is not None else ops.absmax(g)
+                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=g_amax):
+                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16(inp, g, ag, cout, cin)
+                _on_side(side, leaf, inp, g, g_amax)
+                p16 = self._packed.get(mod.weight, "f16", 1)
+                if fuse:
+                    g, g_amax = ops.conv2d_f16_mask16(g, g_amax, p16, p16[3], 3, inp)
+                else:                                      # (behind a pool: the pool's backward carries the ReLU gradient)
+                    g, g_amax = ops.conv2d_f16(g, g_amax, p16, p16[3], 3)
+                masked = fuse
                 continue
             if li in saved.amax:
                 # the forward ran this entry in half precision (it left the input's amax): both products of its backward on the fp16
@@ -711,11 +780,13 @@ class DreamHourglass(nn.Module):
 class _Saved(list):
     """What DreamHourglass.run_forward hands to run_backward: the (input, output) pair of every plan entry, and ``amax``: plan index ->
     the amax scalar of the input of each entry that ran in half precision (train_precision="fp16").  The forward decides which entries
-    those are; the backward runs exactly them in half precision."""
+    those are; the backward runs exactly them in half precision.  ``half_in``: the plan indices of the convs that read a half input
+    (train_activation_storage="fp16"; they have no entry in ``amax``: the stored half is the operand)."""
 
     def __init__(self, *a):
         super().__init__(*a)
         self.amax = {}
+        self.half_in = set()
 
 
 class _HourglassFunction(torch.autograd.Function):
@@ -1126,6 +1197,17 @@ class DreamHourglassMultiStage(nn.Module):
             raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
 
     @property
+    def train_activation_storage(self):
+        """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.train_activation_storage)."""
+        return "fp32"
+
+    @train_activation_storage.setter
+    def train_activation_storage(self, value):
+        if value != "fp32":
+            raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: train_activation_storage=%r is not supported"
+                             % (value,))
+
+    @property
     def train_precision(self):
         return self.stage1.train_precision
 
@@ -1319,6 +1401,16 @@ class ResnetSimple(nn.Module):
     def activation_storage(self, value):
         if value != "fp32":
             raise ValueError("ResnetSimple stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
+
+    @property
+    def train_activation_storage(self):
+        """Always "fp32": ResnetSimple trains in fp32 only (DreamHourglass.train_activation_storage)."""
+        return "fp32"
+
+    @train_activation_storage.setter
+    def train_activation_storage(self, value):
+        if value != "fp32":
+            raise ValueError("ResnetSimple stores its activations in fp32 only: train_activation_storage=%r is not supported" % (value,))
 
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""

@@ -1604,6 +1604,58 @@ def add_f16(a, b, peak=None):
     return out
 
 
+# ---- training with the saved activations stored as IEEE half (train_activation_storage="fp16"): the backward's read side -----------
+def conv3x3_wgrad_f16_x16(x_nhwc, dy_nhwc, amax_dy, cout, cin, flags=0):
+    """conv3x3_wgrad_f16 with x a torch.float16 tensor that IS the operand (no amax of x, no scale) -> (dW OIHW, dbias [cout])."""
+    x, dy = _f16(x_nhwc), _f32(dy_nhwc)
+    b, h, w, cdy = (int(v) for v in dy.shape)
+    if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
+    rows_pad = round_up(cdy, 64)
+    ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
+    dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
+    dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
+    call("dream_conv3x3_wgrad_f16_x16_nhwc_f32", ptr(x), ptr(dy), ptr(amax_dy), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin, cdy, rows_pad,
+         flags, stream())
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
+    return dw, dbias[:cout].contiguous()
+
+
+def conv2d_f16_mask16(x_nhwc, amax_in, packed16, cout, ksize, relu_mask, scale=None, shift=None, flags=0, want_amax=True):
+    """conv2d_f16(..., relu_mask=) with the mask a torch.float16 tensor of the output's shape -> (y fp32, amax_out after the mask)."""
+    hi, _, exp, _ = packed16
+    x, mask = _f32(x_nhwc), _f16(relu_mask)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv2d_f16_mask16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    if tuple(mask.shape) != (b, h, w, cout):
+        raise RuntimeError("conv2d_f16_mask16: relu_mask must have the output's shape %s" % ((b, h, w, cout),))
+    y = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
+    amax_out = new_amax(x.device) if want_amax else None
+    call("dream_conv2d_f16_mask16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(mask), ptr(y),
+         ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y, amax_out
+
+
+def maxpool2_bwd_x16(dy, x, relu=False):
+    """maxpool2_bwd with the forward input x a torch.float16 tensor -> dx fp32."""
+    x = _f16(x)
+    b, h, w, c = (int(v) for v in x.shape)
+    dx = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
+    call("dream_maxpool2_relu_bwd_x16_nhwc_f32" if relu else "dream_maxpool2_bwd_x16_nhwc_f32", ptr(_f32(dy)), ptr(x), ptr(dx),
+         b, h, w, c, stream())
+    return dx
+
+
+def widen_f16(x):
+    """float(x), exact: torch.float16 -> torch.float32."""
+    x = _f16(x)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    call("dream_widen_f16_f32", ptr(x), ptr(out), x.numel(), stream())
+    return out
+
+
 def conv2d_amax(x_nhwc, packed, cout, ksize, stride=1, scale=None, shift=None, residual=None, flags=0):
     """fp32 MFMA conv that also publishes max|y| (feeds the split-precision kernel's input scaling)."""
     x = _f32(x_nhwc)

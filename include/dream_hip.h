@@ -510,6 +510,32 @@ int dream_conv3x3_wgrad_f16_splitk(int B, int H, int W, int Cin, int RowsPad);
 int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
                                      float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
                                      int Cdy, int RowsPad, int flags, void *stream);
+/* ---- training with the saved activations stored as IEEE half (DreamHourglass.train_activation_storage = "fp16") ---------
+ * The backward's read side of tensors that the training forward stored with the _nhwc_f16 launches above (`x16` / `mask16` in the
+ * name: that operand is a half tensor, void *, [B,H,W,C]; gradients stay fp32).
+ * The weight gradient of dream_conv3x3_wgrad_f16_nhwc_f32 with x stored as half (same reference call sites: loss.backward(),
+ * dream/network.py:335, Conv2d layers of dream/models.py:594-615): the stored half IS the operand -- no amax_x, ex = 0 --, copied
+ * into LDS (8 bytes per lane and position, no convert, no multiply).  dy, amax_dy, outputs, workspace, split and flags as there;
+ * x 16-byte aligned. */
+int dream_conv3x3_wgrad_f16_x16_nhwc_f32(const void *x, const float *dy, const unsigned *amax_dy, float *dw_packed,
+                                         float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad,
+                                         int flags, void *stream);
+/* dream_conv2d_f16_nhwc_f32 with DREAM_CONV_RELUMASK (implied) and the mask stored as half: y = mask > 0 ? conv : 0, fp32 NHWC,
+ * amax_out = max|y| after the mask -- the data gradient of a conv behind the ReLU of a conv whose saved output is half
+ * (nn.ReLU(inplace) after the Conv2d layers of dream/models.py:594-615, reached from loss.backward(), dream/network.py:335).
+ * mask [B,H,W,Cout] half.  Every variant of dream_conv_f16_set_variant applies. */
+int dream_conv2d_f16_mask16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                     const float *scale, const float *shift, const void *mask, float *y,
+                                     unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
+                                     int stride, int flags, void *stream);
+/* dream_maxpool2_bwd_nhwc_f32 / dream_maxpool2_relu_bwd_nhwc_f32 (nn.MaxPool2d(2), dream/models.py:589,765-771) with the forward
+ * input x stored as half: dy, dx fp32.  A half compares as its fp32 value: the first maximal element in window scan order wins,
+ * leftover rows / columns of odd extents get zero, exactly as there.  C % 4 == 0; x 8-byte, dy and dx 16-byte aligned. */
+int dream_maxpool2_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream);
+int dream_maxpool2_relu_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream);
+/* out[i] = float(x[i]) (exact), x half, out fp32, i < n, both 16-byte aligned: the widening pass behind the last half-storage
+ * conv of a training forward (the Conv2d in front of the first nn.Upsample / ConvTranspose2d, dream/models.py:613-615,688-705) */
+int dream_widen_f16_f32(const void *x, float *out, size_t n, void *stream);
 /* The same weight gradient in the Winograd F(2x2,3x3) domain (16 instead of 36 multiplications per 2x2 outputs, fp32
  * throughout): dU_p = sum_tiles (A dY A^T)_p x (B^T d B)_p on the fp32 matrix cores, dW = G^T dU G, deterministic split-K.
  * x [B,H,W,Cin], dy [B,H,W,Cdy] (Cdy >= Cout, both multiples of 16), Cin % 64 == 0 -> dw_oihw [Cout,Cin,3,3] (OIHW,
