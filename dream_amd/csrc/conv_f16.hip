@@ -25,6 +25,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16P
     constexpr bool EPI_MASK = false;
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = false;
+    constexpr bool KSPLIT = false;
 #include "conv_f16_body.inc"
 }
 
@@ -35,6 +36,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Co
     constexpr bool EPI_MASK = true;
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = false;
+    constexpr bool KSPLIT = false;
 #include "conv_f16_body.inc"
 }
 
@@ -48,6 +50,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_act16_kernel(const C
     constexpr bool EPI_MASK = false;
     constexpr bool ACT16 = true;
     constexpr bool MASK16 = false;
+    constexpr bool KSPLIT = false;
 #include "conv_f16_body.inc"
 }
 
@@ -58,7 +61,58 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask16_kernel(const 
     constexpr bool EPI_MASK = true;
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = true;
+    constexpr bool KSPLIT = false;
 #include "conv_f16_body.inc"
+}
+
+// conv_f16_act16_kernel on one slice of the contraction (conv_ksplit="auto": small-batch inference, where the grid of a deep layer
+// fills a few per cent of the chip): gridDim.z slices of the Cin/32 x taps stages, each workgroup runs the stages of
+// slice blockIdx.z -- same loader, same MFMA loop -- and stores its raw fp32 accumulator tile to p.y = workspace[slice] (NHWC fp32).
+// No atomics: conv_f16_ksplit_finish_kernel sums the slices in a fixed order.  Plain stride-1 convs only (no pool, upsample, NCHW).
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_ksplit_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = false;
+    constexpr bool ACT16 = true;
+    constexpr bool MASK16 = false;
+    constexpr bool KSPLIT = true;
+#include "conv_f16_body.inc"
+}
+
+// y = half(sat(epilogue(sum_s workspace[s]))): the partial sums of the S slices added in slice order 0 .. S-1 (fp32; two runs give the
+// same bits), then the expression of conv_f16_epilogue.inc -- v * (2^-ew * scale) + shift, ReLU --, max|v| before the saturation into
+// the peak scalar, sat_half, half NHWC.  Elementwise over the flattened tensor, 8 consecutive elements (channels) per lane: two
+// 16-byte loads per slice, one 16-byte store; `slice` = round_up(n, 8) floats.
+__global__ void __launch_bounds__(256) conv_f16_ksplit_finish_kernel(const float *ws, size_t slice, int S, const int *w_exp,
+                                                                     const float *scale, const float *shift, _Float16 *y, size_t n,
+                                                                     int Cout, int relu, unsigned *amax) {
+    const int e = -*w_exp;
+    const float inv = pow2f(e < -126 ? -126 : (e > 127 ? 127 : e));
+    const size_t n8 = (n + 7) / 8;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+        f32x4 lo = *(const f32x4 *)(ws + i * 8), hi = *(const f32x4 *)(ws + i * 8 + 4);
+        for (int s = 1; s < S; ++s) {
+            const float *q = ws + (size_t)s * slice + i * 8;
+            lo += *(const f32x4 *)q;
+            hi += *(const f32x4 *)(q + 4);
+        }
+        int c = (int)((i * 8) % (size_t)Cout);
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float v = (k < 4 ? lo[k & 3] : hi[k & 3]) * (inv * (scale != nullptr ? scale[c] : 1.0f)) + (shift != nullptr ? shift[c] : 0.0f);
+            if (relu) v = fmaxf(v, 0.0f);
+            if (i * 8 + k < n) m = fmaxf(m, fabsf(v));
+            o[k] = sat_half(v);
+            if (++c == Cout) c = 0;
+        }
+        if (i * 8 + 8 <= n) {
+            *(f16x8 *)(y + i * 8) = o;
+        } else {
+            for (int k = 0; i * 8 + k < n; ++k) y[i * 8 + k] = o[k];
+        }
+    }
+    if (amax) publish_amax(amax, m);
 }
 
 struct Variant16h {
@@ -68,9 +122,11 @@ struct Variant16h {
     void (*mask_kernel)(const Conv16Params);
     void (*act16_kernel)(const Conv16Params);
     void (*mask16_kernel)(const Conv16Params);
+    void (*ksplit_kernel)(const Conv16Params);
 };
 #define F16_KERNELS(...) \
-    conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>, conv_f16_mask16_kernel<__VA_ARGS__>
+    conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>, conv_f16_mask16_kernel<__VA_ARGS__>, \
+    conv_f16_ksplit_kernel<__VA_ARGS__>
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -84,11 +140,36 @@ const Variant16h kVariantsF16[] = {
 };
 constexpr int kNumF16 = 8;
 int g_forced_f16 = -1;
+thread_local int g_forced_ksplit = -1;
+
+// the tile of a launch of `pixels` positions
+int variant_f16(long pixels, int Cin, int Cout, int ntaps) {
+    // the variant rule, measured per layer at 128 frames (DESIGN.md 4.8b; profiles/r07_ab_f16_variants.txt): from 128 output channels on
+    // the 128 x 128 tile wins by 5-12 % (160 VGPRs and 51 KB of LDS: three workgroups per CU; the 256-px tiles hold two); a 64-channel
+    // 3x3 conv is 3 % faster on the single-buffered 256 x 64 tile, a 64-channel 1x1 conv (a chunk change per stage) 15 % on the
+    // double-buffered one
+    int v = Cout <= 32 ? 2 : (Cout <= 64 ? (ntaps == 1 ? 1 : 5) : 0);
+    // tiny grids: 64-px tiles -- unless the launch is deep (the first decoder conv: 4 taps x 2048 channels on 13 x 13 maps), where the
+    // weight tile is what a workgroup streams and the 256-px tile re-reads it a quarter as often (0.645 against 0.780 ms)
+    if (Cout > 64 && ((pixels + 255) / 256) * ceil_div(Cout, 64) < 512) v = (long)Cin * ntaps >= 4096 ? 1 : 3;
+    return g_forced_f16 >= 0 ? g_forced_f16 : v;
+}
+
+// conv_ksplit: the flags whose launches are never split (the large-map layers and the K-channel output); the workgroups a split
+// launch may reach, the fewest stages a slice is left with, the most slices.  Measured per layer at 1 .. 16 frames
+// (profiles/ab_f16_ksplit.txt): a split pays where the unsplit grid is at most ~190 workgroups AND the contraction is
+// long -- 512->512 at 25 x 25, one frame: 0.071 -> 0.028 ms with 8 slices; at 50 x 50: 0.072 -> 0.041 with 4 --; from ~310 workgroups
+// on every split lost, and so did slices of 9 .. 18 stages (a 128->128 conv of 36 stages at 157 workgroups: 0.022 -> 0.025 ms in two
+// slices: the finishing pass costs what the halved workgroups save)
+constexpr int kKsplitRefused = DREAM_CONV_POOL2 | DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_RELUMASK;
+constexpr int kKsplitTargetWorkgroups = 384;
+constexpr int kKsplitMinStages = 24;
+constexpr int kKsplitMax = 16;
 
 // act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used; mask16: the ReLU mask (`residual`) is a half tensor
 int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
                const float *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
-               int flags, void *stream, bool act16 = false, bool mask16 = false) {
+               int flags, void *stream, bool act16 = false, bool mask16 = false, int ksplit = 0) {
     DREAM_REQUIRE(x && (amax_in || act16) && w && w_exp && y, "conv_f16: null pointer");
     DREAM_REQUIRE(!act16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
     DREAM_REQUIRE(!act16 || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
@@ -99,15 +180,7 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     p.B = B;
     p.Cin = Cin; p.Cout = Cout; p.CoutPad = CoutPad;
     const long pixels = (long)B * g.H * g.W;
-    // the variant rule, measured per layer at 128 frames (DESIGN.md 4.8b; profiles/r07_ab_f16_variants.txt): from 128 output channels on
-    // the 128 x 128 tile wins by 5-12 % (160 VGPRs and 51 KB of LDS: three workgroups per CU; the 256-px tiles hold two); a 64-channel
-    // 3x3 conv is 3 % faster on the single-buffered 256 x 64 tile, a 64-channel 1x1 conv (a chunk change per stage) 15 % on the
-    // double-buffered one
-    int v = Cout <= 32 ? 2 : (Cout <= 64 ? (g.ntaps == 1 ? 1 : 5) : 0);
-    // tiny grids: 64-px tiles -- unless the launch is deep (the first decoder conv: 4 taps x 2048 channels on 13 x 13 maps), where the
-    // weight tile is what a workgroup streams and the 256-px tile re-reads it a quarter as often (0.645 against 0.780 ms)
-    if (Cout > 64 && ((pixels + 255) / 256) * ceil_div(Cout, 64) < 512) v = (long)Cin * g.ntaps >= 4096 ? 1 : 3;
-    if (g_forced_f16 >= 0) v = g_forced_f16;
+    const int v = variant_f16(pixels, Cin, Cout, g.ntaps);
     const Variant16h &var = kVariantsF16[v];
     DREAM_REQUIRE(CoutPad % var.BN == 0 && CoutPad >= Cout, "CoutPad=%d must be a multiple of %d", CoutPad, var.BN);
     const bool pool = (flags & DREAM_CONV_POOL2) != 0;
@@ -117,13 +190,18 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
     DREAM_REQUIRE(!mask16 || (mask && !act16), "conv_f16: a half mask goes with DREAM_CONV_RELUMASK on fp32 activations");
-    void (*const kernel)(const Conv16Params) = act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel);
+    // ksplit > 0: that many slices of the contraction, y = the fp32 workspace (dream_conv2d_f16_ksplit_nhwc_f16)
+    DREAM_REQUIRE(ksplit == 0 || (act16 && !(flags & kKsplitRefused) && g.out_scale == 1 && ksplit <= 1024),
+                  "conv_f16: a split launch is a plain half-storage conv of at most 1024 slices");
+    void (*const kernel)(const Conv16Params) =
+        ksplit ? var.ksplit_kernel : (act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel));
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
     DREAM_REQUIRE(lds <= 160 * 1024, "LDS request %zu too large", lds);
     if (dream_allow_full_lds((const void *)kernel)) return 2;
-    const dim3 grid((unsigned)(ceil_div((int)((size_t)B * p.tiles_x * p.tiles_y), 8) * 8), (unsigned)ceil_div(Cout, var.BN));
+    const dim3 grid((unsigned)(ceil_div((int)((size_t)B * p.tiles_x * p.tiles_y), 8) * 8), (unsigned)ceil_div(Cout, var.BN),
+                    (unsigned)(ksplit ? ksplit : 1));
     hipLaunchKernelGGL(kernel, grid, dim3(var.threads), lds, (hipStream_t)stream, p);
     DREAM_LAUNCH_OK();
     return 0;
@@ -232,5 +310,63 @@ extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void 
         if (int rc = launch_f16(x, nullptr, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream, true))
             return rc;
     }
+    return 0;
+}
+
+// ---- conv_ksplit="auto": the contraction of a small-grid conv divided over workgroups ---------------------------
+extern "C" int dream_conv_f16_set_ksplit(int n) {
+    DREAM_REQUIRE(n == -1 || n >= 1, "ksplit: -1 (the rule) or a slice count >= 1");
+    g_forced_ksplit = n;
+    return 0;
+}
+
+// Slices of this launch: fixed constants, no device query -- the emulator, a meta-device trace and the GPU agree.  1 wherever the
+// unsplit grid already has kKsplitTargetWorkgroups workgroups; never more than kKsplitMax, never fewer than kKsplitMinStages
+// stages a slice.  Non-increasing in B: a tile never spans frames, and the tile of a launch with more than 64 output channels
+// changes with B only where the answer is 1 on both sides (the tiny-grid rule of variant_f16 holds below 512 units of 256 px x 64
+// channels; above it the 128 x 128 tiles alone are >= 512 workgroups).
+extern "C" int dream_conv2d_f16_ksplit(int B, int H, int W, int Cin, int Cout, int ksize, int flags) {
+    if (B < 1 || H < 1 || W < 1 || Cin < KC || Cin % KC != 0 || Cout < 1 || (ksize != 1 && ksize != 3) || (flags & kKsplitRefused)) return 1;
+    const int nstages = (Cin / KC) * ksize * ksize;
+    if (g_forced_ksplit >= 1) return g_forced_ksplit < nstages ? g_forced_ksplit : nstages;
+    const long pixels = (long)B * H * W;
+    if (Cout > 64 && ((pixels + 255) / 256) * ceil_div(Cout, 64) >= 512) return 1;
+    const Variant16h &var = kVariantsF16[variant_f16(pixels, Cin, Cout, ksize * ksize)];
+    Conv16Params p;
+    fill_params16(p, geom16_conv(H, W, ksize, flags), var.BM, var.NP_MAX, flags);
+    const long wgs = (long)B * p.tiles_x * p.tiles_y * ceil_div(Cout, var.BN);
+    long s = kKsplitTargetWorkgroups / wgs;
+    if (s > nstages / kKsplitMinStages) s = nstages / kKsplitMinStages;
+    if (s > kKsplitMax) s = kKsplitMax;
+    return s < 1 ? 1 : (int)s;
+}
+
+// bytes of S slices of round_up(B H W Cout, 8) floats
+extern "C" size_t dream_conv2d_f16_ksplit_workspace(int B, int H, int W, int Cout, int S) {
+    if (B < 1 || H < 1 || W < 1 || Cout < 1 || S < 1) return 0;
+    return (size_t)S * ((((size_t)B * H * W * Cout) + 7) & ~(size_t)7) * sizeof(float);
+}
+
+// dream_conv2d_f16_nhwc_f16 in S slices: S launches' worth of workgroups in one grid (conv_f16_ksplit_kernel), then the finishing
+// pass.  S == 1 is dream_conv2d_f16_nhwc_f16 itself (the workspace is not touched).
+extern "C" int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                                const float *shift, void *y, unsigned *amax_out, void *workspace, int S, int B,
+                                                int H, int W, int Cin, int Cout, int CoutPad, int ksize, int stride, int flags,
+                                                void *stream) {
+    DREAM_REQUIRE(S >= 1, "conv2d_f16_ksplit: S=%d", S);
+    if (S == 1) return dream_conv2d_f16_nhwc_f16(x, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, ksize, stride, flags, stream);
+    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
+    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    DREAM_REQUIRE(!(flags & kKsplitRefused), "conv2d_f16_ksplit: flags %d: a launch with a fused pool / upsample / NCHW output is not split", flags);
+    DREAM_REQUIRE(workspace && y && (((size_t)workspace | (size_t)y) & 15) == 0, "conv2d_f16_ksplit: workspace and y must be 16-byte aligned");
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
+    if (int rc = launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, nullptr, workspace, nullptr, B, Cin, Cout, CoutPad, g,
+                            flags & ~DREAM_CONV_RELU, stream, true, false, S))
+        return rc;
+    const size_t n = (size_t)B * H * W * Cout, slice = (n + 7) & ~(size_t)7;
+    hipLaunchKernelGGL(conv_f16_ksplit_finish_kernel, dim3((unsigned)(slice / 8 / 256 < 4096 ? slice / 8 / 256 + 1 : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const float *)workspace, slice, S, w_exp, scale, shift, (_Float16 *)y, n, Cout,
+                       (flags & DREAM_CONV_RELU) ? 1 : 0, amax_out);
+    DREAM_LAUNCH_OK();
     return 0;
 }

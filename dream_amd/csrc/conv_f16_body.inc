@@ -2,7 +2,10 @@
 // that was measured (as conv_wino_body.inc).  In scope: the template parameters MR, NR, WM, WN, NPM, DB, PRIO, the argument p, and
 // EPI_MASK (bool constant: the DREAM_CONV_RELUMASK epilogue) and ACT16 (bool constant: activations live in HBM as IEEE half --
 // p.x and an NHWC p.y point to halfs; the patch is copied, not converted: 16-byte pieces of 8 halfs, no input scale) and MASK16
-// (bool constant, read by the epilogue: the ReLU mask of EPI_MASK is a tensor of IEEE halfs).
+// (bool constant, read by the epilogue: the ReLU mask of EPI_MASK is a tensor of IEEE halfs) and KSPLIT (bool constant, with ACT16:
+// slice blockIdx.z of the gridDim.z slices of the contraction -- a contiguous range of the (channel chunk, tap) stages, the leftover
+// spread over the first slices -- whose raw fp32 accumulators go to p.y = workspace[slice] in NHWC fp32: no scale, no shift, no ReLU,
+// no peak; conv_f16_ksplit_finish_kernel sums the slices and runs the epilogue).
     constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
     constexpr int BN = 32 * NR * WN;
     constexpr int QW = ACT16 ? 8 : 4;               // elements of a 16-byte piece
@@ -137,21 +140,31 @@
     };
 
     const int nchunks = p.Cin / KC;
-    load_a(0);
-    load_b(0, 0);
+    // KSPLIT: this workgroup runs the stages [ks_first, ks_end) of the launch's nchunks * ntaps
+    int ks_first = 0, ks_end = 0;
+    if constexpr (KSPLIT) {
+        const int all = nchunks * p.ntaps, S = (int)gridDim.z, s = (int)blockIdx.z, per = all / S, rem = all % S;
+        ks_first = s * per + (s < rem ? s : rem);
+        ks_end = ks_first + per + (s < rem ? 1 : 0);
+        if (ks_first >= ks_end) ks_first = ks_end = 0;   // an empty slice (a caller's S beyond the stages) stores its zeros: no stage, valid loads
+    }
+    load_a(KSPLIT ? ks_first / p.ntaps * KC : 0);
+    load_b(KSPLIT ? ks_first % p.ntaps : 0, KSPLIT ? ks_first / p.ntaps * KC : 0);
     store_a(0);
     store_b(0);
     __syncthreads();
 
-    int buf = 0, abuf = 0, tap = 0, chunk = 0;
-    const int ntaps = p.ntaps, nstages = nchunks * ntaps;
-    for (int st = 0; st < nstages; ++st) {
+    int buf = 0, abuf = 0, tap = KSPLIT ? ks_first % p.ntaps : 0, chunk = KSPLIT ? ks_first / p.ntaps : 0;
+    const int ntaps = p.ntaps, nstages = KSPLIT ? ks_end : nchunks * ntaps;
+    for (int st = KSPLIT ? ks_first : 0; st < nstages; ++st) {
         const bool last_tap = (tap == ntaps - 1);
-        const bool more_chunks = (chunk + 1 < nchunks);
+        // (KSPLIT: the next chunk only where the slice reaches it)
+        const bool more_chunks = KSPLIT ? ((chunk + 1) * ntaps < nstages) : (chunk + 1 < nchunks);
         const bool have_next = (st + 1 < nstages);
         if (have_next) load_b(last_tap ? 0 : tap + 1, last_tap ? (chunk + 1) * KC : chunk * KC);
         // DB: the next chunk's patch is fetched at the first tap and held in registers until the last; SB: one stage ahead
-        if ((DB ? tap == 0 : last_tap) && more_chunks) load_a((chunk + 1) * KC);
+        // (KSPLIT: a slice that begins inside a chunk fetches at its first stage)
+        if ((DB ? (tap == 0 || (KSPLIT && st == ks_first)) : last_tap) && more_chunks) load_a((chunk + 1) * KC);
 
         const int tdy = (int)((p.tap_dy >> (4 * tap)) & 15), tdx = (int)((p.tap_dx >> (4 * tap)) & 15);
         const _Float16 *pa = sA + abuf * NP * S16 + (tdy * PW + tdx) * S16;
@@ -187,4 +200,27 @@
         if (last_tap) { tap = 0; ++chunk; } else ++tap;
     }
 
+    if constexpr (KSPLIT) {
+        // the raw accumulators of this slice, every element of the tile inside the image (a lane owns one channel: 128 bytes per
+        // half-wave and pixel); slices lie round_up(B H W Cout, 8) floats apart (conv_f16_ksplit_finish_kernel reads 32-byte pieces)
+        const size_t slice = ((size_t)p.B * p.H * p.W * p.Cout + 7) & ~(size_t)7;
+        float *ws = p.y + (size_t)blockIdx.z * slice;
+        const int npix = p.TH * TW;
+#pragma unroll
+        for (int ms = 0; ms < MR; ++ms) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = (wm * MR + ms) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int ty = (m * p.rcpTW) >> 16, tx = m - ty * TW;
+                const bool ok = (m < npix) && (y0 + ty < p.H) && (x0 + tx < p.W);
+                const size_t o = (((size_t)b * p.H + y0 + ty) * p.W + x0 + tx) * p.Cout;
+#pragma unroll
+                for (int ns = 0; ns < NR; ++ns) {
+                    const int n = n0 + (wn * NR + ns) * 32 + li;
+                    if (ok && n < p.Cout) ws[o + n] = acc[ms][ns][r];
+                }
+            }
+        }
+        return;
+    }
 #include "conv_f16_epilogue.inc"

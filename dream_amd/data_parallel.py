@@ -130,7 +130,7 @@ def _buffer_stamp(module):
 
 
 def _settings(module):
-    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"))
+    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "conv_ksplit", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"))
 
 
 class _Busy:
@@ -430,7 +430,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "train_precision", "train_activation_storage", "conv_algorithm",
+            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_activation_storage", "conv_algorithm",
                          "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))

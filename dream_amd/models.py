@@ -196,6 +196,12 @@ class DreamHourglass(nn.Module):
         # +-65504, round to nearest even; csrc/conv_f16.hip ACT16) -- half the activation traffic and footprint; the
         # image and the belief maps stay fp32.  "fp32" (default): today's walk.  Training ignores it.  See half_storage_peak().
         self.activation_storage = "fp32"
+        # Inference with precision="fp16" and activation_storage="fp16" only: "auto" = a conv launch whose grid cannot fill the chip (the
+        # deep layers at 1 .. 8 frames) divides its contraction over more workgroups (ops.conv2d_f16_act16_ksplit; csrc/conv_f16.hip
+        # KSPLIT); launches with a fused pool / upsample, the transposed convs, the first conv and the belief-map conv are
+        # never split.  "off" (default): every launch list is what it was.  Read once per forward; training ignores it.
+        self.conv_ksplit = "off"
+        self._ksplit = False                 # the switch as the running forward read it
         self._half_peaks = {}                # device -> the walk's peak scalar: ONE persistent tensor, zeroed in place by every half-storage
         self._half_peak = None               # forward (so every captured hipGraph of this module writes the scalar that is read); the last one used
         # Training: "fp32", or "fp16" = the plain convs (_half_train_entry) run their forward, data-gradient and weight-gradient products
@@ -477,7 +483,8 @@ class DreamHourglass(nn.Module):
             p16 = self._packed.get(mod.weight, "f16", 1)
             return ops.conv_transpose3x3s2_f16_act16(x, p16, p16[3], bias, relu=bool(flags & CONV_RELU), peak=peak), None
         p16 = self._packed.get(mod.weight, "f16", 0)
-        return ops.conv2d_f16_act16(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
+        launch = ops.conv2d_f16_act16_ksplit if self._ksplit else ops.conv2d_f16_act16
+        return launch(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
 
     def half_storage_peak(self):
         """The largest |value|, before saturation, that any launch of the last forward with activation_storage="fp16" -- or the last
@@ -525,6 +532,8 @@ class DreamHourglass(nn.Module):
             raise ValueError("unknown precision %r" % (self.precision,))
         if self.activation_storage not in ("fp32", "fp16"):
             raise ValueError("unknown activation_storage %r (\"fp32\" or \"fp16\")" % (self.activation_storage,))
+        if self.conv_ksplit not in ("off", "auto"):
+            raise ValueError("unknown conv_ksplit %r (\"off\" or \"auto\")" % (self.conv_ksplit,))
         split = self.precision in _HALF_OPS and not save
         act16 = self.activation_storage == "fp16" and not save           # (read once per forward, as ``precision``)
         if act16 and self.precision != "fp16":
@@ -535,6 +544,10 @@ class DreamHourglass(nn.Module):
                 raise ValueError("activation_storage=\"fp16\" takes the NCHW image (precision=\"fp16\"), not a staged NHWC input")
             conv = self._conv_act16
             self._zeroed_half_peak(x.device)
+        self._ksplit = self.conv_ksplit == "auto" and not save           # (read once per forward)
+        if self._ksplit and not act16:
+            raise ValueError("conv_ksplit=\"auto\" needs precision=\"fp16\" and activation_storage=\"fp16\" (they are %r and %r)"
+                             % (self.precision, self.activation_storage))
         half = self._check_train_precision() and bool(save)
         layers = self.plan_layers()
         saved, keep = _Saved(), {}
@@ -1197,6 +1210,16 @@ class DreamHourglassMultiStage(nn.Module):
             raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
 
     @property
+    def conv_ksplit(self):
+        """Always "off": the stages run the fp32-storage walk (DreamHourglass.conv_ksplit)."""
+        return "off"
+
+    @conv_ksplit.setter
+    def conv_ksplit(self, value):
+        if value != "off":
+            raise ValueError("DreamHourglassMultiStage does not split its convs: conv_ksplit=%r is not supported" % (value,))
+
+    @property
     def train_activation_storage(self):
         """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.train_activation_storage)."""
         return "fp32"
@@ -1401,6 +1424,16 @@ class ResnetSimple(nn.Module):
     def activation_storage(self, value):
         if value != "fp32":
             raise ValueError("ResnetSimple stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
+
+    @property
+    def conv_ksplit(self):
+        """Always "off": its convs read and write fp32 (DreamHourglass.conv_ksplit)."""
+        return "off"
+
+    @conv_ksplit.setter
+    def conv_ksplit(self, value):
+        if value != "off":
+            raise ValueError("ResnetSimple does not split its convs: conv_ksplit=%r is not supported" % (value,))
 
     @property
     def train_activation_storage(self):

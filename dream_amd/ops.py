@@ -1552,6 +1552,35 @@ def conv2d_f16_act16(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flag
     return y
 
 
+def conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags=0):
+    """Slices conv2d_f16_act16_ksplit divides the contraction of this launch into (a host computation: no GPU is touched; 1 = not split)."""
+    return int(_hip.lib().dream_conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags))
+
+
+def conv2d_f16_act16_ksplit(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flags=0, peak=None, workspace=None):
+    """conv2d_f16_act16 with the contraction of a small grid divided over conv2d_f16_ksplit() slices (conv_ksplit="auto"): partial
+    sums in an fp32 workspace (torch.empty per call: capturable), summed in slice order.  One slice -- every launch with a fused
+    pool / upsample or the NCHW output, every grid that fills the chip -- IS conv2d_f16_act16.  ``workspace`` (tests): a float32
+    tensor of at least dream_conv2d_f16_ksplit_workspace() bytes to use instead."""
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    s = conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags)
+    if s == 1:
+        return conv2d_f16_act16(x, packed16, cout, ksize, scale, shift, flags, peak=peak)
+    hi, _, exp, _ = packed16
+    if cin != hi.shape[-1]:
+        raise RuntimeError("conv2d_f16_act16_ksplit: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    nbytes = int(_hip.lib().dream_conv2d_f16_ksplit_workspace(b, h, w, cout, s))
+    if workspace is None:
+        workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    elif workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
+        raise RuntimeError("conv2d_f16_act16_ksplit: workspace must be float32 of at least %d bytes" % nbytes)
+    y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv2d_f16_ksplit_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), ptr(workspace), s,
+         b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y
+
+
 def conv_transpose3x3s2_f16_act16(x_nhwc, packed16_mode1, cout, bias=None, relu=True, peak=None):
     hi, _, exp, _ = packed16_mode1
     x = _f16(x_nhwc)

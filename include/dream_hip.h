@@ -326,6 +326,28 @@ int dream_conv_transpose4x4s2_f16_nhwc_f16(const void *x, const void *w, const i
 int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *bias, void *y,
                                            unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
                                            int flags, void *stream);
+/* ---- split-K half-storage convs for small batches (DreamHourglass.conv_ksplit = "auto") -----------------------------------
+ * The tiles of dream_conv2d_f16_nhwc_f16 were measured at 128 frames; at the 1 .. 16 frames of the reference's own callers
+ * (dream/network.py keypoints_from_image: one frame) the grid of a deep layer is a few dozen workgroups on 256 CUs (the rule
+ * below splits at 1 .. 8 frames of 400 x 400; from 16 on every answer is 1).  The
+ * contraction Cin/32 x taps (up to 144 stages) is divided instead: S slices, each a contiguous range of stages run by its own
+ * workgroups, raw fp32 partial tiles in `workspace`, then one elementwise pass that adds the slices in the order 0 .. S-1 and
+ * applies the epilogue of the unsplit launch (2^-ew * scale, shift, ReLU, max|v| before the saturation into amax_out, half
+ * store).  No floating-point atomics: two runs give the same bits.  Plain convs only: a launch with DREAM_CONV_POOL2,
+ * DREAM_CONV_UPSAMPLE2X, DREAM_CONV_ZEROSTUFF2X or DREAM_CONV_OUT_NCHW is never split.
+ * dream_conv2d_f16_ksplit: S of a launch -- a host computation from fixed constants (no device is queried), 1 for every
+ * launch that is not split and for every conv of the hourglass at 128 frames of 400 x 400; non-increasing in B.
+ * dream_conv_f16_set_ksplit (test hook, per thread): -1 = the rule, n >= 1 = min(n, Cin/32 * taps) for every splittable launch.
+ * dream_conv2d_f16_ksplit_workspace: bytes of `workspace` for S slices.
+ * dream_conv2d_f16_ksplit_nhwc_f16: the arguments of dream_conv2d_f16_nhwc_f16 plus workspace (16-byte aligned) and S
+ * (1 <= S <= 1024; slices past the Cin/32 * taps stages are empty and hold zeros -- the rule and the hook never ask for
+ * them); S == 1 IS dream_conv2d_f16_nhwc_f16 (workspace unused); S > 1 with a refused flag is an error. */
+int dream_conv2d_f16_ksplit(int B, int H, int W, int Cin, int Cout, int ksize, int flags);
+size_t dream_conv2d_f16_ksplit_workspace(int B, int H, int W, int Cout, int S);
+int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                                     void *y, unsigned *amax_out, void *workspace, int S, int B, int H, int W, int Cin,
+                                     int Cout, int CoutPad, int ksize, int stride, int flags, void *stream);
+int dream_conv_f16_set_ksplit(int n);
 /* first encoder conv (dream/models.py:592-597): the fp32 arithmetic of dream_conv3x3_first_nchw_amax_f32, y half NHWC */
 int dream_conv3x3_first_nchw_f16(const float *x_nchw, const float *w_oihw, const float *bias, void *y_nhwc,
                                  unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int relu, void *stream);
