@@ -192,6 +192,12 @@ _SIGNATURES = {
     "dream_maxpool2_bwd_x16_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool2_relu_bwd_x16_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_widen_f16_f32": (_I, [_P, _P, _SZ, _P]),
+    "dream_conv2d_f16_g16_entry_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv2d_f16_g16_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv2d_f16_g16_exit_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_maxpool2_bwd_x16_dy16_nhwc_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "dream_maxpool2_relu_bwd_x16_dy16_nhwc_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_conv3x3_wgrad_winograd_workspace": (_SZ, [_I, _I, _I, _I, _I]),
     "dream_conv3x3_wgrad_winograd_nhwc_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv3x3_wgrad_winograd_fuses_bias": (_I, [_I, _I, _I]),

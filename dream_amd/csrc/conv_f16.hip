@@ -26,6 +26,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16P
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = false;
     constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 0;
 #include "conv_f16_body.inc"
 }
 
@@ -37,6 +38,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Co
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = false;
     constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 0;
 #include "conv_f16_body.inc"
 }
 
@@ -51,6 +53,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_act16_kernel(const C
     constexpr bool ACT16 = true;
     constexpr bool MASK16 = false;
     constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 0;
 #include "conv_f16_body.inc"
 }
 
@@ -62,6 +65,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask16_kernel(const 
     constexpr bool ACT16 = false;
     constexpr bool MASK16 = true;
     constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 0;
 #include "conv_f16_body.inc"
 }
 
@@ -75,6 +79,55 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_ksplit_kernel(const 
     constexpr bool ACT16 = true;
     constexpr bool MASK16 = false;
     constexpr bool KSPLIT = true;
+    constexpr int GRAD16 = 0;
+#include "conv_f16_body.inc"
+}
+
+// ---- data gradients stored as IEEE half (train_gradient_storage="fp16") ------------------------------------------
+// Every data gradient of the encoder's half run lives in HBM as half(clamp(g * 2^e_g)), e_g = grad_scale_exponent(*p.grad_amax) -- one
+// exponent per backward pass, derived by every launch from the loss gradient's amax (half_scale.h).  The chain is linear, so the factor
+// travels: GRAD16 = 1 "entry" (the boundary conv: fp32 g in, scaled by its own amax as conv_f16_kernel does; y * 2^e_g stored as half),
+// 2 "interior" (half g in and out: the stored half IS the operand -- ACT16's loader and saturating store --, no scale), 3 "exit" (half g
+// in, y * 2^-e_g stored as fp32, amax_out after the mask).  The mask, where there is one, is a half tensor (MASK16); the unmasked
+// interior form is conv_f16_act16_kernel itself.  amax_out of the half-writing forms: max|y * 2^e_g| of what is stored, before the
+// saturation.  Kernels of their own from the same text.
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_entry_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = false;
+    constexpr bool ACT16 = false;
+    constexpr bool MASK16 = false;
+    constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 1;
+#include "conv_f16_body.inc"
+}
+
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_entry_mask16_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = true;
+    constexpr bool ACT16 = false;
+    constexpr bool MASK16 = true;
+    constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 1;
+#include "conv_f16_body.inc"
+}
+
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_mask16_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = true;
+    constexpr bool ACT16 = true;
+    constexpr bool MASK16 = true;
+    constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 2;
+#include "conv_f16_body.inc"
+}
+
+template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_exit_kernel(const Conv16Params p) {
+    constexpr bool EPI_MASK = true;
+    constexpr bool ACT16 = true;
+    constexpr bool MASK16 = true;
+    constexpr bool KSPLIT = false;
+    constexpr int GRAD16 = 3;
 #include "conv_f16_body.inc"
 }
 
@@ -123,10 +176,13 @@ struct Variant16h {
     void (*act16_kernel)(const Conv16Params);
     void (*mask16_kernel)(const Conv16Params);
     void (*ksplit_kernel)(const Conv16Params);
+    void (*g16_kernel[4])(const Conv16Params);      // entry, entry + mask, interior + mask, exit
 };
 #define F16_KERNELS(...) \
     conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>, conv_f16_mask16_kernel<__VA_ARGS__>, \
-    conv_f16_ksplit_kernel<__VA_ARGS__>
+    conv_f16_ksplit_kernel<__VA_ARGS__>, \
+    {conv_f16_g16_entry_kernel<__VA_ARGS__>, conv_f16_g16_entry_mask16_kernel<__VA_ARGS__>, conv_f16_g16_mask16_kernel<__VA_ARGS__>, \
+     conv_f16_g16_exit_kernel<__VA_ARGS__>}
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -166,13 +222,20 @@ constexpr int kKsplitTargetWorkgroups = 384;
 constexpr int kKsplitMinStages = 24;
 constexpr int kKsplitMax = 16;
 
-// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used; mask16: the ReLU mask (`residual`) is a half tensor
+// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used; mask16: the ReLU mask (`residual`) is a half tensor;
+// grad16 = 1 | 2 | 3: the entry / interior / exit form of a half-stored data gradient (the GRAD16 kernels; act16 then says that x is
+// half: forms 2 and 3), grad_amax the scalar e_g is derived from
 int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
                const float *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
-               int flags, void *stream, bool act16 = false, bool mask16 = false, int ksplit = 0) {
+               int flags, void *stream, bool act16 = false, bool mask16 = false, int ksplit = 0, int grad16 = 0,
+               const unsigned *grad_amax = nullptr) {
     DREAM_REQUIRE(x && (amax_in || act16) && w && w_exp && y, "conv_f16: null pointer");
-    DREAM_REQUIRE(!act16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
-    DREAM_REQUIRE(!act16 || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
+    DREAM_REQUIRE(!act16 || grad16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
+    DREAM_REQUIRE(!(act16 || grad16) || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
+    DREAM_REQUIRE(grad16 == 0 || (grad16 >= 1 && grad16 <= 3 && act16 == (grad16 != 1) && ksplit == 0 && scale == nullptr && shift == nullptr
+                                  && (grad16 == 2 || grad_amax != nullptr) && (flags & ~DREAM_CONV_RELUMASK) == 0 && g.out_scale == 1
+                                  && (residual == nullptr || (mask16 && ((size_t)residual & 3) == 0)) && (grad16 == 1 || residual != nullptr)),
+                  "conv_f16: a half-stored data gradient is a plain conv with an optional half mask");
     DREAM_REQUIRE(Cin % KC == 0, "conv_f16: Cin=%d must be a multiple of %d", Cin, KC);
     Conv16Params p;
     p.x = (const float *)x; p.w_hi = (const _Float16 *)w; p.w_lo = nullptr; p.w_exp = w_exp; p.amax_in = amax_in;
@@ -189,12 +252,15 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     const bool mask = (flags & DREAM_CONV_RELUMASK) != 0;
     DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
-    DREAM_REQUIRE(!mask16 || (mask && !act16), "conv_f16: a half mask goes with DREAM_CONV_RELUMASK on fp32 activations");
+    DREAM_REQUIRE(!mask16 || (mask && (!act16 || grad16)), "conv_f16: a half mask goes with DREAM_CONV_RELUMASK on fp32 activations");
+    DREAM_REQUIRE(!grad16 || mask == (residual != nullptr), "conv_f16: the mask of a half-stored data gradient goes with DREAM_CONV_RELUMASK");
     // ksplit > 0: that many slices of the contraction, y = the fp32 workspace (dream_conv2d_f16_ksplit_nhwc_f16)
     DREAM_REQUIRE(ksplit == 0 || (act16 && !(flags & kKsplitRefused) && g.out_scale == 1 && ksplit <= 1024),
                   "conv_f16: a split launch is a plain half-storage conv of at most 1024 slices");
+    if (grad16) p.grad_amax = grad_amax;           // (shares w_lo's slot, which these kernels do not read)
     void (*const kernel)(const Conv16Params) =
-        ksplit ? var.ksplit_kernel : (act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel));
+        grad16 ? var.g16_kernel[grad16 == 1 ? (mask ? 1 : 0) : grad16]
+               : ksplit ? var.ksplit_kernel : (act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel));
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
@@ -311,6 +377,45 @@ extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void 
             return rc;
     }
     return 0;
+}
+
+// ---- data gradients stored as IEEE half (train_gradient_storage="fp16") ------------------------------------------
+// Three forms of the 3x3 stride-1 conv with the mode-1 packed plane.  grad_amax: device scalar, bit pattern of the loss gradient's
+// amax; every launch of one backward derives e_g = 9 - exponent from it (0 for a zero scalar, clamped to +-100).  mask: [B,H,W,Cout]
+// half or null, y = mask > 0 ? conv : 0.  peak (optional, not zeroed): max|v| of what a half-writing launch stores, before the
+// saturation.  Half tensors must be 16-byte aligned.
+// entry: x fp32, scaled by its own amax_in as dream_conv2d_f16_nhwc_f32 does -> y = half(clamp(conv * 2^e_g))
+extern "C" int dream_conv2d_f16_g16_entry_nhwc_f16(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
+                                                   const void *mask, void *y, const unsigned *grad_amax, unsigned *peak, int B, int H,
+                                                   int W, int Cin, int Cout, int CoutPad, int ksize, int stride, int flags, void *stream) {
+    DREAM_REQUIRE(ksize == 3 && stride == 1 && flags == 0, "conv2d_f16_g16_entry: a plain 3x3 stride-1 conv (flags 0)");
+    DREAM_REQUIRE(grad_amax != nullptr, "conv2d_f16_g16_entry: needs the loss gradient's amax");
+    const int fl = mask ? DREAM_CONV_RELUMASK : 0;
+    const Geom16 g = geom16_conv(H, W, ksize, fl);
+    return launch_f16(x, amax_in, w, w_exp, nullptr, nullptr, (const float *)mask, y, peak, B, Cin, Cout, CoutPad, g, fl, stream, false,
+                      mask != nullptr, 0, 1, grad_amax);
+}
+
+// interior: x half (already times 2^e_g) -> y = half(clamp(conv)): no scale is read.  Without a mask this IS dream_conv2d_f16_nhwc_f16.
+extern "C" int dream_conv2d_f16_g16_nhwc_f16(const void *x, const void *w, const int *w_exp, const void *mask, void *y, unsigned *peak,
+                                             int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize, int stride, int flags,
+                                             void *stream) {
+    DREAM_REQUIRE(ksize == 3 && stride == 1 && flags == 0, "conv2d_f16_g16: a plain 3x3 stride-1 conv (flags 0)");
+    const Geom16 g = geom16_conv(H, W, ksize, 0);
+    if (mask == nullptr) return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, nullptr, y, peak, B, Cin, Cout, CoutPad, g, 0, stream, true);
+    return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, (const float *)mask, y, peak, B, Cin, Cout, CoutPad, g, DREAM_CONV_RELUMASK,
+                      stream, true, true, 0, 2, nullptr);
+}
+
+// exit: x half (times 2^e_g), mask required -> y = (mask > 0 ? conv : 0) * 2^-e_g as fp32; amax_out = max|y| after the mask
+extern "C" int dream_conv2d_f16_g16_exit_nhwc_f32(const void *x, const void *w, const int *w_exp, const void *mask, float *y,
+                                                  const unsigned *grad_amax, unsigned *amax_out, int B, int H, int W, int Cin, int Cout,
+                                                  int CoutPad, int ksize, int stride, int flags, void *stream) {
+    DREAM_REQUIRE(ksize == 3 && stride == 1 && flags == 0, "conv2d_f16_g16_exit: a plain 3x3 stride-1 conv (flags 0)");
+    DREAM_REQUIRE(mask != nullptr && grad_amax != nullptr, "conv2d_f16_g16_exit: needs the mask and the loss gradient's amax");
+    const Geom16 g = geom16_conv(H, W, ksize, DREAM_CONV_RELUMASK);
+    return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, (const float *)mask, y, amax_out, B, Cin, Cout, CoutPad, g,
+                      DREAM_CONV_RELUMASK, stream, true, true, 0, 3, grad_amax);
 }
 
 // ---- conv_ksplit="auto": the contraction of a small-grid conv divided over workgroups ---------------------------

@@ -1,11 +1,12 @@
-// Body of conv_f16_kernel / conv_f16_mask_kernel / conv_f16_act16_kernel / conv_f16_mask16_kernel (conv_f16.hip), included once per kernel so that the plain kernels keep the machine code
+// Body of conv_f16_kernel / conv_f16_mask_kernel / conv_f16_act16_kernel / conv_f16_mask16_kernel / conv_f16_ksplit_kernel / conv_f16_g16_*_kernel (conv_f16.hip), included once per kernel so that the plain kernels keep the machine code
 // that was measured (as conv_wino_body.inc).  In scope: the template parameters MR, NR, WM, WN, NPM, DB, PRIO, the argument p, and
 // EPI_MASK (bool constant: the DREAM_CONV_RELUMASK epilogue) and ACT16 (bool constant: activations live in HBM as IEEE half --
 // p.x and an NHWC p.y point to halfs; the patch is copied, not converted: 16-byte pieces of 8 halfs, no input scale) and MASK16
 // (bool constant, read by the epilogue: the ReLU mask of EPI_MASK is a tensor of IEEE halfs) and KSPLIT (bool constant, with ACT16:
 // slice blockIdx.z of the gridDim.z slices of the contraction -- a contiguous range of the (channel chunk, tap) stages, the leftover
 // spread over the first slices -- whose raw fp32 accumulators go to p.y = workspace[slice] in NHWC fp32: no scale, no shift, no ReLU,
-// no peak; conv_f16_ksplit_finish_kernel sums the slices and runs the epilogue).
+// no peak; conv_f16_ksplit_finish_kernel sums the slices and runs the epilogue) and GRAD16 (int constant, read by the epilogue: the
+// entry / interior / exit form of a half-stored data gradient, 0 otherwise; the loader follows ACT16 as ever).
     constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
     constexpr int BN = 32 * NR * WN;
     constexpr int QW = ACT16 ? 8 : 4;               // elements of a 16-byte piece

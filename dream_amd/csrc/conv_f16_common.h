@@ -5,12 +5,16 @@
 #include <dream_cdna4.h>
 #include "common.h"
 #include "half_store.h"
+#include "half_scale.h"
 #include "../../include/dream_hip.h"
 
 struct Conv16Params {
     const float *x;
     const _Float16 *w_hi;    // [ntaps][CoutPad][Cin]
-    const _Float16 *w_lo;    // (split kernel only)
+    union {                  // (one slot, so that the layout every measured kernel was compiled against stays)
+        const _Float16 *w_lo;       // (split kernel only)
+        const unsigned *grad_amax;  // (the GRAD16 kernels of conv_f16.hip only) device scalar: bit pattern of the loss gradient's amax
+    };
     const int *w_exp;        // device scalar: weights were multiplied by 2^w_exp before the split
     const unsigned *amax_in; // device scalar: bit pattern of max|x| of the input tensor
     const float *scale;

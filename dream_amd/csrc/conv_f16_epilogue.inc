@@ -6,7 +6,15 @@
 // ACT16 (the half-storage kernels of conv_f16.hip): an NHWC y is IEEE half -- the same value, saturated to +-65504 and rounded to
 // nearest even (sat_half); max|y| is taken BEFORE the saturation, so the side channel tells a caller that it happened.  The NCHW
 // output (the K-channel belief maps) stays fp32.
+// GRAD16 (int constant; conv_f16.hip, 0 everywhere else): the forms of a half-stored data gradient -- 1 entry: y * 2^e_g stored as half
+// whatever ACT16 says (x is fp32); 2 interior: ACT16's store with MASK16's mask; 3 exit: y * 2^-e_g stored as fp32 (x is half).
     // ---- epilogue -----------------------------------------------------------------------------------------
+    constexpr bool OUT16 = GRAD16 == 0 ? ACT16 : GRAD16 != 3;      // an NHWC y is IEEE half
+    float gs = 1.0f;                                               // (GRAD16 entry / exit) 2^e_g / 2^-e_g, applied to the finished value
+    if constexpr (GRAD16 == 1 || GRAD16 == 3) {
+        const int eg = grad_scale_exponent(*p.grad_amax);
+        gs = pow2f(GRAD16 == 1 ? eg : -eg);
+    }
     const bool relu = (p.flags & DREAM_CONV_RELU) != 0;
     const bool nchw = (p.flags & DREAM_CONV_OUT_NCHW) != 0;
     float scale_v[NR], shift_v[NR];
@@ -26,7 +34,7 @@
     // first tile row of the two, the odd lane those of the second -- half the store instructions, 4 bytes per lane (+2 .. +9 % on the
     // layer; the pooled form, a quarter of the stores to begin with, measured no gain and keeps the plain store:
     // profiles/ab_act16_store.txt).  Every lane runs every exchange (the validity tests only guard the stores).
-    if constexpr (ACT16) {
+    if constexpr (OUT16) {
         if (!nchw && !pool && (p.Cout & 1) == 0) {
             stored = true;
             typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
@@ -55,11 +63,31 @@
                         for (int j = 0; j < 2; ++j) {
                             v[j] = acc[ms][ns][2 * r2 + j] * scale_v[ns] + shift_v[ns];
                             if (relu) v[j] = fmaxf(v[j], 0.0f);
-                            if (ok[j] && cok) amax = fmaxf(amax, fabsf(v[j]));
+                            if constexpr (GRAD16 == 1) v[j] *= gs;
+                            if constexpr (GRAD16 == 0) {
+                                if (ok[j] && cok) amax = fmaxf(amax, fabsf(v[j]));
+                            }
                         }
                         const float got = quad_perm_1032(odd ? v[0] : v[1]);
-                        const f16x2_ h = {sat_half(odd ? got : v[0]), sat_half(odd ? v[1] : got)};
-                        if (ok[odd] && cok) *(f16x2_ *)(yh + pix[odd] * p.Cout + (ncol[ns] & ~1)) = h;
+                        if constexpr (GRAD16 != 0) {
+                            // the lane's two channels of pixel pix[odd]: the half mask is read as the pair that is stored, the peak is
+                            // taken after the mask, of what is stored
+                            float a0 = odd ? got : v[0], a1 = odd ? v[1] : got;
+                            if (ok[odd] && cok) {
+                                const size_t o2 = pix[odd] * p.Cout + (ncol[ns] & ~1);
+                                if constexpr (EPI_MASK) {
+                                    const f16x2_ mk = *(const f16x2_ *)((const _Float16 *)p.residual + o2);
+                                    a0 = (float)mk[0] > 0.0f ? a0 : 0.0f;
+                                    a1 = (float)mk[1] > 0.0f ? a1 : 0.0f;
+                                }
+                                amax = fmaxf(amax, fmaxf(fabsf(a0), fabsf(a1)));
+                                const f16x2_ h = {sat_half(a0), sat_half(a1)};
+                                *(f16x2_ *)(yh + o2) = h;
+                            }
+                        } else {
+                            const f16x2_ h = {sat_half(odd ? got : v[0]), sat_half(odd ? v[1] : got)};
+                            if (ok[odd] && cok) *(f16x2_ *)(yh + pix[odd] * p.Cout + (ncol[ns] & ~1)) = h;
+                        }
                     }
                 }
             }
@@ -82,11 +110,12 @@
                             ? (((size_t)b * p.Cout + ncol[ns]) * p.Ho + oy) * p.Wo + ox
                             : (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
                         float v = acc[ms][ns][r] * scale_v[ns] + shift_v[ns];
+                        if constexpr (GRAD16 == 1 || GRAD16 == 3) v *= gs;
                         if constexpr (EPI_MASK && MASK16) v = (float)((const _Float16 *)p.residual)[o] > 0.0f ? v : 0.0f;
                         else if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
                         else if (p.residual != nullptr) v = v + p.residual[o];
                         if (relu) v = fmaxf(v, 0.0f);
-                        if constexpr (ACT16) {
+                        if constexpr (OUT16) {
                             if (nchw) p.y[o] = v;
                             else ((_Float16 *)p.y)[o] = sat_half(v);
                         } else {
@@ -116,7 +145,7 @@
                             best = fmaxf(best, v);
                         }
                         const size_t o = (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.Cout + ncol[ns];
-                        if constexpr (ACT16) ((_Float16 *)p.y)[o] = sat_half(best);
+                        if constexpr (OUT16) ((_Float16 *)p.y)[o] = sat_half(best);
                         else p.y[o] = best;
                         amax = fmaxf(amax, fabsf(best));
                     }

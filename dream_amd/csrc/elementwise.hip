@@ -745,6 +745,46 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_x16_kernel(const f32x4 *dy, 
     }
 }
 
+// ... and with dy and dx half as well (train_gradient_storage="fp16": the gradients of the run are stored as half times 2^e_g): 8 halfs
+// (16 bytes) per lane and window element.  Exact -- every dx is a copy of a dy or zero --, so no scale is read and none is applied.
+template <bool RELU>
+__global__ void __launch_bounds__(256) maxpool2_bwd_x16_dy16_kernel(const f16x8 *dy, const f16x8 *x, f16x8 *dx, int B, int H, int W, int C8) {
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t total = (size_t)B * Ho * Wo * C8;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        size_t r = i / C8;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c, row = (size_t)W * C8;
+        const f16x8 v[4] = {x[base], x[base + C8], x[base + row], x[base + row + C8]};
+        const f16x8 g = dy[i];
+        f16x8 o[4] = {zero, zero, zero, zero};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            int arg = 0;
+            float best = (float)v[0][k];
+#pragma unroll
+            for (int j = 1; j < 4; ++j)
+                if ((float)v[j][k] > best) { best = (float)v[j][k]; arg = j; }
+            const _Float16 gk = (!RELU || best > 0.0f) ? g[k] : (_Float16)0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : (_Float16)0;
+        }
+        dx[base] = o[0];
+        dx[base + C8] = o[1];
+        dx[base + row] = o[2];
+        dx[base + row + C8] = o[3];
+        const bool last_x = (ox == Wo - 1) && (W & 1), last_y = (oy == Ho - 1) && (H & 1);
+        if (last_x) { dx[base + 2 * C8] = zero; dx[base + row + 2 * C8] = zero; }
+        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + C8] = zero; }
+        if (last_x && last_y) dx[base + 2 * row + 2 * C8] = zero;
+    }
+}
+
 // out = float(x): the widening pass behind the last half-storage conv of a training forward (exact); 8 halfs per lane
 __global__ void __launch_bounds__(256) widen_f16_kernel(const _Float16 *x, float *out, size_t n) {
     const size_t n8 = n / 8;
@@ -854,6 +894,26 @@ extern "C" int dream_maxpool2_relu_bwd_x16_nhwc_f32(const float *dy, const void 
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool2_bwd_x16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                        (const f32x4 *)dy, (const f16x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+// ... with dy and dx stored as IEEE half too (train_gradient_storage="fp16"): dy [B,H/2,W/2,C], x, dx [B,H,W,C] half, 16-byte aligned,
+// C % 8 == 0; exact (a copy or zero)
+extern "C" int dream_maxpool2_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_bwd_x16_dy16: bad arguments (C %% 8)");
+    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 15) == 0, "maxpool2_bwd_x16_dy16: dy, x, dx must be 16-byte aligned");
+    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
+    hipLaunchKernelGGL(maxpool2_bwd_x16_dy16_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16x8 *)dy, (const f16x8 *)x, (f16x8 *)dx, B, H, W, C / 8);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_maxpool2_relu_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_relu_bwd_x16_dy16: bad arguments (C %% 8)");
+    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 15) == 0, "maxpool2_relu_bwd_x16_dy16: dy, x, dx must be 16-byte aligned");
+    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
+    hipLaunchKernelGGL(maxpool2_bwd_x16_dy16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16x8 *)dy, (const f16x8 *)x, (f16x8 *)dx, B, H, W, C / 8);
     DREAM_LAUNCH_OK();
     return 0;
 }

@@ -23,6 +23,7 @@
 // floating-point atomics) and applies 2^-ex * 2^-eg.
 #include <dream_cdna4.h>
 #include "common.h"
+#include "half_scale.h"
 #include "../../include/dream_hip.h"
 
 namespace {
@@ -46,14 +47,9 @@ struct Wgrad16Params {
 
 DREAM_DEVICE float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 
-// e with max|t| * 2^e in [2^13, 2^14): 13 - exponent, clamped to +-100; 0 for a zero tensor (conv_f16.hip)
-DREAM_DEVICE int scale_exponent(unsigned amax_bits) {
-    const int e = (amax_bits == 0u) ? 0 : 13 - ((int)((amax_bits >> 23) & 255) - 127);
-    return e < -100 ? -100 : (e > 100 ? 100 : e);
-}
-
 __global__ void __launch_bounds__(256, 2) wgrad_f16_kernel(const Wgrad16Params p) {
     constexpr bool X16 = false;
+    constexpr bool DY16 = false;
 #include "wgrad_f16_body.inc"
 }
 
@@ -61,6 +57,16 @@ __global__ void __launch_bounds__(256, 2) wgrad_f16_kernel(const Wgrad16Params p
 // staging bytes, no v_cvt, no multiply.  A kernel of its own from the same text, so that the one above stays instruction-identical.
 __global__ void __launch_bounds__(256, 2) wgrad_f16_x16_kernel(const Wgrad16Params p) {
     constexpr bool X16 = true;
+    constexpr bool DY16 = false;
+#include "wgrad_f16_body.inc"
+}
+
+// ... and on a dy stored as IEEE half times 2^e_g (train_gradient_storage="fp16"; dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32): the stored
+// half IS the operand -- dy staging copies 8-byte pieces of four halfs: half the bytes, no v_cvt, no multiply; amax_dy is not read.
+// The bias partial is the fp32 channel sum of the stored halfs.  2^-e_g is applied by wgrad_f16_reduce_g16_kernel.
+__global__ void __launch_bounds__(256, 2) wgrad_f16_x16_dy16_kernel(const Wgrad16Params p) {
+    constexpr bool X16 = true;
+    constexpr bool DY16 = true;
 #include "wgrad_f16_body.inc"
 }
 
@@ -82,6 +88,28 @@ __global__ void __launch_bounds__(256) wgrad_f16_reduce_kernel(const float *part
         }
         for (; k < splitk; ++k) s += src[(size_t)k * n4];
         ((f32x4 *)out)[i] = (s * ix) * ig;
+    }
+}
+
+// wgrad_f16_reduce_kernel for the launches of wgrad_f16_x16_dy16_kernel (weights and bias): the same fixed-order sum, times 2^-e_g where
+// that kernel applies 2^-eg -- e_g = grad_scale_exponent of the loss gradient's amax (half_scale.h), an exact power of two.
+__global__ void __launch_bounds__(256) wgrad_f16_reduce_g16_kernel(const float *part, float *out, size_t n, int splitk,
+                                                                   const unsigned *grad_amax) {
+    const float ig = pow2f(-grad_scale_exponent(*grad_amax));
+    const size_t n4 = n / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+        const f32x4 *src = (const f32x4 *)part + i;
+        int k = 0;
+        for (; k + 8 <= splitk; k += 8) {
+            f32x4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(k + j) * n4];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[j];
+        }
+        for (; k < splitk; ++k) s += src[(size_t)k * n4];
+        ((f32x4 *)out)[i] = s * ig;
     }
 }
 
@@ -114,17 +142,20 @@ extern "C" size_t dream_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin
 
 namespace {
 
-// x16: x is IEEE half (wgrad_f16_x16_kernel), amax_x is not used and the reduce takes a null amax_x (factor 1)
-int launch_wgrad16(const void *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy, float *dw_packed, float *dbias,
-                   void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad, int flags, void *stream, bool x16) {
+// x16: x is IEEE half (wgrad_f16_x16_kernel), amax_x is not used and the reduce takes a null amax_x (factor 1); dy16 (with x16): dy is
+// IEEE half times 2^e_g (wgrad_f16_x16_dy16_kernel) and amax_dy is the scalar e_g is derived from: the loss gradient's amax
+int launch_wgrad16(const void *x, const unsigned *amax_x, const void *dy, const unsigned *amax_dy, float *dw_packed, float *dbias,
+                   void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad, int flags, void *stream, bool x16,
+                   bool dy16 = false) {
     DREAM_REQUIRE(x && (amax_x || x16) && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
     DREAM_REQUIRE(flags == 0, "wgrad_f16: flags %d not supported (plain 3x3 stride-1 convs only)", flags);
     DREAM_REQUIRE(shape_ok(B, H, W, Cin, RowsPad) && Cdy > 0 && Cdy % 4 == 0 && RowsPad >= Cdy,
                   "wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdy %d, pad %d): Cin %% 32, Cdy %% 4, pad %% 64", B, H, W, Cin, Cdy, RowsPad);
     DREAM_REQUIRE((size_t)B * H * W * (size_t)(Cin > Cdy ? Cin : Cdy) < ((size_t)1 << 40), "wgrad_f16: tensor too large");
     DREAM_REQUIRE(!x16 || ((size_t)x & 15) == 0, "wgrad_f16: a half x must be 16-byte aligned");
+    DREAM_REQUIRE(!dy16 || (x16 && ((size_t)dy & 15) == 0), "wgrad_f16: a half dy goes with a half x and must be 16-byte aligned");
     Wgrad16Params p;
-    p.x = (const float *)x; p.dy = dy; p.amax_x = x16 ? nullptr : amax_x; p.amax_dy = amax_dy;
+    p.x = (const float *)x; p.dy = (const float *)dy; p.amax_x = x16 ? nullptr : amax_x; p.amax_dy = amax_dy;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Ct = Cdy; p.RowsPad = RowsPad;
     p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
     p.tiles_total = B * p.tiles_x * p.tiles_y;
@@ -133,7 +164,7 @@ int launch_wgrad16(const void *x, const unsigned *amax_x, const float *dy, const
     p.part = (float *)workspace;
     float *bias_part = p.part + (size_t)p.splitk * 9 * RowsPad * Cin;
     p.bias_part = dbias ? bias_part : nullptr;
-    void (*const kernel)(const Wgrad16Params) = x16 ? wgrad_f16_x16_kernel : wgrad_f16_kernel;
+    void (*const kernel)(const Wgrad16Params) = dy16 ? wgrad_f16_x16_dy16_kernel : (x16 ? wgrad_f16_x16_kernel : wgrad_f16_kernel);
     if (dream_allow_full_lds((const void *)kernel)) return 2;
     const dim3 grid((unsigned)(p.nrb * p.ncb * ceil_div(p.splitk, 8) * 8));
     hipLaunchKernelGGL(kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
@@ -141,14 +172,22 @@ int launch_wgrad16(const void *x, const unsigned *amax_x, const float *dy, const
     const size_t n = (size_t)9 * RowsPad * Cin;
     size_t gr = (n / 4 + 255) / 256;
     if (gr > 2048) gr = 2048;
-    hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part, dw_packed,
-                       n, p.splitk, p.amax_x, amax_dy);
+    if (dy16)
+        hipLaunchKernelGGL(wgrad_f16_reduce_g16_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part,
+                           dw_packed, n, p.splitk, amax_dy);
+    else
+        hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part, dw_packed,
+                           n, p.splitk, p.amax_x, amax_dy);
     DREAM_LAUNCH_OK();
     if (dbias) {
         // bias partials are [splitk][RowsPad] of unscaled sums; only the first Cdy entries are wanted
         float *total = bias_part + (size_t)p.splitk * RowsPad;
-        hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
-                           (size_t)RowsPad, p.splitk, (const unsigned *)nullptr, (const unsigned *)nullptr);
+        if (dy16)              // the channel sums of the stored halfs carry 2^e_g as well
+            hipLaunchKernelGGL(wgrad_f16_reduce_g16_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
+                               (size_t)RowsPad, p.splitk, amax_dy);
+        else
+            hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
+                               (size_t)RowsPad, p.splitk, (const unsigned *)nullptr, (const unsigned *)nullptr);
         DREAM_LAUNCH_OK();
         if (dream_copy_words(dbias, total, (size_t)Cdy * sizeof(float), (hipStream_t)stream)) return 2;
     }
@@ -172,4 +211,14 @@ extern "C" int dream_conv3x3_wgrad_f16_x16_nhwc_f32(const void *x, const float *
                                                     float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
                                                     int RowsPad, int flags, void *stream) {
     return launch_wgrad16(x, nullptr, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, true);
+}
+
+// The same with dy stored as IEEE half as well (train_gradient_storage="fp16"): dy [B,H,W,Cdy] half, 16-byte aligned, holds the gradient
+// times 2^e_g and is the operand as it is (no amax of dy is read); grad_amax: device scalar, bit pattern of the loss gradient's amax,
+// from which e_g = 9 - exponent is derived as by every launch of that backward.  dw and dbias (the fp32 channel sum of the stored halfs)
+// are multiplied by 2^-e_g once, in the reduce kernel.  Workspace, split and summation order are those of the other two forms.
+extern "C" int dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32(const void *x, const void *dy, const unsigned *grad_amax, float *dw_packed,
+                                                         float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
+                                                         int RowsPad, int flags, void *stream) {
+    return launch_wgrad16(x, nullptr, dy, grad_amax, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, true, true);
 }

@@ -1,7 +1,8 @@
 // Body of wgrad_f16_kernel / wgrad_f16_x16_kernel (wgrad_f16.hip), included once per kernel so that the fp32-x kernel keeps the machine
 // code that was measured (as conv_f16_body.inc).  In scope: the argument p and X16 (bool constant: x lives in HBM as IEEE half --
 // train_activation_storage="fp16"; p.x points to halfs, and the stored half IS the operand: a lane copies its four channels (8 bytes) of
-// each of the 10 positions, no convert, no multiply, ex = 0, amax_x is not read).
+// each of the 10 positions, no convert, no multiply, ex = 0, amax_x is not read) and DY16 (bool constant, with X16: dy lives in HBM as
+// IEEE half times 2^e_g -- train_gradient_storage="fp16"; p.dy points to halfs that are copied the same way, amax_dy is not read).
     DREAM_DYNAMIC_LDS(_Float16, smem);
     _Float16 *sY = smem;                  // [RW][SY]
     _Float16 *sX = smem + RW * SY;        // [3][CW][SX]
@@ -17,7 +18,8 @@
     const int co0 = rbk * RW, ci0 = cbk * CW;
     float sx = 1.0f;                                 // (X16: the stored half is the operand, amax_x is not read)
     if constexpr (!X16) sx = pow2f(scale_exponent(*p.amax_x));
-    const float sg = pow2f(scale_exponent(*p.amax_dy));
+    float sg = 1.0f;                                 // (DY16: the stored half is the operand, amax_dy is not read)
+    if constexpr (!DY16) sg = pow2f(scale_exponent(*p.amax_dy));
 
     f32x16 acc[9];
 #pragma unroll
@@ -42,10 +44,31 @@
         const float *xb = p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;
         const _Float16 *xh = (const _Float16 *)p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;      // (X16)
         const float *gb = p.dy + (size_t)b * p.H * p.W * p.Ct + co0 + q * 4;
+        const _Float16 *gh = (const _Float16 *)p.dy + (size_t)b * p.H * p.W * p.Ct + co0 + q * 4;     // (DY16)
 
         __syncthreads();                             // previous tile fully consumed
         // ---- dy: 8 consecutive positions x 4 channels per thread (loads from clamped, always-legal addresses + a select) -----------
-        {
+        if constexpr (DY16) {
+            // a copy: the producer rounded; the bias sums the stored halfs in fp32, in the order of the fp32 form
+            const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
+            const f16x4 zero4h = {0, 0, 0, 0};
+            f16x4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const bool ok = y_chan_ok && oy < p.H && ox0 + j < p.W;
+                v[j] = *(const f16x4 *)(ok ? gh + ((size_t)oy * p.W + ox0 + j) * p.Ct : (const _Float16 *)p.dy);
+                v[j] = ok ? v[j] : zero4h;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) bsum[c] += (float)v[j][c];
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f16x8 h;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) h[j] = v[j][c];
+                *(f16x8 *)(sY + (q * 4 + c) * SY + grp * 8) = h;
+            }
+        } else {
             const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
             f32x4 v[8];
 #pragma unroll

@@ -430,8 +430,8 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_activation_storage", "conv_algorithm",
-                         "conv1x1_algorithm", "convT_algorithm"):
+            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_activation_storage",
+                         "train_gradient_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))
         src = self.module._dream_flat
@@ -783,6 +783,12 @@ class DreamDataParallel(nn.Module):
         device wanted to store with activation_storage="fp16" (>= 65504: that forward saturated somewhere)."""
         n = getattr(self, "_last_shards", 1)
         return max(m.half_storage_peak() for m in [self.module] + list(self._replicas[:n - 1]))
+
+    def half_gradient_peak(self):
+        """DreamHourglass.half_gradient_peak() of the last backward over every replica that took a chunk of the step: the largest value
+        any device wanted to store with train_gradient_storage="fp16" (>= 65504: a gradient of that step saturated somewhere)."""
+        n = getattr(self, "_last_shards", 1)
+        return max(m.half_gradient_peak() for m in [self.module] + list(self._replicas[:n - 1]))
 
     def forward(self, x, *args, **kwargs):
         object.__setattr__(self, "_last_shards", 1)

@@ -213,6 +213,15 @@ class DreamHourglass(nn.Module):
         # launches and read as half by the backward (wgrad_f16.hip X16, conv_f16.hip MASK16, elementwise.hip).  "fp32"
         # (default): every saved activation is fp32.  Read once per training forward; inference ignores it.  See half_storage_peak().
         self.train_activation_storage = "fp32"
+        # Training with train_precision="fp16" and train_activation_storage="fp16" only: "fp16" = the DATA GRADIENTS that run_backward hands
+        # from entry to entry through that half run live in HBM as IEEE half too (_half_gradient_plan: the gradient with respect to every
+        # half-stored activation but the output of plan entry 0; for vgg_q conv1_2 .. conv5_3 and the pooled tensors), all times ONE power
+        # of two 2^e_g per backward pass, derived on the device from the amax of the loss gradient (csrc/half_scale.h; conv_f16.hip
+        # GRAD16, wgrad_f16.hip DY16, elementwise.hip): no absmax pass runs inside the run.  "fp32" (default): every
+        # gradient is fp32.  Read once per training forward; inference ignores it.  See half_gradient_peak().
+        self.train_gradient_storage = "fp32"
+        self._half_grad_peaks = {}           # device -> the backward's peak scalar (as _half_peaks: persistent, zeroed in place by every such
+        self._half_grad_peak = None          # backward); the last one used
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
         # implicit-GEMM kernel everywhere (csrc/conv_mfma.hip, the reference form)
@@ -379,6 +388,30 @@ class DreamHourglass(nn.Module):
         else:
             self._half_peak.zero_()
         return self._half_peak
+
+    def _half_gradient_plan(self, store16=None):
+        """The rule of train_gradient_storage="fp16" -> the set of plan indices the gradient with respect to whose OUTPUT is stored as
+        IEEE half: the activation itself is half-stored (_half_storage_plan) and it is not the output of plan entry 0 (the first
+        conv's weight gradient reads an fp32 dy)."""
+        return {li for li in (self._half_storage_plan() if store16 is None else store16) if li != 0}
+
+    def _zeroed_half_grad_peak(self, device):
+        """The backward's one peak scalar on ``device``, zeroed in place (created on first use)."""
+        self._half_grad_peak = self._half_grad_peaks.get(device)
+        if self._half_grad_peak is None:
+            self._half_grad_peak = self._half_grad_peaks[device] = ops.new_amax(device)
+        else:
+            self._half_grad_peak.zero_()
+        return self._half_grad_peak
+
+    def half_gradient_peak(self):
+        """The largest |g * 2^e_g|, before saturation, that any launch of the last backward with train_gradient_storage="fp16" wanted to
+        store as a half (this module's own backward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_gradient_peak()).
+        >= 65504: a gradient of that step saturated -- go back to train_gradient_storage="fp32".  Reading it is the mode's only host
+        synchronisation, and happens only here."""
+        if self._half_grad_peak is None:
+            raise RuntimeError("half_gradient_peak(): no backward with train_gradient_storage=\"fp16\" has run")
+        return float(self._half_grad_peak.cpu().view(torch.float32)[0])
 
     # ---- which plan entries run as one -----------------------------------------------------------------------------------
     def _fuse_pool(self, layers, li, x_nhwc, split):
@@ -561,6 +594,15 @@ class DreamHourglass(nn.Module):
                                      % (self.train_precision,))
                 store16 = self._half_storage_plan()
                 self._zeroed_half_peak(x.device)
+            if self.train_gradient_storage not in ("fp32", "fp16"):
+                raise ValueError("unknown train_gradient_storage %r (\"fp32\" or \"fp16\")" % (self.train_gradient_storage,))
+            if self.train_gradient_storage == "fp16":
+                if not half or self.train_activation_storage != "fp16":
+                    raise ValueError("train_gradient_storage=\"fp16\" needs train_precision=\"fp16\" and train_activation_storage=\"fp16\" "
+                                     "(they are %r and %r)" % (self.train_precision, self.train_activation_storage))
+                saved.grad16 = self._half_gradient_plan(store16)
+                if any(layers[li][0] == "pool" and li - 1 not in saved.grad16 for li in saved.grad16):
+                    raise ValueError("train_gradient_storage=\"fp16\": a max-pool directly behind the first conv is not built")
         act, amax, li = x, x_amax, 0
         while li < len(layers):
             kind, mod, flags = layers[li]
@@ -628,6 +670,11 @@ class DreamHourglass(nn.Module):
         input_px = int(sh[0]) * (int(sh[2]) * int(sh[3]) if layers[0][0] == "first" else int(sh[1]) * int(sh[2]))
         side = _SideStream.create(grad_out_nchw, self.overlap_wgrad and input_px <= self.OVERLAP_MAX_PIXELS)
         g = g_input = None
+        # train_gradient_storage="fp16" (as the forward recorded it): one amax of the loss gradient, from which every launch of the run
+        # derives the exponent e_g its half gradients are stored with; no host synchronisation, no state from step to step
+        grad16 = saved.grad16
+        eg_amax = ops.absmax(grad_out_nchw) if grad16 else None
+        g_peak = self._zeroed_half_grad_peak(grad_out_nchw.device) if grad16 else None
         pending = {}                                       # skip source plan index -> gradient that branched off
         masked = False                                     # g already carries the ReLU gradient of layer li
 
@@ -650,7 +697,10 @@ class DreamHourglass(nn.Module):
             if kind == "pool":
                 g_amax = None
                 masked = relu_feeds(li - 1)
-                g = (ops.maxpool2_bwd_x16 if inp.dtype == torch.float16 else ops.maxpool2_bwd)(g, inp, relu=masked)
+                if li in grad16:                           # g is half, and so is the gradient it becomes: exact, no scale is read
+                    g = ops.maxpool2_bwd_x16_dy16(g, inp, relu=masked)
+                else:
+                    g = (ops.maxpool2_bwd_x16 if inp.dtype == torch.float16 else ops.maxpool2_bwd)(g, inp, relu=masked)
                 continue
             if kind == "add":
                 pending[flags] = ops.clone(g)              # later in-place ReLU masks must not touch this copy
@@ -690,6 +740,28 @@ class DreamHourglass(nn.Module):
                 if need_input_grad:
                     g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
+                continue
+            if li in saved.half_in and (li in grad16 or li - 1 in grad16):
+                # ... and the run's gradients are half (train_gradient_storage="fp16").  g in: half (times 2^e_g) unless this is the
+                # boundary conv; g out: half unless it is the gradient with respect to entry 0's output (the exit, which takes 2^-e_g)
+                p16 = self._packed.get(mod.weight, "f16", 1)
+                mask = inp if fuse else None               # (behind a pool: the pool's backward carries the ReLU gradient)
+                if li in grad16:
+                    def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=eg_amax):
+                        grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16_dy16(inp, g, ag, cout, cin)
+                    _on_side(side, leaf, inp, g, eg_amax)
+                    if li - 1 in grad16:
+                        g, g_amax = ops.conv2d_f16_g16(g, p16, p16[3], 3, relu_mask=mask, peak=g_peak), None
+                    else:
+                        assert fuse, "internal: the exit form of a half-stored data gradient carries the first conv's ReLU mask"
+                        g, g_amax = ops.conv2d_f16_g16_exit(g, p16, p16[3], 3, eg_amax, mask)
+                else:
+                    g_amax = g_amax if g_amax is not None else ops.absmax(g)
+                    def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=g_amax):
+                        grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16(inp, g, ag, cout, cin)
+                    _on_side(side, leaf, inp, g, g_amax)
+                    g, g_amax = ops.conv2d_f16_g16_entry(g, g_amax, p16, p16[3], 3, eg_amax, relu_mask=mask, peak=g_peak), None
+                masked = fuse
                 continue
             if li in saved.half_in:
                 # the forward read a half input here (train_activation_storage="fp16"): the weight gradient takes the stored half as its
@@ -794,12 +866,14 @@ class _Saved(list):
     """What DreamHourglass.run_forward hands to run_backward: the (input, output) pair of every plan entry, and ``amax``: plan index ->
     the amax scalar of the input of each entry that ran in half precision (train_precision="fp16").  The forward decides which entries
     those are; the backward runs exactly them in half precision.  ``half_in``: the plan indices of the convs that read a half input
-    (train_activation_storage="fp16"; they have no entry in ``amax``: the stored half is the operand)."""
+    (train_activation_storage="fp16"; they have no entry in ``amax``: the stored half is the operand).  ``grad16``: the plan indices the
+    gradient with respect to whose output the backward stores as half (train_gradient_storage="fp16"; empty otherwise)."""
 
     def __init__(self, *a):
         super().__init__(*a)
         self.amax = {}
         self.half_in = set()
+        self.grad16 = set()
 
 
 class _HourglassFunction(torch.autograd.Function):
@@ -1220,6 +1294,17 @@ class DreamHourglassMultiStage(nn.Module):
             raise ValueError("DreamHourglassMultiStage does not split its convs: conv_ksplit=%r is not supported" % (value,))
 
     @property
+    def train_gradient_storage(self):
+        """Always "fp32": the stages hand fp32 gradients to one another (DreamHourglass.train_gradient_storage)."""
+        return "fp32"
+
+    @train_gradient_storage.setter
+    def train_gradient_storage(self, value):
+        if value != "fp32":
+            raise ValueError("DreamHourglassMultiStage stores its gradients in fp32 only: train_gradient_storage=%r is not supported"
+                             % (value,))
+
+    @property
     def train_activation_storage(self):
         """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.train_activation_storage)."""
         return "fp32"
@@ -1434,6 +1519,16 @@ class ResnetSimple(nn.Module):
     def conv_ksplit(self, value):
         if value != "off":
             raise ValueError("ResnetSimple does not split its convs: conv_ksplit=%r is not supported" % (value,))
+
+    @property
+    def train_gradient_storage(self):
+        """Always "fp32": ResnetSimple trains in fp32 only (DreamHourglass.train_gradient_storage)."""
+        return "fp32"
+
+    @train_gradient_storage.setter
+    def train_gradient_storage(self, value):
+        if value != "fp32":
+            raise ValueError("ResnetSimple stores its gradients in fp32 only: train_gradient_storage=%r is not supported" % (value,))
 
     @property
     def train_activation_storage(self):

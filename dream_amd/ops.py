@@ -1685,6 +1685,83 @@ def widen_f16(x):
     return out
 
 
+# ---- training with the encoder's data gradients stored as IEEE half (train_gradient_storage="fp16") ------------------------------
+# A stored gradient is half(clamp(g * 2^e_g, +-65504)), e_g = 9 - exponent(*grad_amax): ONE device scalar per backward pass (absmax of
+# the loss gradient) that every launch derives the exponent from.  ``peak`` as above.
+def _g16_conv_shapes(name, x, packed16, cout, relu_mask):
+    hi, _, exp, _ = packed16
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != hi.shape[-1]:
+        raise RuntimeError("%s: input has %d channels, packed weights expect %d" % (name, cin, hi.shape[-1]))
+    mask = None if relu_mask is None else _f16(relu_mask)
+    if mask is not None and tuple(mask.shape) != (b, h, w, cout):
+        raise RuntimeError("%s: relu_mask must have the output's shape %s" % (name, (b, h, w, cout)))
+    return hi, exp, mask, b, h, w, cin
+
+
+def conv2d_f16_g16_entry(x_nhwc, amax_in, packed16, cout, ksize, grad_amax, relu_mask=None, peak=None, flags=0):
+    """The data gradient that enters the half-stored run: conv2d_f16 / conv2d_f16_mask16 on the fp32 ``x_nhwc`` (scaled by its own
+    amax), stored as torch.float16 times 2^e_g."""
+    x = _f32(x_nhwc)
+    hi, exp, mask, b, h, w, cin = _g16_conv_shapes("conv2d_f16_g16_entry", x, packed16, cout, relu_mask)
+    y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv2d_f16_g16_entry_nhwc_f16", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(mask), ptr(y), ptr(grad_amax), ptr(peak),
+         b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y
+
+
+def conv2d_f16_g16(x_nhwc, packed16, cout, ksize, relu_mask=None, peak=None, flags=0):
+    """A data gradient inside the run: torch.float16 in (the operand as it is), torch.float16 out; ``relu_mask`` a torch.float16
+    tensor or None (then the launch is conv2d_f16_act16's)."""
+    x = _f16(x_nhwc)
+    hi, exp, mask, b, h, w, cin = _g16_conv_shapes("conv2d_f16_g16", x, packed16, cout, relu_mask)
+    y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv2d_f16_g16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(mask), ptr(y), ptr(peak), b, h, w, cin, cout,
+         int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y
+
+
+def conv2d_f16_g16_exit(x_nhwc, packed16, cout, ksize, grad_amax, relu_mask, want_amax=True, flags=0):
+    """The data gradient that leaves the run: torch.float16 in, masked, times 2^-e_g -> (y fp32, amax_out after the mask)."""
+    x = _f16(x_nhwc)
+    hi, exp, mask, b, h, w, cin = _g16_conv_shapes("conv2d_f16_g16_exit", x, packed16, cout, relu_mask)
+    y = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
+    amax_out = new_amax(x.device) if want_amax else None
+    call("dream_conv2d_f16_g16_exit_nhwc_f32", ptr(x), ptr(hi), ptr(exp), ptr(mask), ptr(y), ptr(grad_amax), ptr(amax_out), b, h, w,
+         cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y, amax_out
+
+
+def conv3x3_wgrad_f16_x16_dy16(x_nhwc, dy_nhwc, grad_amax, cout, cin, flags=0):
+    """conv3x3_wgrad_f16_x16 with dy a torch.float16 tensor that holds the gradient times 2^e_g and IS the operand
+    -> (dW OIHW, dbias [cout]), both times 2^-e_g."""
+    x, dy = _f16(x_nhwc), _f16(dy_nhwc)
+    b, h, w, cdy = (int(v) for v in dy.shape)
+    if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
+    rows_pad = round_up(cdy, 64)
+    ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
+    dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
+    dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
+    call("dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32", ptr(x), ptr(dy), ptr(grad_amax), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin, cdy,
+         rows_pad, flags, stream())
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
+    return dw, dbias[:cout].contiguous()
+
+
+def maxpool2_bwd_x16_dy16(dy, x, relu=False):
+    """maxpool2_bwd with dy, the forward input x and dx all torch.float16 (exact: a copy or zero)."""
+    x, dy = _f16(x), _f16(dy)
+    b, h, w, c = (int(v) for v in x.shape)
+    if tuple(dy.shape) != (b, h // 2, w // 2, c):
+        raise RuntimeError("maxpool2_bwd_x16_dy16: dy %s does not go with x %s" % (tuple(dy.shape), tuple(x.shape)))
+    dx = torch.empty((b, h, w, c), dtype=torch.float16, device=x.device)
+    call("dream_maxpool2_relu_bwd_x16_dy16_nhwc_f16" if relu else "dream_maxpool2_bwd_x16_dy16_nhwc_f16", ptr(dy), ptr(x), ptr(dx),
+         b, h, w, c, stream())
+    return dx
+
+
 def conv2d_amax(x_nhwc, packed, cout, ksize, stride=1, scale=None, shift=None, residual=None, flags=0):
     """fp32 MFMA conv that also publishes max|y| (feeds the split-precision kernel's input scaling)."""
     x = _f32(x_nhwc)

@@ -558,6 +558,36 @@ int dream_maxpool2_relu_bwd_x16_nhwc_f32(const float *dy, const void *x, float *
 /* out[i] = float(x[i]) (exact), x half, out fp32, i < n, both 16-byte aligned: the widening pass behind the last half-storage
  * conv of a training forward (the Conv2d in front of the first nn.Upsample / ConvTranspose2d, dream/models.py:613-615,688-705) */
 int dream_widen_f16_f32(const void *x, float *out, size_t n, void *stream);
+/* ---- training with the encoder's data gradients stored as IEEE half (DreamHourglass.train_gradient_storage = "fp16") ------
+ * The data gradients that loss.backward() (dream/network.py:335) hands from layer to layer through the half run of the encoder
+ * (Conv2d / ReLU / MaxPool2d of dream/models.py:589-615) live in HBM as half(clamp(g * 2^e_g, +-65504)): ONE exponent per
+ * backward pass, e_g = 9 - exponent(amax of the loss gradient) (0 for a zero scalar, clamped to +-100), derived by every launch
+ * from `grad_amax`, a device scalar holding that amax's bit pattern.  `g16` / `dy16` in the name: the gradient operand is such a
+ * half tensor (void *, 16-byte aligned).  `peak` (optional, never zeroed here): max|v| of what a half-writing launch stores, taken
+ * before the saturation.  The convs are plain 3x3 stride-1 convs with the mode-1 packed plane (flags must be 0); mask
+ * [B,H,W,Cout] half or NULL: y = mask > 0 ? conv : 0.  Every variant of dream_conv_f16_set_variant applies.
+ * entry (the conv at the upper end of the run): x fp32 with its amax_in, as dream_conv2d_f16_nhwc_f32 -> y = half(conv * 2^e_g). */
+int dream_conv2d_f16_g16_entry_nhwc_f16(const float *x, const unsigned *amax_in, const void *w, const int *w_exp, const void *mask,
+                                        void *y, const unsigned *grad_amax, unsigned *peak, int B, int H, int W, int Cin,
+                                        int Cout, int CoutPad, int ksize, int stride, int flags, void *stream);
+/* interior: x half (it carries 2^e_g) -> y half: the stored half is the operand, no scalar is read.  mask NULL: this is
+ * dream_conv2d_f16_nhwc_f16. */
+int dream_conv2d_f16_g16_nhwc_f16(const void *x, const void *w, const int *w_exp, const void *mask, void *y, unsigned *peak, int B,
+                                  int H, int W, int Cin, int Cout, int CoutPad, int ksize, int stride, int flags, void *stream);
+/* exit (the lower end): x half, mask required -> y = (mask > 0 ? conv : 0) * 2^-e_g, fp32; amax_out = max|y| after the mask. */
+int dream_conv2d_f16_g16_exit_nhwc_f32(const void *x, const void *w, const int *w_exp, const void *mask, float *y,
+                                       const unsigned *grad_amax, unsigned *amax_out, int B, int H, int W, int Cin, int Cout,
+                                       int CoutPad, int ksize, int stride, int flags, void *stream);
+/* dream_conv3x3_wgrad_f16_x16_nhwc_f32 with dy such a half tensor too: copied into LDS (no convert, no multiply, no amax of dy);
+ * dw_packed and dbias -- the fp32 channel sum of the stored halfs -- are multiplied by 2^-e_g once, in the reduce kernel.
+ * Workspace, split and summation order as there. */
+int dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32(const void *x, const void *dy, const unsigned *grad_amax, float *dw_packed,
+                                              float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad,
+                                              int flags, void *stream);
+/* dream_maxpool2_bwd_x16_nhwc_f32 / dream_maxpool2_relu_bwd_x16_nhwc_f32 with dy and dx half as well: exact (a copy or zero), so it
+ * reads no scalar.  C % 8 == 0; dy, x, dx 16-byte aligned. */
+int dream_maxpool2_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream);
+int dream_maxpool2_relu_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream);
 /* The same weight gradient in the Winograd F(2x2,3x3) domain (16 instead of 36 multiplications per 2x2 outputs, fp32
  * throughout): dU_p = sum_tiles (A dY A^T)_p x (B^T d B)_p on the fp32 matrix cores, dW = G^T dU G, deterministic split-K.
  * x [B,H,W,Cin], dy [B,H,W,Cdy] (Cdy >= Cout, both multiples of 16), Cin % 64 == 0 -> dw_oihw [Cout,Cin,3,3] (OIHW,
