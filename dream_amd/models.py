@@ -20,6 +20,7 @@ resolves the group of entries that run as one (``_group``), the kernel of every 
 place (``_conv3x3_choice`` / ``_conv3x3``, ``_ups_tile`` / ``_ups_conv``), and the split-precision inference path is the same walk
 on other launches.  If the HIP library or a GPU is missing the call raises -- there is no CPU path in this package.
 """
+import collections
 import os
 import threading
 
@@ -93,6 +94,71 @@ class _PackedCache:
 # ops.conv_transpose3x3s2_<suffix>, ops.pack_conv_weight_<suffix>, ops.pack_convT4x4_weight_<suffix>) and of their packed forms.  Both
 # take the same arguments and thread the same amax side channel; what differs is the arithmetic (csrc/conv_f16x3.hip, csrc/conv_f16.hip).
 _HALF_OPS = {"fp16x3": "f16x3", "fp16": "f16"}
+
+# The precision switches of DreamHourglass, as data: (attribute, allowed values -- the first is the default --, what any other value
+# needs: (attribute, value) pairs, the pass that reads it, is an unknown value refused in the other pass as well?).  An unmet need is
+# refused in the pass that reads the switch only.  DreamHourglass._resolve_switches is the one reader: a new mode is a row here, a field
+# of _Walk and, per conv entry, a form (run_forward; _Saved.half for the backward).
+_SWITCHES = (
+    ("precision", ("fp32", "fp16x3", "fp16"), (), "inference", True),
+    ("activation_storage", ("fp32", "fp16"), (("precision", "fp16"),), "inference", True),
+    ("conv_ksplit", ("off", "auto"), (("precision", "fp16"), ("activation_storage", "fp16")), "inference", True),
+    ("train_precision", ("fp32", "fp16"), (), "training", True),
+    ("train_activation_storage", ("fp32", "fp16"), (("train_precision", "fp16"),), "training", False),
+    ("train_gradient_storage", ("fp32", "fp16"), (("train_precision", "fp16"), ("train_activation_storage", "fp16")), "training", False),
+)
+
+# What one walk of the plan does, resolved once from the switches (DreamHourglass._resolve_switches).  ``family``: the kernels of an
+# inference conv, "fp32" | "f16x3" | "f16"; ``act16`` / ``ksplit``: inference stores its activations as half / may split a small launch;
+# ``half_train``: the plain convs of a training pass run on the fp16 matrix cores; ``store16`` / ``grad16``: the plan indices whose
+# output / the gradient with respect to whose output a training pass stores as half; ``half_storage``: the walk writes the
+# half-storage peak scalar (half_storage_peak()).
+_Walk = collections.namedtuple("_Walk", "family act16 ksplit half_train store16 grad16 half_storage")
+
+
+class _PeakScalar:
+    """A peak scalar that the half-storage launches of one pass atomicMax into: ONE persistent tensor per device, zeroed in place by
+    every such pass (so every captured hipGraph of the module writes the scalar that is read), and the last one used."""
+
+    def __init__(self, never):
+        self._never, self._by_device, self._last = never, {}, None
+
+    def zeroed(self, device):
+        """The scalar on ``device``, zeroed in place (created on first use)."""
+        self._last = self._by_device.get(device)
+        if self._last is None:
+            self._last = self._by_device[device] = ops.new_amax(device)
+        else:
+            self._last.zero_()
+        return self._last
+
+    def read(self):
+        if self._last is None:
+            raise RuntimeError(self._never)
+        return float(self._last.cpu().view(torch.float32)[0])
+
+
+def _half_wgrad(x, x_amax, dy, dy_amax, dy16, cout, cin):
+    """The weight gradient of a conv entry that ran on the fp16 matrix cores, by which of its operands are stored as half (x: where the
+    forward left no amax of it; dy: ``dy16``, and then ``dy_amax`` is the amax of the loss gradient) -> (dW, dbias)."""
+    if x_amax is not None:
+        return ops.conv3x3_wgrad_f16(x, x_amax, dy, dy_amax, cout, cin)
+    return (ops.conv3x3_wgrad_f16_x16_dy16 if dy16 else ops.conv3x3_wgrad_f16_x16)(x, dy, dy_amax, cout, cin)
+
+
+def _half_dgrad(dy, dy_amax, p16, mask, x16, dy16, dx16, grad_amax, peak):
+    """... and its data gradient, by which of x (the ReLU mask), dy and dx are stored as half -> (dx, its amax or None).  ``mask``: the
+    input of the entry where dx carries the ReLU gradient of the entry in front, else None."""
+    if dy16 and dx16:                                  # inside the half-stored run
+        return ops.conv2d_f16_g16(dy, p16, p16[3], 3, relu_mask=mask, peak=peak), None
+    if dx16:                                           # the boundary conv: fp32 in (scaled by its own amax), half out
+        return ops.conv2d_f16_g16_entry(dy, dy_amax, p16, p16[3], 3, grad_amax, relu_mask=mask, peak=peak), None
+    if dy16:                                           # the gradient with respect to entry 0's output: takes 2^-e_g
+        assert mask is not None, "internal: the exit form of a half-stored data gradient carries the first conv's ReLU mask"
+        return ops.conv2d_f16_g16_exit(dy, p16, p16[3], 3, grad_amax, mask)
+    if x16 and mask is not None:                       # the mask is the half output of the conv in front
+        return ops.conv2d_f16_mask16(dy, dy_amax, p16, p16[3], 3, mask)
+    return ops.conv2d_f16(dy, dy_amax, p16, p16[3], 3, relu_mask=mask)       # (behind a pool: the pool's backward carries the ReLU gradient)
 
 
 class DreamHourglass(nn.Module):
@@ -201,9 +267,7 @@ class DreamHourglass(nn.Module):
         # KSPLIT); launches with a fused pool / upsample, the transposed convs, the first conv and the belief-map conv are
         # never split.  "off" (default): every launch list is what it was.  Read once per forward; training ignores it.
         self.conv_ksplit = "off"
-        self._ksplit = False                 # the switch as the running forward read it
-        self._half_peaks = {}                # device -> the walk's peak scalar: ONE persistent tensor, zeroed in place by every half-storage
-        self._half_peak = None               # forward (so every captured hipGraph of this module writes the scalar that is read); the last one used
+        self._storage_peak = _PeakScalar("half_storage_peak(): no forward with activation_storage=\"fp16\" has run")
         # Training: "fp32", or "fp16" = the plain convs (_half_train_entry) run their forward, data-gradient and weight-gradient products
         # on the fp16 matrix cores (conv_f16.hip, wgrad_f16.hip: fp32 tensors in HBM, operands rounded once while staged, per-tensor
         # power-of-two scales from the amax side channel); every other plan entry keeps its fp32 launches.  Does not affect inference.
@@ -220,8 +284,7 @@ class DreamHourglass(nn.Module):
         # GRAD16, wgrad_f16.hip DY16, elementwise.hip): no absmax pass runs inside the run.  "fp32" (default): every
         # gradient is fp32.  Read once per training forward; inference ignores it.  See half_gradient_peak().
         self.train_gradient_storage = "fp32"
-        self._half_grad_peaks = {}           # device -> the backward's peak scalar (as _half_peaks: persistent, zeroed in place by every such
-        self._half_grad_peak = None          # backward); the last one used
+        self._gradient_peak = _PeakScalar("half_gradient_peak(): no backward with train_gradient_storage=\"fp16\" has run")
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
         # implicit-GEMM kernel everywhere (csrc/conv_mfma.hip, the reference form)
@@ -342,10 +405,32 @@ class DreamHourglass(nn.Module):
             return ops.conv_transpose4x4s2(x, pk4, rows, None, bias, flags & CONV_RELU, direct_taps=36)
         return ops.upsample2_bwd(self._conv3x3(mod, 1, x))
 
-    def _check_train_precision(self):
-        if self.train_precision not in ("fp32", "fp16"):
-            raise ValueError("unknown train_precision %r (\"fp32\" or \"fp16\")" % (self.train_precision,))
-        return self.train_precision == "fp16"
+    def _resolve_switches(self, save, x_is_nhwc=False):
+        """Reads the precision switches (_SWITCHES), once per forward -> the _Walk of this pass; raises ValueError for an unknown value
+        and for a value whose needs are not met."""
+        this_pass, read = "training" if save else "inference", {}
+        for name, allowed, needs, reader, always in _SWITCHES:
+            value = getattr(self, name)
+            if (always or reader == this_pass) and value not in allowed:
+                raise ValueError("unknown %s %r" % (name, value)           # (a switch of two values names them)
+                                 + (" (\"%s\" or \"%s\")" % allowed if len(allowed) == 2 else ""))
+            if reader != this_pass:                    # the other pass ignores it
+                value = allowed[0]
+            elif value != allowed[0] and any(getattr(self, n) != v for n, v in needs):
+                are = tuple(getattr(self, n) for n, _ in needs)
+                raise ValueError("%s=\"%s\" needs %s (%s)" % (name, value, " and ".join("%s=\"%s\"" % need for need in needs),
+                                                            "%s is %r" % (needs[0][0], are[0]) if len(are) == 1 else "they are %r and %r" % are))
+            read[name] = value
+        act16 = read["activation_storage"] == "fp16"
+        if act16 and x_is_nhwc:
+            raise ValueError("activation_storage=\"fp16\" takes the NCHW image (precision=\"fp16\"), not a staged NHWC input")
+        half_storage = read["train_activation_storage"] == "fp16"
+        store16 = frozenset(self._half_storage_plan()) if half_storage else frozenset()
+        grad16 = frozenset(self._half_gradient_plan(store16)) if read["train_gradient_storage"] == "fp16" else frozenset()
+        if any(self._plan[li][0] == "pool" and li - 1 not in grad16 for li in grad16):
+            raise ValueError("train_gradient_storage=\"fp16\": a max-pool directly behind the first conv is not built")
+        return _Walk(_HALF_OPS.get(read["precision"], "fp32"), act16, read["conv_ksplit"] == "auto", read["train_precision"] == "fp16",
+                     store16, grad16, act16 or half_storage)
 
     @staticmethod
     def _half_train_entry(kind, mod, flags, in_channels):
@@ -380,38 +465,18 @@ class DreamHourglass(nn.Module):
                 return half
             half = keep
 
-    def _zeroed_half_peak(self, device):
-        """The walk's one peak scalar on ``device``, zeroed in place (created on first use)."""
-        self._half_peak = self._half_peaks.get(device)
-        if self._half_peak is None:
-            self._half_peak = self._half_peaks[device] = ops.new_amax(device)
-        else:
-            self._half_peak.zero_()
-        return self._half_peak
-
     def _half_gradient_plan(self, store16=None):
         """The rule of train_gradient_storage="fp16" -> the set of plan indices the gradient with respect to whose OUTPUT is stored as
         IEEE half: the activation itself is half-stored (_half_storage_plan) and it is not the output of plan entry 0 (the first
         conv's weight gradient reads an fp32 dy)."""
         return {li for li in (self._half_storage_plan() if store16 is None else store16) if li != 0}
 
-    def _zeroed_half_grad_peak(self, device):
-        """The backward's one peak scalar on ``device``, zeroed in place (created on first use)."""
-        self._half_grad_peak = self._half_grad_peaks.get(device)
-        if self._half_grad_peak is None:
-            self._half_grad_peak = self._half_grad_peaks[device] = ops.new_amax(device)
-        else:
-            self._half_grad_peak.zero_()
-        return self._half_grad_peak
-
     def half_gradient_peak(self):
         """The largest |g * 2^e_g|, before saturation, that any launch of the last backward with train_gradient_storage="fp16" wanted to
         store as a half (this module's own backward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_gradient_peak()).
         >= 65504: a gradient of that step saturated -- go back to train_gradient_storage="fp32".  Reading it is the mode's only host
         synchronisation, and happens only here."""
-        if self._half_grad_peak is None:
-            raise RuntimeError("half_gradient_peak(): no backward with train_gradient_storage=\"fp16\" has run")
-        return float(self._half_grad_peak.cpu().view(torch.float32)[0])
+        return self._gradient_peak.read()
 
     # ---- which plan entries run as one -----------------------------------------------------------------------------------
     def _fuse_pool(self, layers, li, x_nhwc, split):
@@ -425,11 +490,11 @@ class DreamHourglass(nn.Module):
             return True         # F(4x4,3x3) works on whole 4x4 tiles anyway: the pooled store is free at every map size (saves the 100^2 / 50^2 passes)
         return min(int(x_nhwc.shape[1]), int(x_nhwc.shape[2])) >= 160
 
-    def _first_pair_subbatch(self, layers, li, x_nchw, save):
+    def _first_pair_subbatch(self, layers, li, x_nchw, save, split):
         """Frames per sub-batch for the first conv pair of an inference pass (0: run the layers whole).  DREAM_FIRST_SUBBATCH=n; only
         where the second conv runs on the F(4x4,3x3) kernel with the pool fused, is no skip source, and the batch has several sub-batches."""
         n = int(os.environ.get("DREAM_FIRST_SUBBATCH", "0"))
-        if n <= 0 or save or self.precision != "fp32" or li + 2 >= len(layers):
+        if n <= 0 or save or split or li + 2 >= len(layers):
             return 0
         (k1, m1, f1), (k2, _, _) = layers[li + 1], layers[li + 2]
         b, _, h, w = (int(v) for v in x_nchw.shape)
@@ -450,7 +515,7 @@ class DreamHourglass(nn.Module):
         kind, mod, flags = layers[li]
         follower = layers[li + 1][0] if li + 1 < len(layers) else None
         if kind == "first":
-            sub = self._first_pair_subbatch(layers, li, x, save)
+            sub = self._first_pair_subbatch(layers, li, x, save, split)
             return ("pair+pool", sub) if sub else ("conv", 0)
         if kind == "conv" and follower == "pool":
             if not save:
@@ -484,40 +549,36 @@ class DreamHourglass(nn.Module):
             return ops.conv_transpose3x3s2(x, packed, bias, rows, relu=bool(flags & CONV_RELU), skip=skip), None
         return self._conv3x3(mod, 0, x, bias, skip=skip, flags=flags), None
 
-    def _conv_half(self, sfx, kind, mod, x, amax, w, bias, flags):
-        """One conv entry of the plan on the kernels of _HALF_OPS suffix ``sfx`` -> (y, amax of y).  Each kernel publishes max|y| of its
-        output (amax side channel) so the next conv can scale its input into fp16 range; skip connections are not folded here.  The
-        3-channel first conv stays on its fp32 VALU kernel."""
+    def _conv_half(self, sfx, kind, mod, x, amax, w, bias, flags, peak=None, ksplit=False):
+        """One conv entry of the plan on the kernels of _HALF_OPS suffix ``sfx`` ("f16x3": three MFMAs per product, fp32-class error;
+        "f16": operands rounded to fp16, one MFMA per product).  Skip connections are not folded here; the 3-channel first conv keeps
+        its fp32 VALU arithmetic.  Two forms:
+          ``peak`` None   fp32 tensors in HBM -> (y, amax of y): each kernel publishes max|y| of its output (amax side channel) so the
+                          next conv can scale its input into fp16 range;
+          ``peak``        ("f16" only) half tensors in HBM, the stored half is the operand -> (y, None): no amax travels, every launch
+                          atomicMaxes what it wanted to store into that peak scalar instead; ``ksplit``: a plain conv whose grid cannot
+                          fill the chip divides its contraction (conv_ksplit="auto")."""
+        stored, relu = peak is not None, bool(flags & CONV_RELU)
         if kind == "first":
-            return ops.conv3x3_first_amax(x, w, bias, relu=bool(flags & CONV_RELU))
-        if flags & CONV_UPSAMPLE2X:
-            pk4 = self._packed.get(mod.weight, "ups_" + sfx)
-            return getattr(ops, "conv_transpose4x4s2_" + sfx)(x, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
-        if kind == "deconv":
-            p16 = self._packed.get(mod.weight, sfx, 1)
-            return getattr(ops, "conv_transpose3x3s2_" + sfx)(x, amax, p16, p16[3], bias, relu=bool(flags & CONV_RELU))
-        p16 = self._packed.get(mod.weight, sfx, 0)
-        return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
-
-    def _conv_act16(self, kind, mod, x, amax, w, bias, flags, skip=None):
-        """One conv entry of the plan with activation_storage="fp16" -> (y, None): the launches of _conv_half("f16", ...) on half
-        tensors.  Same packed forms ("f16", "ups_f16"); no amax travels (the stored half is the operand), every launch atomicMaxes
-        what it wanted to store into the walk's one peak scalar instead.  The 3-channel first conv keeps its fp32 VALU arithmetic."""
-        peak = self._half_peak
-        if kind == "first":
-            return ops.conv3x3_first_f16(x, w, bias, relu=bool(flags & CONV_RELU), peak=peak), None
-        if kind == "wide":
+            return (ops.conv3x3_first_f16(x, w, bias, relu=relu, peak=peak), None) if stored else ops.conv3x3_first_amax(x, w, bias, relu=relu)
+        if kind == "wide" and stored:
             raise ValueError("activation_storage=\"fp16\" is built for the 3-channel first conv only (a multi-stage hourglass stages "
                              "its later inputs in fp32)")
         if flags & CONV_UPSAMPLE2X:
-            pk4 = self._packed.get(mod.weight, "ups_f16")
-            return ops.conv_transpose4x4s2_f16_act16(x, pk4, pk4[3], None, bias, flags & CONV_RELU, peak=peak), None
+            pk4 = self._packed.get(mod.weight, "ups_" + sfx)
+            if stored:
+                return ops.conv_transpose4x4s2_f16_act16(x, pk4, pk4[3], None, bias, flags & CONV_RELU, peak=peak), None
+            return getattr(ops, "conv_transpose4x4s2_" + sfx)(x, amax, pk4, pk4[3], None, bias, flags & CONV_RELU, direct_taps=36)
         if kind == "deconv":
-            p16 = self._packed.get(mod.weight, "f16", 1)
-            return ops.conv_transpose3x3s2_f16_act16(x, p16, p16[3], bias, relu=bool(flags & CONV_RELU), peak=peak), None
-        p16 = self._packed.get(mod.weight, "f16", 0)
-        launch = ops.conv2d_f16_act16_ksplit if self._ksplit else ops.conv2d_f16_act16
-        return launch(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
+            p16 = self._packed.get(mod.weight, sfx, 1)
+            if stored:
+                return ops.conv_transpose3x3s2_f16_act16(x, p16, p16[3], bias, relu=relu, peak=peak), None
+            return getattr(ops, "conv_transpose3x3s2_" + sfx)(x, amax, p16, p16[3], bias, relu=relu)
+        p16 = self._packed.get(mod.weight, sfx, 0)
+        if stored:
+            launch = ops.conv2d_f16_act16_ksplit if ksplit else ops.conv2d_f16_act16
+            return launch(x, p16, p16[3], 3, None, bias, flags, peak=None if flags & CONV_OUT_NCHW else peak), None
+        return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], 3, None, bias, None, flags, want_amax=not (flags & CONV_OUT_NCHW))
 
     def half_storage_peak(self):
         """The largest |value|, before saturation, that any launch of the last forward with activation_storage="fp16" -- or the last
@@ -525,17 +586,7 @@ class DreamHourglass(nn.Module):
         as a half (this module's own forward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_storage_peak(), which takes the
         maximum over the replicas).  >= 65504: that forward saturated -- go back
         to activation_storage="fp32".  Reading it is the mode's only host synchronisation, and happens only here."""
-        if self._half_peak is None:
-            raise RuntimeError("half_storage_peak(): no forward with activation_storage=\"fp16\" has run")
-        return float(self._half_peak.cpu().view(torch.float32)[0])
-
-    def _conv_f16x3(self, kind, mod, x, amax, w, bias, flags, skip=None):
-        """... on the split-precision kernels (three MFMAs per product, fp32-class error)."""
-        return self._conv_half("f16x3", kind, mod, x, amax, w, bias, flags)
-
-    def _conv_f16(self, kind, mod, x, amax, w, bias, flags, skip=None):
-        """... on the half-precision kernel (operands rounded to fp16, one MFMA per product)."""
-        return self._conv_half("f16", kind, mod, x, amax, w, bias, flags)
+        return self._storage_peak.read()
 
     def _first_pair_in_subbatches(self, layers, li, x, params, sub):
         """conv1_1 -> conv1_2 (+ pool) over sub-batches of ``sub`` frames, so that the 64-channel full-resolution tensor between them
@@ -557,52 +608,18 @@ class DreamHourglass(nn.Module):
         every plan entry, which run_backward needs, is returned as well.  ``x_is_nhwc``: the caller (multi-stage) already built the
         zero-padded NHWC input of a "wide" first conv (``x_amax``: its max|x|, for the split-precision kernels).
 
-        One walk: at each conv the group of entries it heads is resolved (_group) and run, then the walk moves past them.  Inference
-        with precision "fp16x3" / "fp16" is the same walk on the split- / half-precision launches (_conv_f16x3 / _conv_f16), with the amax
-        side channel threaded through; it folds no skip-adds and runs no sub-batches."""
+        One walk: the switches are read once (_resolve_switches -> what this pass does), then at each conv the group of entries it
+        heads is resolved (_group), the form it runs in is decided -- the fp32 kernels (_conv_fp32), or the fp16 matrix cores on fp32
+        tensors with the amax side channel threaded through, or on a stored half operand (_conv_half) -- and it is run; then the walk
+        moves past the group.  An inference pass runs every conv in the one form its switches name (other than fp32 it folds no
+        skip-adds and runs no sub-batches), a training pass the plain convs in half precision where train_precision says so, on
+        whatever its input is stored as; what it chose per entry travels to run_backward in ``saved.half``."""
         self._check_input(x, x_is_nhwc)
-        if self.precision != "fp32" and self.precision not in _HALF_OPS:
-            raise ValueError("unknown precision %r" % (self.precision,))
-        if self.activation_storage not in ("fp32", "fp16"):
-            raise ValueError("unknown activation_storage %r (\"fp32\" or \"fp16\")" % (self.activation_storage,))
-        if self.conv_ksplit not in ("off", "auto"):
-            raise ValueError("unknown conv_ksplit %r (\"off\" or \"auto\")" % (self.conv_ksplit,))
-        split = self.precision in _HALF_OPS and not save
-        act16 = self.activation_storage == "fp16" and not save           # (read once per forward, as ``precision``)
-        if act16 and self.precision != "fp16":
-            raise ValueError("activation_storage=\"fp16\" needs precision=\"fp16\" (precision is %r)" % (self.precision,))
-        conv = {"fp16x3": self._conv_f16x3, "fp16": self._conv_f16}[self.precision] if split else self._conv_fp32
-        if act16:
-            if x_is_nhwc:
-                raise ValueError("activation_storage=\"fp16\" takes the NCHW image (precision=\"fp16\"), not a staged NHWC input")
-            conv = self._conv_act16
-            self._zeroed_half_peak(x.device)
-        self._ksplit = self.conv_ksplit == "auto" and not save           # (read once per forward)
-        if self._ksplit and not act16:
-            raise ValueError("conv_ksplit=\"auto\" needs precision=\"fp16\" and activation_storage=\"fp16\" (they are %r and %r)"
-                             % (self.precision, self.activation_storage))
-        half = self._check_train_precision() and bool(save)
+        walk = self._resolve_switches(bool(save), x_is_nhwc)
+        split, act16, store16 = walk.family != "fp32", walk.act16, walk.store16
+        peak = self._storage_peak.zeroed(x.device) if walk.half_storage else None
         layers = self.plan_layers()
-        saved, keep = _Saved(), {}
-        store16 = set()                                # plan entries whose output this (training) forward stores as half
-        if save:                                       # (read once per training forward, as ``train_precision``)
-            if self.train_activation_storage not in ("fp32", "fp16"):
-                raise ValueError("unknown train_activation_storage %r (\"fp32\" or \"fp16\")" % (self.train_activation_storage,))
-            if self.train_activation_storage == "fp16":
-                if not half:
-                    raise ValueError("train_activation_storage=\"fp16\" needs train_precision=\"fp16\" (train_precision is %r)"
-                                     % (self.train_precision,))
-                store16 = self._half_storage_plan()
-                self._zeroed_half_peak(x.device)
-            if self.train_gradient_storage not in ("fp32", "fp16"):
-                raise ValueError("unknown train_gradient_storage %r (\"fp32\" or \"fp16\")" % (self.train_gradient_storage,))
-            if self.train_gradient_storage == "fp16":
-                if not half or self.train_activation_storage != "fp16":
-                    raise ValueError("train_gradient_storage=\"fp16\" needs train_precision=\"fp16\" and train_activation_storage=\"fp16\" "
-                                     "(they are %r and %r)" % (self.train_precision, self.train_activation_storage))
-                saved.grad16 = self._half_gradient_plan(store16)
-                if any(layers[li][0] == "pool" and li - 1 not in saved.grad16 for li in saved.grad16):
-                    raise ValueError("train_gradient_storage=\"fp16\": a max-pool directly behind the first conv is not built")
+        saved, keep = _Saved(grad16=walk.grad16), {}
         act, amax, li = x, x_amax, 0
         while li < len(layers):
             kind, mod, flags = layers[li]
@@ -612,9 +629,9 @@ class DreamHourglass(nn.Module):
             elif kind == "add":
                 self._join(act, keep[flags])
                 if act16:
-                    out = ops.add_f16(act, keep[flags], peak=self._half_peak)
+                    out = ops.add_f16(act, keep[flags], peak=peak)
                 else:
-                    out, amax = ops.add(act, keep[flags], want_amax=split or half)
+                    out, amax = ops.add(act, keep[flags], want_amax=split or walk.half_train)
                 outs = [out]
             else:
                 if kind == "wide" and not x_is_nhwc and not act16:
@@ -622,31 +639,34 @@ class DreamHourglass(nn.Module):
                         amax = ops.absmax(act)
                     act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
                 w, bias = params[self._param_slot[li]], params[self._param_slot[li] + 1]
-                half_entry = half and self._half_train_entry(kind, mod, flags, act.shape[3])
+                half_entry = walk.half_train and self._half_train_entry(kind, mod, flags, act.shape[3])
                 group, sub = self._group(layers, li, act, save, split, half_entry)
-                if kind == "first" and li in store16:
-                    outs, amax = [ops.conv3x3_first_f16(act, w, bias, relu=bool(flags & CONV_RELU), peak=self._half_peak)], None
-                elif half_entry and act.dtype == torch.float16:
-                    # train_activation_storage="fp16": the stored half is the operand (no amax travels), the half-storage inference
-                    # launch; the conv that ends the run stores half as well and a widening pass (exact) follows: its saved output is fp32
-                    saved.half_in.add(li)
-                    p16 = self._packed.get(mod.weight, "f16", 0)
-                    out = ops.conv2d_f16_act16(act, p16, p16[3], 3, None, bias, flags, peak=self._half_peak)
-                    outs, amax = [out if li in store16 else ops.widen_f16(out)], None
-                elif half_entry:
-                    # the amax of the launch that produced ``act`` where it is still that tensor's, one absmax pass otherwise; it travels
-                    # with ``saved`` to the weight gradient
-                    saved.amax[li] = amax = amax if amax is not None else ops.absmax(act)
-                    outs = list(self._conv_f16(kind, mod, act, amax, w, bias, flags))
-                    amax = outs.pop()
-                elif group == "pair+pool":
+                # the form of this entry: its kernels, and whether they work on a stored half (then no amax travels)
+                if save:
+                    stored = (kind == "first" and li in store16) or (half_entry and act.dtype == torch.float16)
+                    family = "f16" if half_entry or stored else "fp32"
+                else:
+                    family, stored = walk.family, act16
+                if group == "pair+pool":
                     outs = [None, None, self._first_pair_in_subbatches(layers, li, act, params, sub)]
                 elif group == "conv+pool_both":
                     outs = list(self._conv3x3(mod, 0, act, bias, flags=flags, pool_both=True))
                     amax = None
                 else:
                     skip = keep[layers[li + 1][2]] if group == "conv+add" else None
-                    out, amax = conv(kind, mod, act, amax, w, bias, flags | (CONV_POOL2 if group == "conv+pool" else 0), skip)
+                    group_flags = flags | (CONV_POOL2 if group == "conv+pool" else 0)
+                    if family == "fp32":
+                        out, amax = self._conv_fp32(kind, mod, act, amax, w, bias, group_flags, skip)
+                    else:
+                        if half_entry:
+                            # what the backward needs: the amax of the fp32 input -- that of the launch that produced ``act`` where it is
+                            # still that tensor's, one absmax pass otherwise -- or None: the stored half is the operand
+                            if not stored and amax is None:
+                                amax = ops.absmax(act)
+                            saved.half[li] = None if stored else amax
+                        out, amax = self._conv_half(family, kind, mod, act, amax, w, bias, group_flags, peak if stored else None, walk.ksplit)
+                        if save and stored and li not in store16:
+                            out = ops.widen_f16(out)       # the conv that ends the half run stores half as well; its saved output is fp32 (exact)
                     outs = [out] if group == "conv" else [None, out]
             # one output per plan entry the group covered (None: folded away, never stored -- and then neither saved nor a skip source)
             for out in outs:
@@ -662,7 +682,6 @@ class DreamHourglass(nn.Module):
         multi-stage hourglass, dL/d(NHWC input of the "wide" first conv)).  ``reducer``: overlapped data-parallel
         all-reduce that is fed every gradient as soon as it exists."""
         layers = self.plan_layers()
-        self._check_train_precision()
         g_amax = None                                      # amax scalar of g while g is still the tensor an fp16 launch wrote
         grads = _GradList(2 * len(self._param_slot), reducer)
         # weight gradients are leaves of the data-gradient chain: second stream when the batch is small (see _SideStream)
@@ -674,7 +693,7 @@ class DreamHourglass(nn.Module):
         # derives the exponent e_g its half gradients are stored with; no host synchronisation, no state from step to step
         grad16 = saved.grad16
         eg_amax = ops.absmax(grad_out_nchw) if grad16 else None
-        g_peak = self._zeroed_half_grad_peak(grad_out_nchw.device) if grad16 else None
+        g_peak = self._gradient_peak.zeroed(grad_out_nchw.device) if grad16 else None
         pending = {}                                       # skip source plan index -> gradient that branched off
         masked = False                                     # g already carries the ReLU gradient of layer li
 
@@ -741,52 +760,20 @@ class DreamHourglass(nn.Module):
                     g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
                 continue
-            if li in saved.half_in and (li in grad16 or li - 1 in grad16):
-                # ... and the run's gradients are half (train_gradient_storage="fp16").  g in: half (times 2^e_g) unless this is the
-                # boundary conv; g out: half unless it is the gradient with respect to entry 0's output (the exit, which takes 2^-e_g)
-                p16 = self._packed.get(mod.weight, "f16", 1)
-                mask = inp if fuse else None               # (behind a pool: the pool's backward carries the ReLU gradient)
-                if li in grad16:
-                    def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=eg_amax):
-                        grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16_dy16(inp, g, ag, cout, cin)
-                    _on_side(side, leaf, inp, g, eg_amax)
-                    if li - 1 in grad16:
-                        g, g_amax = ops.conv2d_f16_g16(g, p16, p16[3], 3, relu_mask=mask, peak=g_peak), None
-                    else:
-                        assert fuse, "internal: the exit form of a half-stored data gradient carries the first conv's ReLU mask"
-                        g, g_amax = ops.conv2d_f16_g16_exit(g, p16, p16[3], 3, eg_amax, mask)
-                else:
+            if li in saved.half:
+                # the forward ran this entry on the fp16 matrix cores: both products of its backward run there too.  What varies is which
+                # of x (train_activation_storage: the forward left no amax), dy and dx (train_gradient_storage: half, times 2^e_g) are
+                # stored as half.  An fp32 dy is scaled by its amax: that of the launch that wrote it, or one pass that serves both products
+                x_amax = saved.half[li]
+                x16, dy16, dx16 = x_amax is None, li in grad16, li - 1 in grad16
+                if not dy16:
                     g_amax = g_amax if g_amax is not None else ops.absmax(g)
-                    def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=g_amax):
-                        grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16(inp, g, ag, cout, cin)
-                    _on_side(side, leaf, inp, g, g_amax)
-                    g, g_amax = ops.conv2d_f16_g16_entry(g, g_amax, p16, p16[3], 3, eg_amax, relu_mask=mask, peak=g_peak), None
-                masked = fuse
-                continue
-            if li in saved.half_in:
-                # the forward read a half input here (train_activation_storage="fp16"): the weight gradient takes the stored half as its
-                # operand, the data gradient masks with the half output of the conv in front
-                g_amax = g_amax if g_amax is not None else ops.absmax(g)
-                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ag=g_amax):
-                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16_x16(inp, g, ag, cout, cin)
-                _on_side(side, leaf, inp, g, g_amax)
-                p16 = self._packed.get(mod.weight, "f16", 1)
-                if fuse:
-                    g, g_amax = ops.conv2d_f16_mask16(g, g_amax, p16, p16[3], 3, inp)
-                else:                                      # (behind a pool: the pool's backward carries the ReLU gradient)
-                    g, g_amax = ops.conv2d_f16(g, g_amax, p16, p16[3], 3)
-                masked = fuse
-                continue
-            if li in saved.amax:
-                # the forward ran this entry in half precision (it left the input's amax): both products of its backward on the fp16
-                # matrix cores too; one pass over g (or the amax of the launch that wrote it) serves both
-                g_amax = g_amax if g_amax is not None else ops.absmax(g)
-                x_amax = saved.amax[li]
-                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ax=x_amax, ag=g_amax):
-                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_f16(inp, ax, g, ag, cout, cin)
-                _on_side(side, leaf, inp, g, x_amax, g_amax)
+                dy_amax = eg_amax if dy16 else g_amax
+                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ax=x_amax, ag=dy_amax, dy16=dy16):
+                    grads[pi], grads[pi + 1] = _half_wgrad(inp, ax, g, ag, dy16, cout, cin)
+                _on_side(side, leaf, *(t for t in (inp, g, x_amax, dy_amax) if t is not None))
                 p16 = self._packed.get(mod.weight, "f16", 1)       # transposed, flipped taps: the data-gradient operator
-                g, g_amax = ops.conv2d_f16(g, g_amax, p16, p16[3], 3, relu_mask=inp if fuse else None)
+                g, g_amax = _half_dgrad(g, g_amax, p16, inp if fuse else None, x16, dy16, dx16, eg_amax, g_peak)
                 masked = fuse
                 continue
             g_amax = None
@@ -863,17 +850,21 @@ class DreamHourglass(nn.Module):
 
 
 class _Saved(list):
-    """What DreamHourglass.run_forward hands to run_backward: the (input, output) pair of every plan entry, and ``amax``: plan index ->
-    the amax scalar of the input of each entry that ran in half precision (train_precision="fp16").  The forward decides which entries
-    those are; the backward runs exactly them in half precision.  ``half_in``: the plan indices of the convs that read a half input
-    (train_activation_storage="fp16"; they have no entry in ``amax``: the stored half is the operand).  ``grad16``: the plan indices the
-    gradient with respect to whose output the backward stores as half (train_gradient_storage="fp16"; empty otherwise)."""
+    """What DreamHourglass.run_forward hands to run_backward: the (input, output) pair of every plan entry, and the form of every conv
+    entry it ran on the fp16 matrix cores (train_precision="fp16") -- the backward runs exactly those in half precision.  ``half``:
+    plan index -> the amax scalar of that entry's fp32 input, or None where the input is stored as half and is the operand as it is
+    (train_activation_storage="fp16").  ``grad16``: the plan indices the gradient with respect to whose output the backward stores as
+    half (train_gradient_storage="fp16"; empty otherwise)."""
 
-    def __init__(self, *a):
+    def __init__(self, *a, grad16=frozenset()):
         super().__init__(*a)
-        self.amax = {}
-        self.half_in = set()
-        self.grad16 = set()
+        self.half = {}
+        self.grad16 = grad16
+
+    @property
+    def half_in(self):
+        """The plan indices of the convs that read a half input."""
+        return {li for li, amax in self.half.items() if amax is None}
 
 
 class _HourglassFunction(torch.autograd.Function):
@@ -1228,6 +1219,24 @@ def _reduced(reducer, grads):
     return [reducer.result(g) for g in grads]
 
 
+class _FixedSwitch:
+    """A precision switch of DreamHourglass on a class that has one setting of it only: reads as ``value``, and assigning anything
+    else raises ValueError("<refusal>: <name>=<the value> is not supported").  ``why``: the reason, for the reader."""
+
+    def __init__(self, value, refusal, why):
+        self.value, self.refusal, self.__doc__ = value, refusal, "Always %r: %s." % (value, why)
+
+    def __set_name__(self, owner, name):
+        self.name = name
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else self.value
+
+    def __set__(self, obj, value):
+        if value != self.value:
+            raise ValueError("%s: %s=%r is not supported" % (self.refusal, self.name, value))
+
+
 class DreamHourglassMultiStage(nn.Module):
     """The reference's DreamHourglassMultiStage (models.py:350-553): ``stage1`` .. ``stageS`` hourglasses (same
     ``state_dict()`` keys); stage s > 1 reads cat([image, belief maps of stage s-1]) -- the maps nearest-upsampled x4
@@ -1273,47 +1282,12 @@ class DreamHourglassMultiStage(nn.Module):
         for st in self.stages():
             st.precision = value
 
-    @property
-    def activation_storage(self):
-        """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.activation_storage)."""
-        return "fp32"
-
-    @activation_storage.setter
-    def activation_storage(self, value):
-        if value != "fp32":
-            raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
-
-    @property
-    def conv_ksplit(self):
-        """Always "off": the stages run the fp32-storage walk (DreamHourglass.conv_ksplit)."""
-        return "off"
-
-    @conv_ksplit.setter
-    def conv_ksplit(self, value):
-        if value != "off":
-            raise ValueError("DreamHourglassMultiStage does not split its convs: conv_ksplit=%r is not supported" % (value,))
-
-    @property
-    def train_gradient_storage(self):
-        """Always "fp32": the stages hand fp32 gradients to one another (DreamHourglass.train_gradient_storage)."""
-        return "fp32"
-
-    @train_gradient_storage.setter
-    def train_gradient_storage(self, value):
-        if value != "fp32":
-            raise ValueError("DreamHourglassMultiStage stores its gradients in fp32 only: train_gradient_storage=%r is not supported"
-                             % (value,))
-
-    @property
-    def train_activation_storage(self):
-        """Always "fp32": the glue between the stages (stage_input) is fp32 (DreamHourglass.train_activation_storage)."""
-        return "fp32"
-
-    @train_activation_storage.setter
-    def train_activation_storage(self, value):
-        if value != "fp32":
-            raise ValueError("DreamHourglassMultiStage stores its activations in fp32 only: train_activation_storage=%r is not supported"
-                             % (value,))
+    _FP32_ACTIVATIONS = "DreamHourglassMultiStage stores its activations in fp32 only"
+    activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
+    conv_ksplit = _FixedSwitch("off", "DreamHourglassMultiStage does not split its convs", "the stages run the fp32-storage walk")
+    train_gradient_storage = _FixedSwitch("fp32", "DreamHourglassMultiStage stores its gradients in fp32 only",
+                                          "the stages hand fp32 gradients to one another")
+    train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
 
     @property
     def train_precision(self):
@@ -1489,56 +1463,13 @@ class ResnetSimple(nn.Module):
         # ``freeze`` is accepted and unused, exactly as in the reference (models.py:19: never read).
         self.imagenet_initialised = _pretrained.init_resnet101_trunk(self) if pretrained else False
 
-    @property
-    def train_precision(self):
-        """Always "fp32": BatchNorm training on the fp16 matrix cores is not built (DreamHourglass.train_precision)."""
-        return "fp32"
-
-    @train_precision.setter
-    def train_precision(self, value):
-        if value != "fp32":
-            raise ValueError("ResnetSimple trains in fp32 only: train_precision=%r is not supported" % (value,))
-
-    @property
-    def activation_storage(self):
-        """Always "fp32": the stride-2 trunk convs, the 3x3 max-pool and the 4x4 transposed convs read and write fp32
-        (DreamHourglass.activation_storage)."""
-        return "fp32"
-
-    @activation_storage.setter
-    def activation_storage(self, value):
-        if value != "fp32":
-            raise ValueError("ResnetSimple stores its activations in fp32 only: activation_storage=%r is not supported" % (value,))
-
-    @property
-    def conv_ksplit(self):
-        """Always "off": its convs read and write fp32 (DreamHourglass.conv_ksplit)."""
-        return "off"
-
-    @conv_ksplit.setter
-    def conv_ksplit(self, value):
-        if value != "off":
-            raise ValueError("ResnetSimple does not split its convs: conv_ksplit=%r is not supported" % (value,))
-
-    @property
-    def train_gradient_storage(self):
-        """Always "fp32": ResnetSimple trains in fp32 only (DreamHourglass.train_gradient_storage)."""
-        return "fp32"
-
-    @train_gradient_storage.setter
-    def train_gradient_storage(self, value):
-        if value != "fp32":
-            raise ValueError("ResnetSimple stores its gradients in fp32 only: train_gradient_storage=%r is not supported" % (value,))
-
-    @property
-    def train_activation_storage(self):
-        """Always "fp32": ResnetSimple trains in fp32 only (DreamHourglass.train_activation_storage)."""
-        return "fp32"
-
-    @train_activation_storage.setter
-    def train_activation_storage(self, value):
-        if value != "fp32":
-            raise ValueError("ResnetSimple stores its activations in fp32 only: train_activation_storage=%r is not supported" % (value,))
+    _FP32_ACTIVATIONS = "ResnetSimple stores its activations in fp32 only"
+    train_precision = _FixedSwitch("fp32", "ResnetSimple trains in fp32 only", "BatchNorm training on the fp16 matrix cores is not built")
+    activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS,
+                                      "the stride-2 trunk convs, the 3x3 max-pool and the 4x4 transposed convs read and write fp32")
+    conv_ksplit = _FixedSwitch("off", "ResnetSimple does not split its convs", "its convs read and write fp32")
+    train_gradient_storage = _FixedSwitch("fp32", "ResnetSimple stores its gradients in fp32 only", "ResnetSimple trains in fp32 only")
+    train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "ResnetSimple trains in fp32 only")
 
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""

@@ -321,7 +321,7 @@ def check_entries_outside_the_run_bit_equal(dev):
                 assert torch.equal(ops.maxpool2(inp), out), li
             elif tc.is_plain(kind, mod, flags, int(inp.shape[3])):
                 w, bias = params[m._param_slot[li]], params[m._param_slot[li] + 1]
-                again, _ = m._conv_f16(kind, mod, inp, ops.absmax(inp), w, bias, flags)
+                again, _ = m._conv_half("f16", kind, mod, inp, ops.absmax(inp), w, bias, flags)
                 assert torch.equal(again, out), li
             else:
                 w, bias = params[m._param_slot[li]], params[m._param_slot[li] + 1]

@@ -63,6 +63,8 @@ def write(fixture, path):
     with open(path, "w") as f:
         f.write('{"launches": [\n' + ",\n".join(json.dumps(s) for s in fixture["launches"]) + '\n],\n"cases": {\n')
         f.write(",\n".join("%s: %s" % (json.dumps(n), json.dumps(c, separators=(",", ":"))) for n, c in fixture["cases"].items()))
+        for key in sorted(set(fixture) - {"launches", "cases"}):           # further entries: one mapping each, a line per item
+            f.write("\n},\n%s: {\n" % json.dumps(key) + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v)) for k, v in fixture[key].items()))
         f.write("\n}}\n")
 
 
