@@ -20,114 +20,65 @@
 
 namespace {
 
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
+// ---- the forms of the kernel ---------------------------------------------------------------------------------------------------------
+// One kernel text (conv_f16_body.inc, conv_f16_epilogue.inc), nine kernels per tile: each form is a kernel of its own from the same
+// text, so that adding one leaves the machine code of the measured ones as it is (tools/isa_same.py).  This table is the
+// one place that says what a form is: the five constants the body and the epilogue read, and what launch_f16 accepts with it.
+//   plain          fp32 x (scaled by its amax while staged), fp32 y: precision="fp16"
+//   mask           + the DREAM_CONV_RELUMASK epilogue, y = residual > 0 ? conv : 0 -- the data gradient of a conv behind a ReLU
+//                  (train_precision="fp16")
+//   act16          x and an NHWC y are IEEE halfs (activation_storage="fp16"): the stored half IS the MFMA operand -- the patch is copied
+//                  into LDS in 16-byte pieces of 8 halfs (no v_cvt, no multiply), 2^-ew is the whole output scale, amax_in is not read;
+//                  the epilogue saturates, rounds and stores halfs (the NCHW output stays fp32)
+//   mask16         mask with the mask tensor stored as IEEE half (train_activation_storage="fp16")
+//   ksplit         act16 on slice blockIdx.z of the gridDim.z slices of the Cin/32 x taps stages (conv_ksplit="auto"):
+//                  the raw fp32 accumulator tile goes to p.y = workspace[slice] (NHWC fp32), no atomics -- conv_f16_ksplit_finish_kernel
+//                  sums the slices in a fixed order.  Plain stride-1 convs only (no pool, upsample, NCHW)
+//   g16 ...        data gradients stored as IEEE half (train_gradient_storage="fp16"): every data gradient of the
+//                  encoder's half run lives in HBM as half(clamp(g * 2^e_g)), e_g = grad_scale_exponent(*p.grad_amax) -- one exponent per
+//                  backward pass, derived by every launch from the loss gradient's amax (half_scale.h).  The chain is linear, so the
+//                  factor travels: GRAD16 = 1 "entry" (the boundary conv: fp32 g in, scaled by its own amax as the plain form does;
+//                  y * 2^e_g stored as half), 2 "interior" (half g in and out: act16's loader and saturating store, no scale), 3 "exit"
+//                  (half g in, y * 2^-e_g stored as fp32, amax_out after the mask).  The mask, where there is one, is a half tensor; the
+//                  unmasked interior form is act16 itself.  amax_out of the half-writing forms: max|y * 2^e_g| of what is stored, before
+//                  the saturation.
+enum Form16 { kPlain, kMask, kAct16, kMask16, kKsplit, kG16Entry, kG16EntryMask, kG16Interior, kG16Exit, kNumForms };
+
+// the flags whose launches are never split (conv_ksplit: the large-map layers and the K-channel output)
+constexpr int kKsplitRefused = DREAM_CONV_POOL2 | DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_RELUMASK;
+
+struct Form16Row {
+    const char *name;
+    bool EPI_MASK, ACT16, MASK16, KSPLIT;     // the kernel's constants
+    int GRAD16;
+    bool affine;                              // launch_f16: scale / shift may be given
+    bool residual;                            //             `residual` may be a true residual (a form with EPI_MASK: it IS the mask)
+    int flags_ok;                             //             the flag bits the form accepts
+    // what follows from the constants: x is half (16-byte aligned, amax_in unused); an NHWC y is half; grad_amax is read
+    constexpr bool x16() const { return ACT16; }
+    constexpr bool y16() const { return GRAD16 == 0 ? ACT16 : GRAD16 != 3; }
+    constexpr bool needs_grad_amax() const { return GRAD16 == 1 || GRAD16 == 3; }
+};
+constexpr Form16Row kForms[kNumForms] = {
+    //  name                EPI_MASK ACT16  MASK16 KSPLIT GRAD16 affine residual flags_ok
+    {"plain",               false,   false, false, false, 0,     true,  true,    ~DREAM_CONV_RELUMASK},
+    {"mask",                true,    false, false, false, 0,     true,  false,   ~0},
+    {"act16",               false,   true,  false, false, 0,     true,  false,   ~DREAM_CONV_RELUMASK},
+    {"mask16",              true,    false, true,  false, 0,     true,  false,   ~0},
+    {"ksplit",              false,   true,  false, true,  0,     false, false,   ~kKsplitRefused},
+    {"g16 entry",           false,   false, false, false, 1,     false, false,   0},
+    {"g16 entry + mask",    true,    false, true,  false, 1,     false, false,   DREAM_CONV_RELUMASK},
+    {"g16 interior",        true,    true,  true,  false, 2,     false, false,   DREAM_CONV_RELUMASK},
+    {"g16 exit",            true,    true,  true,  false, 3,     false, false,   DREAM_CONV_RELUMASK},
+};
+
+template <int FORM, int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = false;
-    constexpr bool ACT16 = false;
-    constexpr bool MASK16 = false;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 0;
-#include "conv_f16_body.inc"
-}
-
-// The same kernel with the DREAM_CONV_RELUMASK epilogue (y = residual > 0 ? conv : 0: the data gradient of a conv behind a ReLU,
-// train_precision="fp16").  A kernel of its own, from the same text, so that the inference kernels above stay instruction-identical.
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = true;
-    constexpr bool ACT16 = false;
-    constexpr bool MASK16 = false;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 0;
-#include "conv_f16_body.inc"
-}
-
-// The same kernel on activations stored as IEEE half (activation_storage="fp16"; the *_nhwc_f16 entry points): p.x and an NHWC p.y
-// are halfs.  The stored half IS the MFMA operand -- the patch is copied into LDS in 16-byte pieces of 8 halfs (half the load
-// instructions and bytes, no v_cvt, no multiply; on the `db` variants half the registers that hold the next chunk's patch), 2^-ew is
-// the whole output scale and amax_in is not read; the epilogue saturates, rounds and stores halfs (the NCHW output stays fp32).
-// Again a kernel of its own from the same text.
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_act16_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = false;
-    constexpr bool ACT16 = true;
-    constexpr bool MASK16 = false;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 0;
-#include "conv_f16_body.inc"
-}
-
-// conv_f16_mask_kernel with the mask tensor stored as IEEE half (train_activation_storage="fp16": the saved output of the conv in
-// front is half): `residual` points to halfs, y = mask > 0 ? conv : 0.  x, y and amax_out are as in conv_f16_mask_kernel.
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_mask16_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = true;
-    constexpr bool ACT16 = false;
-    constexpr bool MASK16 = true;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 0;
-#include "conv_f16_body.inc"
-}
-
-// conv_f16_act16_kernel on one slice of the contraction (conv_ksplit="auto": small-batch inference, where the grid of a deep layer
-// fills a few per cent of the chip): gridDim.z slices of the Cin/32 x taps stages, each workgroup runs the stages of
-// slice blockIdx.z -- same loader, same MFMA loop -- and stores its raw fp32 accumulator tile to p.y = workspace[slice] (NHWC fp32).
-// No atomics: conv_f16_ksplit_finish_kernel sums the slices in a fixed order.  Plain stride-1 convs only (no pool, upsample, NCHW).
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_ksplit_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = false;
-    constexpr bool ACT16 = true;
-    constexpr bool MASK16 = false;
-    constexpr bool KSPLIT = true;
-    constexpr int GRAD16 = 0;
-#include "conv_f16_body.inc"
-}
-
-// ---- data gradients stored as IEEE half (train_gradient_storage="fp16") ------------------------------------------
-// Every data gradient of the encoder's half run lives in HBM as half(clamp(g * 2^e_g)), e_g = grad_scale_exponent(*p.grad_amax) -- one
-// exponent per backward pass, derived by every launch from the loss gradient's amax (half_scale.h).  The chain is linear, so the factor
-// travels: GRAD16 = 1 "entry" (the boundary conv: fp32 g in, scaled by its own amax as conv_f16_kernel does; y * 2^e_g stored as half),
-// 2 "interior" (half g in and out: the stored half IS the operand -- ACT16's loader and saturating store --, no scale), 3 "exit" (half g
-// in, y * 2^-e_g stored as fp32, amax_out after the mask).  The mask, where there is one, is a half tensor (MASK16); the unmasked
-// interior form is conv_f16_act16_kernel itself.  amax_out of the half-writing forms: max|y * 2^e_g| of what is stored, before the
-// saturation.  Kernels of their own from the same text.
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_entry_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = false;
-    constexpr bool ACT16 = false;
-    constexpr bool MASK16 = false;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 1;
-#include "conv_f16_body.inc"
-}
-
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_entry_mask16_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = true;
-    constexpr bool ACT16 = false;
-    constexpr bool MASK16 = true;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 1;
-#include "conv_f16_body.inc"
-}
-
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_mask16_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = true;
-    constexpr bool ACT16 = true;
-    constexpr bool MASK16 = true;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 2;
-#include "conv_f16_body.inc"
-}
-
-template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_g16_exit_kernel(const Conv16Params p) {
-    constexpr bool EPI_MASK = true;
-    constexpr bool ACT16 = true;
-    constexpr bool MASK16 = true;
-    constexpr bool KSPLIT = false;
-    constexpr int GRAD16 = 3;
+    constexpr bool EPI_MASK = kForms[FORM].EPI_MASK;
+    constexpr bool ACT16 = kForms[FORM].ACT16;
+    constexpr bool MASK16 = kForms[FORM].MASK16;
+    constexpr bool KSPLIT = kForms[FORM].KSPLIT;
+    constexpr int GRAD16 = kForms[FORM].GRAD16;
 #include "conv_f16_body.inc"
 }
 
@@ -171,18 +122,12 @@ __global__ void __launch_bounds__(256) conv_f16_ksplit_finish_kernel(const float
 struct Variant16h {
     const char *name;
     int BM, BN, NP_MAX, threads, abufs;
-    void (*kernel)(const Conv16Params);
-    void (*mask_kernel)(const Conv16Params);
-    void (*act16_kernel)(const Conv16Params);
-    void (*mask16_kernel)(const Conv16Params);
-    void (*ksplit_kernel)(const Conv16Params);
-    void (*g16_kernel[4])(const Conv16Params);      // entry, entry + mask, interior + mask, exit
+    void (*kernel[kNumForms])(const Conv16Params);
 };
-#define F16_KERNELS(...) \
-    conv_f16_kernel<__VA_ARGS__>, conv_f16_mask_kernel<__VA_ARGS__>, conv_f16_act16_kernel<__VA_ARGS__>, conv_f16_mask16_kernel<__VA_ARGS__>, \
-    conv_f16_ksplit_kernel<__VA_ARGS__>, \
-    {conv_f16_g16_entry_kernel<__VA_ARGS__>, conv_f16_g16_entry_mask16_kernel<__VA_ARGS__>, conv_f16_g16_mask16_kernel<__VA_ARGS__>, \
-     conv_f16_g16_exit_kernel<__VA_ARGS__>}
+#define F16_KERNELS(...) /* in the order of Form16 */ \
+    {conv_f16_kernel<kPlain, __VA_ARGS__>, conv_f16_kernel<kMask, __VA_ARGS__>, conv_f16_kernel<kAct16, __VA_ARGS__>, \
+     conv_f16_kernel<kMask16, __VA_ARGS__>, conv_f16_kernel<kKsplit, __VA_ARGS__>, conv_f16_kernel<kG16Entry, __VA_ARGS__>, \
+     conv_f16_kernel<kG16EntryMask, __VA_ARGS__>, conv_f16_kernel<kG16Interior, __VA_ARGS__>, conv_f16_kernel<kG16Exit, __VA_ARGS__>}
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -211,35 +156,34 @@ int variant_f16(long pixels, int Cin, int Cout, int ntaps) {
     return g_forced_f16 >= 0 ? g_forced_f16 : v;
 }
 
-// conv_ksplit: the flags whose launches are never split (the large-map layers and the K-channel output); the workgroups a split
-// launch may reach, the fewest stages a slice is left with, the most slices.  Measured per layer at 1 .. 16 frames
+// conv_ksplit (the flags whose launches are never split: kKsplitRefused above): the workgroups a split launch may reach, the fewest
+// stages a slice is left with, the most slices.  Measured per layer at 1 .. 16 frames
 // (profiles/ab_f16_ksplit.txt): a split pays where the unsplit grid is at most ~190 workgroups AND the contraction is
 // long -- 512->512 at 25 x 25, one frame: 0.071 -> 0.028 ms with 8 slices; at 50 x 50: 0.072 -> 0.041 with 4 --; from ~310 workgroups
 // on every split lost, and so did slices of 9 .. 18 stages (a 128->128 conv of 36 stages at 157 workgroups: 0.022 -> 0.025 ms in two
 // slices: the finishing pass costs what the halved workgroups save)
-constexpr int kKsplitRefused = DREAM_CONV_POOL2 | DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_RELUMASK;
 constexpr int kKsplitTargetWorkgroups = 384;
 constexpr int kKsplitMinStages = 24;
 constexpr int kKsplitMax = 16;
 
-// act16: x and an NHWC y are halfs (conv_f16_act16_kernel), amax_in is not used; mask16: the ReLU mask (`residual`) is a half tensor;
-// grad16 = 1 | 2 | 3: the entry / interior / exit form of a half-stored data gradient (the GRAD16 kernels; act16 then says that x is
-// half: forms 2 and 3), grad_amax the scalar e_g is derived from
-int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale, const float *shift,
-               const float *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad, const Geom16 &g,
-               int flags, void *stream, bool act16 = false, bool mask16 = false, int ksplit = 0, int grad16 = 0,
-               const unsigned *grad_amax = nullptr) {
-    DREAM_REQUIRE(x && (amax_in || act16) && w && w_exp && y, "conv_f16: null pointer");
-    DREAM_REQUIRE(!act16 || grad16 || (residual == nullptr && !(flags & DREAM_CONV_RELUMASK)), "conv_f16: half storage takes no residual / ReLU mask");
-    DREAM_REQUIRE(!(act16 || grad16) || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
-    DREAM_REQUIRE(grad16 == 0 || (grad16 >= 1 && grad16 <= 3 && act16 == (grad16 != 1) && ksplit == 0 && scale == nullptr && shift == nullptr
-                                  && (grad16 == 2 || grad_amax != nullptr) && (flags & ~DREAM_CONV_RELUMASK) == 0 && g.out_scale == 1
-                                  && (residual == nullptr || (mask16 && ((size_t)residual & 3) == 0)) && (grad16 == 1 || residual != nullptr)),
-                  "conv_f16: a half-stored data gradient is a plain conv with an optional half mask");
+// One launch of `form` (kForms).  `residual`: the true residual or, with DREAM_CONV_RELUMASK, the mask (fp32 or half, as the form
+// says); ksplit: the slices of the ksplit form, y = the fp32 workspace (dream_conv2d_f16_ksplit_nhwc_f16); grad_amax: the scalar the g16
+// entry / exit forms derive e_g from
+int launch_f16(Form16 form, const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale,
+               const float *shift, const void *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad,
+               const Geom16 &g, int flags, void *stream, int ksplit = 0, const unsigned *grad_amax = nullptr) {
+    const Form16Row &f = kForms[form];
+    DREAM_REQUIRE(x && (amax_in || f.x16()) && w && w_exp && y, "conv_f16: null pointer");
+    DREAM_REQUIRE((flags & ~f.flags_ok) == 0, "conv_f16: the %s form does not take flags %d", f.name, flags & ~f.flags_ok);
+    DREAM_REQUIRE(f.affine || (scale == nullptr && shift == nullptr), "conv_f16: the %s form takes no scale / shift", f.name);
+    DREAM_REQUIRE(f.EPI_MASK || f.residual || residual == nullptr, "conv_f16: the %s form takes no residual", f.name);
+    DREAM_REQUIRE(!(f.x16() || f.y16()) || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
+    DREAM_REQUIRE(!(f.GRAD16 && f.MASK16) || ((size_t)residual & 3) == 0, "conv_f16: the half mask of the %s form must be 4-byte aligned", f.name);
+    DREAM_REQUIRE(!f.needs_grad_amax() || grad_amax != nullptr, "conv_f16: the %s form needs the loss gradient's amax", f.name);
     DREAM_REQUIRE(Cin % KC == 0, "conv_f16: Cin=%d must be a multiple of %d", Cin, KC);
     Conv16Params p;
     p.x = (const float *)x; p.w_hi = (const _Float16 *)w; p.w_lo = nullptr; p.w_exp = w_exp; p.amax_in = amax_in;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.y = (float *)y; p.amax_out = amax_out;
+    p.scale = scale; p.shift = shift; p.residual = (const float *)residual; p.y = (float *)y; p.amax_out = amax_out;
     p.B = B;
     p.Cin = Cin; p.Cout = Cout; p.CoutPad = CoutPad;
     const long pixels = (long)B * g.H * g.W;
@@ -252,15 +196,11 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     const bool mask = (flags & DREAM_CONV_RELUMASK) != 0;
     DREAM_REQUIRE(!mask || (residual != nullptr && !pool && !(flags & (DREAM_CONV_OUT_NCHW | DREAM_CONV_RES_AFTER_RELU)) && g.out_scale == 1),
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
-    DREAM_REQUIRE(!mask16 || (mask && (!act16 || grad16)), "conv_f16: a half mask goes with DREAM_CONV_RELUMASK on fp32 activations");
-    DREAM_REQUIRE(!grad16 || mask == (residual != nullptr), "conv_f16: the mask of a half-stored data gradient goes with DREAM_CONV_RELUMASK");
-    // ksplit > 0: that many slices of the contraction, y = the fp32 workspace (dream_conv2d_f16_ksplit_nhwc_f16)
-    DREAM_REQUIRE(ksplit == 0 || (act16 && !(flags & kKsplitRefused) && g.out_scale == 1 && ksplit <= 1024),
-                  "conv_f16: a split launch is a plain half-storage conv of at most 1024 slices");
-    if (grad16) p.grad_amax = grad_amax;           // (shares w_lo's slot, which these kernels do not read)
-    void (*const kernel)(const Conv16Params) =
-        grad16 ? var.g16_kernel[grad16 == 1 ? (mask ? 1 : 0) : grad16]
-               : ksplit ? var.ksplit_kernel : (act16 ? var.act16_kernel : (mask ? (mask16 ? var.mask16_kernel : var.mask_kernel) : var.kernel));
+    DREAM_REQUIRE(!f.EPI_MASK || mask, "conv_f16: the %s form goes with DREAM_CONV_RELUMASK", f.name);
+    DREAM_REQUIRE(f.KSPLIT ? ksplit >= 1 && ksplit <= 1024 : ksplit == 0, "conv_f16: a split launch is the ksplit form in 1 .. 1024 slices");
+    DREAM_REQUIRE(!(f.KSPLIT || f.GRAD16) || g.out_scale == 1, "conv_f16: the %s form is a plain conv", f.name);
+    if (f.GRAD16) p.grad_amax = grad_amax;         // (shares w_lo's slot, which these kernels do not read)
+    void (*const kernel)(const Conv16Params) = var.kernel[form];
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
     DREAM_REQUIRE(p.PH * p.PW <= var.NP_MAX, "conv_f16: patch of %d pixels exceeds the variant's %d", p.PH * p.PW, var.NP_MAX);
     const size_t lds = ((size_t)var.abufs * p.PH * p.PW + (size_t)2 * var.BN) * S16 * sizeof(_Float16);
@@ -271,6 +211,34 @@ int launch_f16(const void *x, const unsigned *amax_in, const void *w, const int 
     hipLaunchKernelGGL(kernel, grid, dim3(var.threads), lds, (hipStream_t)stream, p);
     DREAM_LAUNCH_OK();
     return 0;
+}
+
+// what the k x k entry points require of their shape arguments
+int check_conv2d_f16(int H, int W, int ksize, int stride, int flags) {
+    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
+    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
+    return 0;
+}
+
+// the two transposed convs by their sub-pixel phases, on fp32 (kPlain) or half (kAct16: amax_in null) activations
+int convT4_f16(Form16 form, const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *scale,
+               const float *shift, void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int flags,
+               void *stream) {
+    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
+                  "convT4x4_f16: unsupported flags");
+    return for_convT4_phases(H, W, Cin, CoutPad, [&](const Geom16 &g, size_t off) {
+        return launch_f16(form, x, amax_in, (const _Float16 *)w + off, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g,
+                          flags, stream);
+    });
+}
+
+int convT3_f16(Form16 form, const void *x, const unsigned *amax_in, const void *w, const int *w_exp, const float *bias, void *y,
+               unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream) {
+    DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16: only the ReLU flag is supported");
+    return for_convT3_phases(H, W, [&](const Geom16 &g) {
+        return launch_f16(form, x, amax_in, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+    });
 }
 
 }  // namespace
@@ -286,11 +254,10 @@ extern "C" int dream_conv2d_f16_nhwc_f32(const float *x, const unsigned *amax_in
                                          const float *scale, const float *shift, const float *residual, float *y,
                                          unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
                                          int stride, int flags, void *stream) {
-    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
-    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
-    DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
+    if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
     const Geom16 g = geom16_conv(H, W, ksize, flags);
-    return launch_f16(x, amax_in, w, w_exp, scale, shift, residual, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+    return launch_f16((flags & DREAM_CONV_RELUMASK) ? kMask : kPlain, x, amax_in, w, w_exp, scale, shift, residual, y, amax_out, B, Cin,
+                      Cout, CoutPad, g, flags, stream);
 }
 
 // dream_conv2d_f16_nhwc_f32 with DREAM_CONV_RELUMASK (set here) and the mask stored as IEEE half (train_activation_storage="fp16"):
@@ -299,13 +266,11 @@ extern "C" int dream_conv2d_f16_mask16_nhwc_f32(const float *x, const unsigned *
                                                 const float *scale, const float *shift, const void *mask, float *y,
                                                 unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad, int ksize,
                                                 int stride, int flags, void *stream) {
-    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
-    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
     DREAM_REQUIRE(mask != nullptr && !(flags & DREAM_CONV_UPSAMPLE2X), "conv2d_f16_mask16: needs the mask, takes no upsample");
     flags |= DREAM_CONV_RELUMASK;
     const Geom16 g = geom16_conv(H, W, ksize, flags);
-    return launch_f16(x, amax_in, w, w_exp, scale, shift, (const float *)mask, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream,
-                      false, true);
+    return launch_f16(kMask16, x, amax_in, w, w_exp, scale, shift, mask, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
 }
 
 // ConvTranspose2d(k=4,s=2,p=1) on the fp16 path: the four 2x2-tap sub-pixel phases of dream_conv_transpose4x4s2_f16x3_nhwc_f32.
@@ -313,29 +278,14 @@ extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f32(const float *x, const unsi
                                                       const float *scale, const float *shift, float *y, unsigned *amax_out,
                                                       int B, int H, int W, int Cin, int Cout, int CoutPad, int flags,
                                                       void *stream) {
-    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
-                  "convT4x4_f16: unsupported flags");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT4_phase(H, W, ph);
-        const size_t off = (size_t)ph * 4 * CoutPad * Cin;
-        if (int rc = launch_f16(x, amax_in, (const _Float16 *)w + off, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout,
-                                CoutPad, g, flags, stream))
-            return rc;
-    }
-    return 0;
+    return convT4_f16(kPlain, x, amax_in, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
 }
 
 // ConvTranspose2d(k=3,s=2,p=1,output_padding 1) on the fp16 path: the phases of dream_conv_transpose3x3s2_f16x3_nhwc_f32.
 extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
                                                       const float *bias, float *y, unsigned *amax_out, int B, int H, int W,
                                                       int Cin, int Cout, int CoutPad, int flags, void *stream) {
-    DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16: only the ReLU flag is supported");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT3_phase(H, W, ph);
-        if (int rc = launch_f16(x, amax_in, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
-            return rc;
-    }
-    return 0;
+    return convT3_f16(kPlain, x, amax_in, w, w_exp, bias, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
 }
 
 // ---- activations stored as IEEE half (activation_storage="fp16") -----------------------------------------------------------------
@@ -345,38 +295,21 @@ extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsi
 extern "C" int dream_conv2d_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
                                          void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
                                          int ksize, int stride, int flags, void *stream) {
-    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
-    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
-    DREAM_REQUIRE(!(flags & DREAM_CONV_UPSAMPLE2X) || (H % 2 == 0 && W % 2 == 0), "fused x2 upsample needs even H, W");
+    if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
     const Geom16 g = geom16_conv(H, W, ksize, flags);
-    return launch_f16(x, nullptr, w, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream, true);
+    return launch_f16(kAct16, x, nullptr, w, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
 }
 
 extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
                                                       const float *shift, void *y, unsigned *amax_out, int B, int H, int W,
                                                       int Cin, int Cout, int CoutPad, int flags, void *stream) {
-    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
-                  "convT4x4_f16: unsupported flags");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT4_phase(H, W, ph);
-        const size_t off = (size_t)ph * 4 * CoutPad * Cin;
-        if (int rc = launch_f16(x, nullptr, (const _Float16 *)w + off, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout,
-                                CoutPad, g, flags, stream, true))
-            return rc;
-    }
-    return 0;
+    return convT4_f16(kAct16, x, nullptr, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
 }
 
 extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *bias, void *y,
                                                       unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int CoutPad,
                                                       int flags, void *stream) {
-    DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16: only the ReLU flag is supported");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT3_phase(H, W, ph);
-        if (int rc = launch_f16(x, nullptr, w, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream, true))
-            return rc;
-    }
-    return 0;
+    return convT3_f16(kAct16, x, nullptr, w, w_exp, bias, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
 }
 
 // ---- data gradients stored as IEEE half (train_gradient_storage="fp16") ------------------------------------------
@@ -392,8 +325,8 @@ extern "C" int dream_conv2d_f16_g16_entry_nhwc_f16(const float *x, const unsigne
     DREAM_REQUIRE(grad_amax != nullptr, "conv2d_f16_g16_entry: needs the loss gradient's amax");
     const int fl = mask ? DREAM_CONV_RELUMASK : 0;
     const Geom16 g = geom16_conv(H, W, ksize, fl);
-    return launch_f16(x, amax_in, w, w_exp, nullptr, nullptr, (const float *)mask, y, peak, B, Cin, Cout, CoutPad, g, fl, stream, false,
-                      mask != nullptr, 0, 1, grad_amax);
+    return launch_f16(mask ? kG16EntryMask : kG16Entry, x, amax_in, w, w_exp, nullptr, nullptr, mask, y, peak, B, Cin, Cout, CoutPad, g, fl,
+                      stream, 0, grad_amax);
 }
 
 // interior: x half (already times 2^e_g) -> y = half(clamp(conv)): no scale is read.  Without a mask this IS dream_conv2d_f16_nhwc_f16.
@@ -402,9 +335,8 @@ extern "C" int dream_conv2d_f16_g16_nhwc_f16(const void *x, const void *w, const
                                              void *stream) {
     DREAM_REQUIRE(ksize == 3 && stride == 1 && flags == 0, "conv2d_f16_g16: a plain 3x3 stride-1 conv (flags 0)");
     const Geom16 g = geom16_conv(H, W, ksize, 0);
-    if (mask == nullptr) return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, nullptr, y, peak, B, Cin, Cout, CoutPad, g, 0, stream, true);
-    return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, (const float *)mask, y, peak, B, Cin, Cout, CoutPad, g, DREAM_CONV_RELUMASK,
-                      stream, true, true, 0, 2, nullptr);
+    return launch_f16(mask ? kG16Interior : kAct16, x, nullptr, w, w_exp, nullptr, nullptr, mask, y, peak, B, Cin, Cout, CoutPad, g,
+                      mask ? DREAM_CONV_RELUMASK : 0, stream);
 }
 
 // exit: x half (times 2^e_g), mask required -> y = (mask > 0 ? conv : 0) * 2^-e_g as fp32; amax_out = max|y| after the mask
@@ -414,8 +346,8 @@ extern "C" int dream_conv2d_f16_g16_exit_nhwc_f32(const void *x, const void *w, 
     DREAM_REQUIRE(ksize == 3 && stride == 1 && flags == 0, "conv2d_f16_g16_exit: a plain 3x3 stride-1 conv (flags 0)");
     DREAM_REQUIRE(mask != nullptr && grad_amax != nullptr, "conv2d_f16_g16_exit: needs the mask and the loss gradient's amax");
     const Geom16 g = geom16_conv(H, W, ksize, DREAM_CONV_RELUMASK);
-    return launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, (const float *)mask, y, amax_out, B, Cin, Cout, CoutPad, g,
-                      DREAM_CONV_RELUMASK, stream, true, true, 0, 3, grad_amax);
+    return launch_f16(kG16Exit, x, nullptr, w, w_exp, nullptr, nullptr, mask, y, amax_out, B, Cin, Cout, CoutPad, g, DREAM_CONV_RELUMASK,
+                      stream, 0, grad_amax);
 }
 
 // ---- conv_ksplit="auto": the contraction of a small-grid conv divided over workgroups ---------------------------
@@ -452,7 +384,7 @@ extern "C" size_t dream_conv2d_f16_ksplit_workspace(int B, int H, int W, int Cou
     return (size_t)S * ((((size_t)B * H * W * Cout) + 7) & ~(size_t)7) * sizeof(float);
 }
 
-// dream_conv2d_f16_nhwc_f16 in S slices: S launches' worth of workgroups in one grid (conv_f16_ksplit_kernel), then the finishing
+// dream_conv2d_f16_nhwc_f16 in S slices: S launches' worth of workgroups in one grid (the ksplit form), then the finishing
 // pass.  S == 1 is dream_conv2d_f16_nhwc_f16 itself (the workspace is not touched).
 extern "C" int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
                                                 const float *shift, void *y, unsigned *amax_out, void *workspace, int S, int B,
@@ -460,13 +392,12 @@ extern "C" int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, co
                                                 void *stream) {
     DREAM_REQUIRE(S >= 1, "conv2d_f16_ksplit: S=%d", S);
     if (S == 1) return dream_conv2d_f16_nhwc_f16(x, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, ksize, stride, flags, stream);
-    DREAM_REQUIRE(ksize == 1 || ksize == 3, "conv2d_f16: kernel size %d not supported", ksize);
-    DREAM_REQUIRE(stride == 1, "conv2d_f16: stride %d not supported (strided convs stay on the fp32 kernel)", stride);
+    if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
     DREAM_REQUIRE(!(flags & kKsplitRefused), "conv2d_f16_ksplit: flags %d: a launch with a fused pool / upsample / NCHW output is not split", flags);
     DREAM_REQUIRE(workspace && y && (((size_t)workspace | (size_t)y) & 15) == 0, "conv2d_f16_ksplit: workspace and y must be 16-byte aligned");
     const Geom16 g = geom16_conv(H, W, ksize, flags);
-    if (int rc = launch_f16(x, nullptr, w, w_exp, nullptr, nullptr, nullptr, workspace, nullptr, B, Cin, Cout, CoutPad, g,
-                            flags & ~DREAM_CONV_RELU, stream, true, false, S))
+    if (int rc = launch_f16(kKsplit, x, nullptr, w, w_exp, nullptr, nullptr, nullptr, workspace, nullptr, B, Cin, Cout, CoutPad, g,
+                            flags & ~DREAM_CONV_RELU, stream, S))
         return rc;
     const size_t n = (size_t)B * H * W * Cout, slice = (n + 7) & ~(size_t)7;
     hipLaunchKernelGGL(conv_f16_ksplit_finish_kernel, dim3((unsigned)(slice / 8 / 256 < 4096 ? slice / 8 / 256 + 1 : 4096)), dim3(256), 0, (hipStream_t)stream,

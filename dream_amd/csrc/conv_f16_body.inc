@@ -1,5 +1,5 @@
-// Body of conv_f16_kernel / conv_f16_mask_kernel / conv_f16_act16_kernel / conv_f16_mask16_kernel / conv_f16_ksplit_kernel / conv_f16_g16_*_kernel (conv_f16.hip), included once per kernel so that the plain kernels keep the machine code
-// that was measured (as conv_wino_body.inc).  In scope: the template parameters MR, NR, WM, WN, NPM, DB, PRIO, the argument p, and
+// Body of conv_f16_kernel<FORM, ...> (conv_f16.hip; the forms and their constants: the kForms table there), a kernel of its own per form
+// so that each keeps the machine code that was measured (as conv_wino_body.inc).  In scope: the template parameters MR, NR, WM, WN, NPM, DB, PRIO, the argument p, and
 // EPI_MASK (bool constant: the DREAM_CONV_RELUMASK epilogue) and ACT16 (bool constant: activations live in HBM as IEEE half --
 // p.x and an NHWC p.y point to halfs; the patch is copied, not converted: 16-byte pieces of 8 halfs, no input scale) and MASK16
 // (bool constant, read by the epilogue: the ReLU mask of EPI_MASK is a tensor of IEEE halfs) and KSPLIT (bool constant, with ACT16:

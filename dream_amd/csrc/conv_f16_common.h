@@ -109,6 +109,20 @@ Geom16 geom16_convT3_phase(int H, int W, int ph) {
     return g;
 }
 
+// The four phases of the two transposed convs: launch(geometry[, element offset of the phase's block of the packed planes]) for each,
+// stopping at the first launch that fails
+template <class Launch> int for_convT4_phases(int H, int W, int Cin, int CoutPad, Launch launch) {
+    for (int ph = 0; ph < 4; ++ph)
+        if (int rc = launch(geom16_convT4_phase(H, W, ph), (size_t)ph * 4 * CoutPad * Cin)) return rc;
+    return 0;
+}
+
+template <class Launch> int for_convT3_phases(int H, int W, Launch launch) {
+    for (int ph = 0; ph < 4; ++ph)
+        if (int rc = launch(geom16_convT3_phase(H, W, ph))) return rc;
+    return 0;
+}
+
 // tile, patch and tap tables of one launch of variant (BM, NP_MAX) into p (everything but the pointers and B / Cin / Cout / CoutPad)
 void fill_params16(Conv16Params &p, const Geom16 &g, int BM, int np_max, int flags) {
     const bool pool = (flags & DREAM_CONV_POOL2) != 0;

@@ -1,8 +1,8 @@
 // Epilogue of the implicit-GEMM kernels on the fp16 matrix cores, included at the end of conv_f16x3_kernel and conv_f16_kernel (one
 // text, and the split kernel's machine code stays what was measured).  In scope: p, acc[MR][NR], inv, wm, wn, li, lh, b, y0, x0, n0,
 // TW, pool, EPI_MASK and ACT16 (bool constants).  acc * (inv * scale) + shift (+ residual) (ReLU) -> y, or the 2x2 window maximum; publishes
-// max|y|.  EPI_MASK (conv_f16_mask_kernel only): `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it;
-// MASK16 (conv_f16_mask16_kernel): that mask is a tensor of IEEE halfs.
+// max|y|.  The constants are those of a form of conv_f16_kernel (the kForms table of conv_f16.hip; all false / 0 in the split kernel).
+// EPI_MASK: `residual` is a ReLU mask, y = residual > 0 ? value : 0, max|y| taken after it; MASK16: that mask is a tensor of IEEE halfs.
 // ACT16 (the half-storage kernels of conv_f16.hip): an NHWC y is IEEE half -- the same value, saturated to +-65504 and rounded to
 // nearest even (sat_half); max|y| is taken BEFORE the saturation, so the side channel tells a caller that it happened.  The NCHW
 // output (the K-channel belief maps) stays fp32.

@@ -381,14 +381,10 @@ extern "C" int dream_conv_transpose4x4s2_f16x3_nhwc_f32(const float *x, const un
                                                         int Cin, int Cout, int CoutPad, int flags, void *stream) {
     DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2)) == 0,
                   "convT4x4_f16x3: unsupported flags");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT4_phase(H, W, ph);
-        const size_t off = (size_t)ph * 4 * CoutPad * Cin;
-        if (int rc = launch16(x, amax_in, (const _Float16 *)w_hi + off, (const _Float16 *)w_lo + off, w_exp, scale, shift, nullptr,
-                              y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
-            return rc;
-    }
-    return 0;
+    return for_convT4_phases(H, W, Cin, CoutPad, [&](const Geom16 &g, size_t off) {
+        return launch16(x, amax_in, (const _Float16 *)w_hi + off, (const _Float16 *)w_lo + off, w_exp, scale, shift, nullptr, y, amax_out,
+                        B, Cin, Cout, CoutPad, g, flags, stream);
+    });
 }
 
 // ConvTranspose2d(k=3,s=2,p=1,output_padding 1) on the split-precision path: the sub-pixel decomposition of
@@ -398,12 +394,9 @@ extern "C" int dream_conv_transpose3x3s2_f16x3_nhwc_f32(const float *x, const un
                                                         unsigned *amax_out, int B, int H, int W, int Cin, int Cout,
                                                         int CoutPad, int flags, void *stream) {
     DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "convT3x3_f16x3: only the ReLU flag is supported");
-    for (int ph = 0; ph < 4; ++ph) {
-        const Geom16 g = geom16_convT3_phase(H, W, ph);
-        if (int rc = launch16(x, amax_in, w_hi, w_lo, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream))
-            return rc;
-    }
-    return 0;
+    return for_convT3_phases(H, W, [&](const Geom16 &g) {
+        return launch16(x, amax_in, w_hi, w_lo, w_exp, nullptr, bias, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+    });
 }
 
 // k x k (1 | 3) stride-1 conv, same contract as dream_conv2d_nhwc_f32, on the split-precision path.

@@ -142,20 +142,24 @@ extern "C" size_t dream_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin
 
 namespace {
 
-// x16: x is IEEE half (wgrad_f16_x16_kernel), amax_x is not used and the reduce takes a null amax_x (factor 1); dy16 (with x16): dy is
-// IEEE half times 2^e_g (wgrad_f16_x16_dy16_kernel) and amax_dy is the scalar e_g is derived from: the loss gradient's amax
-int launch_wgrad16(const void *x, const unsigned *amax_x, const void *dy, const unsigned *amax_dy, float *dw_packed, float *dbias,
-                   void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad, int flags, void *stream, bool x16,
-                   bool dy16 = false) {
-    DREAM_REQUIRE(x && (amax_x || x16) && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
+// The three forms of the launch: the kernel and which operands it reads as IEEE half.  x16: amax_x is not used, the reduce takes a null
+// amax_x (factor 1); dy16: dy is half times 2^e_g, amax_dy is the scalar e_g is derived from (the loss gradient's amax) by the g16 reduce
+enum WgradForm { kWgradF32, kWgradX16, kWgradX16Dy16 };
+const struct { void (*kernel)(const Wgrad16Params); bool x16, dy16; } kWgradForms[] = {
+    {wgrad_f16_kernel, false, false}, {wgrad_f16_x16_kernel, true, false}, {wgrad_f16_x16_dy16_kernel, true, true}};
+
+int launch_wgrad16(WgradForm form, const void *x, const unsigned *amax_x, const void *dy, const unsigned *amax_dy, float *dw_packed,
+                   float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy, int RowsPad, int flags, void *stream) {
+    const auto &f = kWgradForms[form];
+    DREAM_REQUIRE(x && (amax_x || f.x16) && dy && amax_dy && dw_packed && workspace, "wgrad_f16: null pointer");
     DREAM_REQUIRE(flags == 0, "wgrad_f16: flags %d not supported (plain 3x3 stride-1 convs only)", flags);
     DREAM_REQUIRE(shape_ok(B, H, W, Cin, RowsPad) && Cdy > 0 && Cdy % 4 == 0 && RowsPad >= Cdy,
                   "wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdy %d, pad %d): Cin %% 32, Cdy %% 4, pad %% 64", B, H, W, Cin, Cdy, RowsPad);
     DREAM_REQUIRE((size_t)B * H * W * (size_t)(Cin > Cdy ? Cin : Cdy) < ((size_t)1 << 40), "wgrad_f16: tensor too large");
-    DREAM_REQUIRE(!x16 || ((size_t)x & 15) == 0, "wgrad_f16: a half x must be 16-byte aligned");
-    DREAM_REQUIRE(!dy16 || (x16 && ((size_t)dy & 15) == 0), "wgrad_f16: a half dy goes with a half x and must be 16-byte aligned");
+    DREAM_REQUIRE(!f.x16 || ((size_t)x & 15) == 0, "wgrad_f16: a half x must be 16-byte aligned");
+    DREAM_REQUIRE(!f.dy16 || ((size_t)dy & 15) == 0, "wgrad_f16: a half dy must be 16-byte aligned");
     Wgrad16Params p;
-    p.x = (const float *)x; p.dy = (const float *)dy; p.amax_x = x16 ? nullptr : amax_x; p.amax_dy = amax_dy;
+    p.x = (const float *)x; p.dy = (const float *)dy; p.amax_x = f.x16 ? nullptr : amax_x; p.amax_dy = amax_dy;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Ct = Cdy; p.RowsPad = RowsPad;
     p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
     p.tiles_total = B * p.tiles_x * p.tiles_y;
@@ -164,30 +168,24 @@ int launch_wgrad16(const void *x, const unsigned *amax_x, const void *dy, const 
     p.part = (float *)workspace;
     float *bias_part = p.part + (size_t)p.splitk * 9 * RowsPad * Cin;
     p.bias_part = dbias ? bias_part : nullptr;
-    void (*const kernel)(const Wgrad16Params) = dy16 ? wgrad_f16_x16_dy16_kernel : (x16 ? wgrad_f16_x16_kernel : wgrad_f16_kernel);
-    if (dream_allow_full_lds((const void *)kernel)) return 2;
+    if (dream_allow_full_lds((const void *)f.kernel)) return 2;
     const dim3 grid((unsigned)(p.nrb * p.ncb * ceil_div(p.splitk, 8) * 8));
-    hipLaunchKernelGGL(kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(f.kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, p);
     DREAM_LAUNCH_OK();
+    // the form's reduce kernel over n sums: times 2^-e_g (a half dy), else times 2^-ex * 2^-eg of the amax scalars given (null: 1)
+    const auto reduce = [&](size_t blocks, const float *part, float *out, size_t n, const unsigned *ax, const unsigned *ady) {
+        if (f.dy16)
+            hipLaunchKernelGGL(wgrad_f16_reduce_g16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, part, out, n, p.splitk, amax_dy);
+        else
+            hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, part, out, n, p.splitk, ax, ady);
+    };
     const size_t n = (size_t)9 * RowsPad * Cin;
-    size_t gr = (n / 4 + 255) / 256;
-    if (gr > 2048) gr = 2048;
-    if (dy16)
-        hipLaunchKernelGGL(wgrad_f16_reduce_g16_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part,
-                           dw_packed, n, p.splitk, amax_dy);
-    else
-        hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)stream, (const float *)p.part, dw_packed,
-                           n, p.splitk, p.amax_x, amax_dy);
+    reduce((n / 4 + 255) / 256 > 2048 ? 2048 : (n / 4 + 255) / 256, p.part, dw_packed, n, p.amax_x, amax_dy);
     DREAM_LAUNCH_OK();
     if (dbias) {
-        // bias partials are [splitk][RowsPad] of unscaled sums; only the first Cdy entries are wanted
+        // bias partials are [splitk][RowsPad] of unscaled sums (a half dy's carry 2^e_g as well); only the first Cdy entries are wanted
         float *total = bias_part + (size_t)p.splitk * RowsPad;
-        if (dy16)              // the channel sums of the stored halfs carry 2^e_g as well
-            hipLaunchKernelGGL(wgrad_f16_reduce_g16_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
-                               (size_t)RowsPad, p.splitk, amax_dy);
-        else
-            hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)bias_part, total,
-                               (size_t)RowsPad, p.splitk, (const unsigned *)nullptr, (const unsigned *)nullptr);
+        reduce(1, bias_part, total, (size_t)RowsPad, nullptr, nullptr);
         DREAM_LAUNCH_OK();
         if (dream_copy_words(dbias, total, (size_t)Cdy * sizeof(float), (hipStream_t)stream)) return 2;
     }
@@ -202,7 +200,7 @@ int launch_wgrad16(const void *x, const unsigned *amax_x, const void *dy, const 
 extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dy, const unsigned *amax_dy,
                                                 float *dw_packed, float *dbias, void *workspace, int B, int H, int W, int Cin,
                                                 int Cdy, int RowsPad, int flags, void *stream) {
-    return launch_wgrad16(x, amax_x, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, false);
+    return launch_wgrad16(kWgradF32, x, amax_x, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream);
 }
 
 // The same with x stored as IEEE half (train_activation_storage="fp16"): x [B,H,W,Cin] half, 16-byte aligned, is the operand as it is
@@ -210,7 +208,7 @@ extern "C" int dream_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *
 extern "C" int dream_conv3x3_wgrad_f16_x16_nhwc_f32(const void *x, const float *dy, const unsigned *amax_dy, float *dw_packed,
                                                     float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
                                                     int RowsPad, int flags, void *stream) {
-    return launch_wgrad16(x, nullptr, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, true);
+    return launch_wgrad16(kWgradX16, x, nullptr, dy, amax_dy, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream);
 }
 
 // The same with dy stored as IEEE half as well (train_gradient_storage="fp16"): dy [B,H,W,Cdy] half, 16-byte aligned, holds the gradient
@@ -220,5 +218,5 @@ extern "C" int dream_conv3x3_wgrad_f16_x16_nhwc_f32(const void *x, const float *
 extern "C" int dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32(const void *x, const void *dy, const unsigned *grad_amax, float *dw_packed,
                                                          float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
                                                          int RowsPad, int flags, void *stream) {
-    return launch_wgrad16(x, nullptr, dy, grad_amax, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream, true, true);
+    return launch_wgrad16(kWgradX16Dy16, x, nullptr, dy, grad_amax, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream);
 }

@@ -1337,6 +1337,28 @@ def absmax(x):
     return a
 
 
+def _packed_planes(name, packed16, cin):
+    """(hi, lo, exp) of a packed weight tuple (lo: None on the fp16 path), which must expect an input of ``cin`` channels."""
+    hi, lo, exp, _ = packed16
+    if cin != hi.shape[-1]:
+        raise RuntimeError("%s: input has %d channels, packed weights expect %d" % (name, cin, hi.shape[-1]))
+    return hi, lo, exp
+
+
+def _conv16_out(b, h, w, cout, flags, device, half=False):
+    """-> (y, h, w): the uninitialised output of a stride-1 conv launch on a stored [b,h,w,.] input and the grid the launch is given
+    (the stored size doubled by a fused upsample).  NHWC -- halved by a fused pool --, torch.float16 with ``half``; the NCHW output is
+    float32 always."""
+    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
+        h, w = 2 * h, 2 * w
+    if flags & CONV_POOL2:
+        shape, nhwc = (b, h // 2, w // 2, cout), True
+    else:
+        nhwc = not flags & CONV_OUT_NCHW
+        shape = (b, h, w, cout) if nhwc else (b, cout, h, w)
+    return torch.empty(shape, dtype=torch.float16 if half and nhwc else torch.float32, device=device), h, w
+
+
 def pack_conv_weight_f16x3(w_oihw, mode=0):
     """-> (hi, lo, exp, rows): two fp16 planes [ntaps][rows_pad][cols_pad] of w*2^exp and the device int exp."""
     w = _f32(w_oihw)
@@ -1354,17 +1376,10 @@ def pack_conv_weight_f16x3(w_oihw, mode=0):
 
 def conv2d_f16x3(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, residual=None, flags=0, want_amax=True):
     """Split-precision conv (stride 1): returns (y, amax_out)."""
-    hi, lo, exp, _ = packed16
     x = _f32(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv2d_f16x3: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
-    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
-        h, w = 2 * h, 2 * w
-    shape = (b, cout, h, w) if flags & CONV_OUT_NCHW else (b, h, w, cout)
-    if flags & CONV_POOL2:
-        shape = (b, h // 2, w // 2, cout)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    hi, lo, exp = _packed_planes("conv2d_f16x3", packed16, cin)
+    y, h, w = _conv16_out(b, h, w, cout, flags, x.device)
     amax_out = new_amax(x.device) if want_amax else None
     call("dream_conv2d_f16x3_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(lo), ptr(exp), ptr(scale), ptr(shift),
          ptr(residual), ptr(y), ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
@@ -1373,11 +1388,9 @@ def conv2d_f16x3(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None,
 
 def conv_transpose3x3s2_f16x3(x_nhwc, amax_in, packed16_mode1, cout, bias=None, relu=True):
     """Split-precision ConvTranspose2d(k3,s2,p1,output_padding 1) (+ReLU) by sub-pixel phases -> (y, amax_out)."""
-    hi, lo, exp, _ = packed16_mode1
     x = _f32(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv_transpose3x3s2_f16x3: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, lo, exp = _packed_planes("conv_transpose3x3s2_f16x3", packed16_mode1, cin)
     y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
     amax_out = new_amax(x.device)
     call("dream_conv_transpose3x3s2_f16x3_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(lo), ptr(exp), ptr(bias), ptr(y),
@@ -1453,21 +1466,14 @@ def conv2d_f16(x_nhwc, amax_in, packed16, cout, ksize, scale=None, shift=None, r
     """Half-precision conv (stride 1, fp16 operands, fp32 accumulation): returns (y, amax_out).  ``relu_mask`` (a tensor of the
     output's shape; not with ``residual``): y = relu_mask > 0 ? conv : 0 and amax_out is taken after the mask -- with the mode-1
     packed plane (transposed, flipped taps) the data gradient of a conv behind a ReLU."""
-    hi, _, exp, _ = packed16
     x = _f32(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv2d_f16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv2d_f16", packed16, cin)
     if relu_mask is not None:
         if residual is not None or tuple(relu_mask.shape) != (b, h, w, cout):
             raise RuntimeError("conv2d_f16: relu_mask must have the output's shape %s and excludes a residual" % ((b, h, w, cout),))
         residual, flags = _f32(relu_mask), flags | CONV_RELUMASK
-    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
-        h, w = 2 * h, 2 * w
-    shape = (b, cout, h, w) if flags & CONV_OUT_NCHW else (b, h, w, cout)
-    if flags & CONV_POOL2:
-        shape = (b, h // 2, w // 2, cout)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    y, h, w = _conv16_out(b, h, w, cout, flags, x.device)
     amax_out = new_amax(x.device) if want_amax else None
     call("dream_conv2d_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(residual), ptr(y),
          ptr(amax_out), b, h, w, cin, cout, int(hi.shape[-2]), ksize, 1, flags, stream())
@@ -1479,11 +1485,9 @@ def conv3x3_wgrad_f16_splitk(b, h, w, cin, cdy):
     return int(_hip.lib().dream_conv3x3_wgrad_f16_splitk(b, h, w, cin, round_up(cdy, 64)))
 
 
-def conv3x3_wgrad_f16(x_nhwc, amax_x, dy_nhwc, amax_dy, cout, cin, flags=0):
-    """Weight + bias gradient of a 3x3 stride-1 conv on the fp16 matrix cores (csrc/wgrad_f16.hip): both operands rounded once to
-    fp16(v * 2^e), e from their amax scalars, fp32 accumulation -> (dW OIHW [cout,cin,3,3], dbias [cout]), the contract of
-    conv3x3_wgrad.  dbias is the channel sum of the unrounded dy.  cin % 32 == 0; dy may carry padded channels (>= cout)."""
-    x, dy = _f32(x_nhwc), _f32(dy_nhwc)
+def _wgrad_f16(x, dy, cout, cin, flags, launch):
+    """What the three conv3x3_wgrad_f16* wrappers share: workspace, packed dW and dbias, their ``launch(dwp, dbias, workspace, b, h, w, cin,
+    cdy, rows_pad, flags, stream)`` -- the tail of each entry point's arguments --, the unpacking -> (dW OIHW, dbias [cout])."""
     b, h, w, cdy = (int(v) for v in dy.shape)
     if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
         raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
@@ -1491,20 +1495,26 @@ def conv3x3_wgrad_f16(x_nhwc, amax_x, dy_nhwc, amax_dy, cout, cin, flags=0):
     ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
     dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
     dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
-    call("dream_conv3x3_wgrad_f16_nhwc_f32", ptr(x), ptr(amax_x), ptr(dy), ptr(amax_dy), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin,
-         cdy, rows_pad, flags, stream())
+    launch(ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin, cdy, rows_pad, flags, stream())
     dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
     call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
     return dw, dbias[:cout].contiguous()
 
 
+def conv3x3_wgrad_f16(x_nhwc, amax_x, dy_nhwc, amax_dy, cout, cin, flags=0):
+    """Weight + bias gradient of a 3x3 stride-1 conv on the fp16 matrix cores (csrc/wgrad_f16.hip): both operands rounded once to
+    fp16(v * 2^e), e from their amax scalars, fp32 accumulation -> (dW OIHW [cout,cin,3,3], dbias [cout]), the contract of
+    conv3x3_wgrad.  dbias is the channel sum of the unrounded dy.  cin % 32 == 0; dy may carry padded channels (>= cout)."""
+    x, dy = _f32(x_nhwc), _f32(dy_nhwc)
+    return _wgrad_f16(x, dy, cout, cin, flags, lambda *out_and_shape: call(
+        "dream_conv3x3_wgrad_f16_nhwc_f32", ptr(x), ptr(amax_x), ptr(dy), ptr(amax_dy), *out_and_shape))
+
+
 def conv_transpose3x3s2_f16(x_nhwc, amax_in, packed16_mode1, cout, bias=None, relu=True):
     """Half-precision ConvTranspose2d(k3,s2,p1,output_padding 1) (+ReLU) by sub-pixel phases -> (y, amax_out)."""
-    hi, _, exp, _ = packed16_mode1
     x = _f32(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv_transpose3x3s2_f16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv_transpose3x3s2_f16", packed16_mode1, cin)
     y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
     amax_out = new_amax(x.device)
     call("dream_conv_transpose3x3s2_f16_nhwc_f32", ptr(x), ptr(amax_in), ptr(hi), ptr(exp), ptr(bias), ptr(y), ptr(amax_out),
@@ -1534,19 +1544,10 @@ def _f16(t):
 
 def conv2d_f16_act16(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flags=0, peak=None):
     """conv2d_f16 on half activations (stride 1; no residual, no ReLU mask) -> y: torch.float16 NHWC, float32 with CONV_OUT_NCHW."""
-    hi, _, exp, _ = packed16
     x = _f16(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv2d_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
-    if flags & (CONV_UPSAMPLE2X | CONV_ZEROSTUFF2X):
-        h, w = 2 * h, 2 * w
-    if flags & CONV_POOL2:
-        y = torch.empty((b, h // 2, w // 2, cout), dtype=torch.float16, device=x.device)
-    elif flags & CONV_OUT_NCHW:
-        y = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device)
-    else:
-        y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    hi, _, exp = _packed_planes("conv2d_f16_act16", packed16, cin)
+    y, h, w = _conv16_out(b, h, w, cout, flags, x.device, half=True)
     call("dream_conv2d_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), b, h, w, cin, cout,
          int(hi.shape[-2]), ksize, 1, flags, stream())
     return y
@@ -1567,9 +1568,7 @@ def conv2d_f16_act16_ksplit(x_nhwc, packed16, cout, ksize, scale=None, shift=Non
     s = conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags)
     if s == 1:
         return conv2d_f16_act16(x, packed16, cout, ksize, scale, shift, flags, peak=peak)
-    hi, _, exp, _ = packed16
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv2d_f16_act16_ksplit: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv2d_f16_act16_ksplit", packed16, cin)
     nbytes = int(_hip.lib().dream_conv2d_f16_ksplit_workspace(b, h, w, cout, s))
     if workspace is None:
         workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
@@ -1582,11 +1581,9 @@ def conv2d_f16_act16_ksplit(x_nhwc, packed16, cout, ksize, scale=None, shift=Non
 
 
 def conv_transpose3x3s2_f16_act16(x_nhwc, packed16_mode1, cout, bias=None, relu=True, peak=None):
-    hi, _, exp, _ = packed16_mode1
     x = _f16(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv_transpose3x3s2_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv_transpose3x3s2_f16_act16", packed16_mode1, cin)
     y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
     call("dream_conv_transpose3x3s2_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(bias), ptr(y), ptr(peak), b, h, w, cin, cout,
          int(hi.shape[-2]), CONV_RELU if relu else 0, stream())
@@ -1594,11 +1591,9 @@ def conv_transpose3x3s2_f16_act16(x_nhwc, packed16_mode1, cout, bias=None, relu=
 
 
 def conv_transpose4x4s2_f16_act16(x_nhwc, packed16, cout, scale=None, shift=None, flags=0, peak=None):
-    hi, _, exp, _ = packed16
     x = _f16(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv_transpose4x4s2_f16_act16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv_transpose4x4s2_f16_act16", packed16, cin)
     y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
     call("dream_conv_transpose4x4s2_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), b, h, w, cin,
          cout, int(hi.shape[-2]), flags, stream())
@@ -1637,27 +1632,15 @@ def add_f16(a, b, peak=None):
 def conv3x3_wgrad_f16_x16(x_nhwc, dy_nhwc, amax_dy, cout, cin, flags=0):
     """conv3x3_wgrad_f16 with x a torch.float16 tensor that IS the operand (no amax of x, no scale) -> (dW OIHW, dbias [cout])."""
     x, dy = _f16(x_nhwc), _f32(dy_nhwc)
-    b, h, w, cdy = (int(v) for v in dy.shape)
-    if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
-        raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
-    rows_pad = round_up(cdy, 64)
-    ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
-    dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
-    dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
-    call("dream_conv3x3_wgrad_f16_x16_nhwc_f32", ptr(x), ptr(dy), ptr(amax_dy), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin, cdy, rows_pad,
-         flags, stream())
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-    call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
-    return dw, dbias[:cout].contiguous()
+    return _wgrad_f16(x, dy, cout, cin, flags, lambda *out_and_shape: call(
+        "dream_conv3x3_wgrad_f16_x16_nhwc_f32", ptr(x), ptr(dy), ptr(amax_dy), *out_and_shape))
 
 
 def conv2d_f16_mask16(x_nhwc, amax_in, packed16, cout, ksize, relu_mask, scale=None, shift=None, flags=0, want_amax=True):
     """conv2d_f16(..., relu_mask=) with the mask a torch.float16 tensor of the output's shape -> (y fp32, amax_out after the mask)."""
-    hi, _, exp, _ = packed16
     x, mask = _f32(x_nhwc), _f16(relu_mask)
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("conv2d_f16_mask16: input has %d channels, packed weights expect %d" % (cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes("conv2d_f16_mask16", packed16, cin)
     if tuple(mask.shape) != (b, h, w, cout):
         raise RuntimeError("conv2d_f16_mask16: relu_mask must have the output's shape %s" % ((b, h, w, cout),))
     y = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
@@ -1689,10 +1672,8 @@ def widen_f16(x):
 # A stored gradient is half(clamp(g * 2^e_g, +-65504)), e_g = 9 - exponent(*grad_amax): ONE device scalar per backward pass (absmax of
 # the loss gradient) that every launch derives the exponent from.  ``peak`` as above.
 def _g16_conv_shapes(name, x, packed16, cout, relu_mask):
-    hi, _, exp, _ = packed16
     b, h, w, cin = (int(v) for v in x.shape)
-    if cin != hi.shape[-1]:
-        raise RuntimeError("%s: input has %d channels, packed weights expect %d" % (name, cin, hi.shape[-1]))
+    hi, _, exp = _packed_planes(name, packed16, cin)
     mask = None if relu_mask is None else _f16(relu_mask)
     if mask is not None and tuple(mask.shape) != (b, h, w, cout):
         raise RuntimeError("%s: relu_mask must have the output's shape %s" % (name, (b, h, w, cout)))
@@ -1736,18 +1717,8 @@ def conv3x3_wgrad_f16_x16_dy16(x_nhwc, dy_nhwc, grad_amax, cout, cin, flags=0):
     """conv3x3_wgrad_f16_x16 with dy a torch.float16 tensor that holds the gradient times 2^e_g and IS the operand
     -> (dW OIHW, dbias [cout]), both times 2^-e_g."""
     x, dy = _f16(x_nhwc), _f16(dy_nhwc)
-    b, h, w, cdy = (int(v) for v in dy.shape)
-    if int(x.shape[3]) != cin or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
-        raise RuntimeError("wgrad_f16: x %s does not go with dy %s and %d input channels" % (tuple(x.shape), tuple(dy.shape), cin))
-    rows_pad = round_up(cdy, 64)
-    ws = _workspace(_hip.lib().dream_conv3x3_wgrad_f16_workspace(b, h, w, cin, rows_pad), x.device)
-    dwp = torch.empty((9, rows_pad, cin), dtype=torch.float32, device=x.device)
-    dbias = torch.empty((cdy,), dtype=torch.float32, device=x.device)
-    call("dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32", ptr(x), ptr(dy), ptr(grad_amax), ptr(dwp), ptr(dbias), ptr(ws), b, h, w, cin, cdy,
-         rows_pad, flags, stream())
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-    call("dream_unpack_conv3x3_weight", ptr(dwp), ptr(dw), cout, cin, rows_pad, cin, stream())
-    return dw, dbias[:cout].contiguous()
+    return _wgrad_f16(x, dy, cout, cin, flags, lambda *out_and_shape: call(
+        "dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32", ptr(x), ptr(dy), ptr(grad_amax), *out_and_shape))
 
 
 def maxpool2_bwd_x16_dy16(dy, x, relu=False):

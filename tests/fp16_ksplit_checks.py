@@ -109,6 +109,17 @@ def check_case(dev, case, k):
         check_conv(dev, B, H, W, Cin, Cout, k, 1000, seed=6)                                     # (clamped to the stages)
 
 
+def check_tile(dev, variant):
+    """The split kernel of tile ``variant`` of the fp16 variant table, forced, on the smallest launch case: 3x3 in two uneven slices,
+    1x1 in as many slices as stages."""
+    assert _hip.lib().dream_conv_f16_set_variant(variant) == 0
+    try:
+        check_conv(dev, *LAUNCH_CASES[0], 3, 2, seed=variant)
+        check_conv(dev, *LAUNCH_CASES[0], 1, 3, seed=variant)
+    finally:
+        _hip.lib().dream_conv_f16_set_variant(-1)
+
+
 def check_saturation(dev, case, k):
     B, H, W, Cin, Cout = case
     check_conv(dev, B, H, W, Cin, Cout, k, 2, x_scale=100.0, w_scale=30.0, saturate=True)

@@ -41,6 +41,11 @@ def test_split_launches_on_the_tiles_of_the_deep_layers(variant):
         lib.dream_conv_f16_set_variant(-1)
 
 
+@pytest.mark.parametrize("variant", range(8))
+def test_split_launches_on_every_tile(variant):
+    kc.check_tile(DEV, variant)
+
+
 @pytest.mark.parametrize("ksize", [1, 3])
 @pytest.mark.parametrize("case", kc.LAUNCH_CASES, ids=lambda c: "x".join(str(v) for v in c))
 def test_saturation_is_finite_and_reported(case, ksize):
