@@ -72,6 +72,17 @@ _SIGNATURES = {
     "dream_conv3x3_winograd_bwd_bnmask_nhwc_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dream_conv1x1_bwd_bnmask_nhwc_f32": (_I, [_P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dream_conv1x1_wgrad_pre_nhwc_f32": (_I, [_P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P]),
+    "dream_conv1x1_weight_halfs": (_SZ, [_I, _I]),
+    "dream_conv1x1_f16_set_ksplit": (_I, [_I]),
+    "dream_pack_conv1x1_weight_f16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "dream_pack16_job_bytes": (_SZ, []),
+    "dream_pack_conv1x1_weights_f16_batched": (_I, [_P, _I, _P, _I, _P]),
+    "dream_conv1x1_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _c.c_long, _I, _I, _I, _P]),
+    "dream_conv1x1_bnstats_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "dream_conv1x1_bwd_bnmask_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dream_conv1x1_wgrad_f16_workspace": (_SZ, [_c.c_long, _I, _I]),
+    "dream_conv1x1_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P]),
+    "dream_bn_bwd_apply_amax_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _P]),
     "dream_maxpool3s2_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

@@ -388,6 +388,41 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_mask_kernel(const f32x4 *z, 
     }
 }
 
+// The same pass, publishing max|dz| (train_gemm_precision="fp16" of ResnetSimple: the per-tensor scale of the gradient operand that the 1x1
+// data- / weight-gradient GEMMs of gemm1x1_f16.hip round to half).  A kernel of its own -- the body above is repeated, not templated --
+// so that bn_bwd_apply_mask_kernel stays instruction-identical (tools/isa_same.py).  Same expressions in the same order: dz is bit-equal.
+__global__ void __launch_bounds__(256) bn_bwd_apply_mask_amax_kernel(const f32x4 *z, const f32x4 *dy, const f32x4 *y_act, const float *ab,
+                                                                     const f32x4 *mean, const f32x4 *invstd, const f32x4 *gamma,
+                                                                     const f32x4 *dgamma, const f32x4 *dbeta, f32x4 *dz, f32x4 *g_out,
+                                                                     size_t n4, int C4, float inv_n, int mask, unsigned *amax) {
+    const f32x4 *a4 = (const f32x4 *)ab, *b4 = (const f32x4 *)(ab + 4 * (size_t)C4);
+    float m = 0.0f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        const f32x4 v = z[i], mu = mean[c], is = invstd[c], ga = gamma[c], dg = dgamma[c], db = dbeta[c];
+        f32x4 g = dy[i];
+        if (mask == 1) {
+            const f32x4 ya = y_act[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = ya[k] > 0.0f ? g[k] : 0.0f;
+        } else if (mask == 2) {
+            const f32x4 a = a4[c], b = b4[c];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = __builtin_fmaf(a[k], v[k], b[k]) > 0.0f ? g[k] : 0.0f;
+        }
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float xh = (v[k] - mu[k]) * is[k];
+            o[k] = ga[k] * is[k] * (g[k] - db[k] * inv_n - xh * dg[k] * inv_n);
+            m = fmaxf(m, fabsf(o[k]));
+        }
+        dz[i] = o;
+        if (g_out) g_out[i] = g;
+    }
+    publish_amax(amax, m);             // (every lane arrives: the loop above is the only divergence)
+}
+
 }  // namespace
 
 extern "C" size_t dream_bn_workspace(int C) { return (size_t)kStatBlocks * C * 2 * sizeof(double) + (size_t)C * sizeof(float); }
@@ -531,6 +566,24 @@ extern "C" int dream_bn_bwd_apply_nhwc_f32(const float *z, const float *dy, cons
                        (const f32x4 *)dy, (const f32x4 *)y_act, ab ? ab : gamma, (const f32x4 *)save_mean, (const f32x4 *)save_invstd,
                        (const f32x4 *)gamma, (const f32x4 *)dgamma, (const f32x4 *)dbeta, (f32x4 *)dz, (f32x4 *)g_out, n4, C / 4,
                        (float)(1.0 / (double)npix), mask);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+
+// dream_bn_bwd_apply_nhwc_f32 that also publishes max|dz| into *amax_out (the bit pattern of a non-negative float; zeroed here by the
+// library's fill kernel, then raised by atomicMax): dz and g_out are bit-equal to the plain entry point's
+extern "C" int dream_bn_bwd_apply_amax_nhwc_f32(const float *z, const float *dy, const float *y_act, const float *ab, const float *gamma,
+                                                const float *save_mean, const float *save_invstd, const float *dgamma, const float *dbeta,
+                                                float *dz, float *g_out, unsigned *amax_out, size_t npix, int C, int mask, void *stream) {
+    DREAM_REQUIRE(z && dy && gamma && save_mean && save_invstd && dgamma && dbeta && dz && amax_out, "bn_bwd_apply_amax: null pointer");
+    DREAM_REQUIRE(mask == 0 || (mask == 1 && y_act) || (mask == 2 && ab), "bn_bwd_apply_amax: mask %d without its source", mask);
+    DREAM_REQUIRE(C > 0 && C % 4 == 0 && npix > 0, "bn_bwd_apply_amax: unsupported C=%d", C);
+    if (dream_zero_words(amax_out, sizeof(unsigned), (hipStream_t)stream)) return 2;
+    const size_t n4 = npix * (size_t)(C / 4);
+    hipLaunchKernelGGL(bn_bwd_apply_mask_amax_kernel, dim3(stream_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)z,
+                       (const f32x4 *)dy, (const f32x4 *)y_act, ab ? ab : gamma, (const f32x4 *)save_mean, (const f32x4 *)save_invstd,
+                       (const f32x4 *)gamma, (const f32x4 *)dgamma, (const f32x4 *)dbeta, (f32x4 *)dz, (f32x4 *)g_out, n4, C / 4,
+                       (float)(1.0 / (double)npix), mask, amax_out);
     DREAM_LAUNCH_OK();
     return 0;
 }

@@ -115,7 +115,8 @@ def reset_weight_caches(module):
             m._cache = {}
         if m.__dict__.get("_pack_pending") is not None:
             m._pack_join()                                  # a re-pack on the second stream still writes into the old copies
-        for name in ("_pack_state", "_pack_records", "_pack_pending"):       # ResnetSimple._repack_weights: its graph writes into the old copies
+        # ResnetSimple._repack_weights / _repack_half_weights: their tables write into the old copies
+        for name in ("_pack_state", "_pack_records", "_pack_pending", "_pack16_state", "_half_sources"):
             m.__dict__.pop(name, None)
 
 
@@ -430,7 +431,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_activation_storage",
+            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_gemm_precision", "train_activation_storage",
                          "train_gradient_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))
@@ -795,10 +796,11 @@ class DreamDataParallel(nn.Module):
         if args or kwargs:
             return self.module(x, *args, **kwargs)
         one = self.n_devices(x.shape[0]) == 1
-        if (one and self.single_device_graphs and self.module.training and torch.is_grad_enabled()
-                and getattr(self.module, "train_precision", "fp32") != "fp32"):
-            raise ValueError("dream_amd: hip_graph_train (DREAM_TRAIN_GRAPH=1) does not replay train_precision=%r steps; switch one of "
-                             "them off" % (self.module.train_precision,))
+        if one and self.single_device_graphs and self.module.training and torch.is_grad_enabled():
+            for name in ("train_precision", "train_gemm_precision"):
+                if getattr(self.module, name, "fp32") != "fp32":
+                    raise ValueError("dream_amd: hip_graph_train (DREAM_TRAIN_GRAPH=1) does not replay %s=%r steps; switch one of "
+                                     "them off" % (name, getattr(self.module, name)))
         if one and not (self.single_device_graphs and self.module.training and torch.is_grad_enabled()):
             return self.module(x)
         params = self.module.dp_parameters()

@@ -1464,7 +1464,8 @@ class ResnetSimple(nn.Module):
         self.imagenet_initialised = _pretrained.init_resnet101_trunk(self) if pretrained else False
 
     _FP32_ACTIVATIONS = "ResnetSimple stores its activations in fp32 only"
-    train_precision = _FixedSwitch("fp32", "ResnetSimple trains in fp32 only", "BatchNorm training on the fp16 matrix cores is not built")
+    # (the hourglass's switch: its plain 3x3 convs.  ResnetSimple's half-precision training is a switch of its own, train_gemm_precision)
+    train_precision = _FixedSwitch("fp32", "ResnetSimple trains in fp32 only", "its half-precision training covers the fused 1x1 GEMMs: train_gemm_precision")
     activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS,
                                       "the stride-2 trunk convs, the 3x3 max-pool and the 4x4 transposed convs read and write fp32")
     conv_ksplit = _FixedSwitch("off", "ResnetSimple does not split its convs", "its convs read and write fp32")
@@ -1474,6 +1475,12 @@ class ResnetSimple(nn.Module):
     def _read_switches(self):
         """The host-side switches: defaults from the environment; bench.py, the tools and the tests also set the attributes on an instance."""
         self.precision = "fp32"        # "fp16x3" / "fp16": evaluation-mode forward on the split- / half-precision conv kernel
+        # Training: "fp16" = the 1x1 convs that run on the GEMM kernel with their BatchNorm fused (_half_unit: conv1 / conv3 / the downsample
+        # convs of the Bottlenecks and the patch-row form of layer4.0.conv2) multiply on the fp16 matrix cores -- forward, data gradient and
+        # weight gradient (csrc/gemm1x1_f16.hip; DESIGN.md 4.8j).  Tensors, BatchNorm statistics and the optimizer stay fp32; needs
+        # bn_fusion and conv1x1_algorithm="gemm".  Read once per forward pass (_resolve_train_gemm_precision).  Not spelled ``train_precision``:
+        # that name is DreamHourglass's switch (its plain 3x3 convs), which this class exposes as fixed to "fp32" and keeps refusing.
+        self.train_gemm_precision = "fp32"
         self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
         # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
         self.conv1x1_algorithm = os.environ.get("DREAM_CONV1X1_ALGORITHM", "gemm")
@@ -1689,6 +1696,76 @@ class ResnetSimple(nn.Module):
             cout, cin = cin, cout
         return self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and cin == int(x.shape[3]) and ops.conv1x1_applies(x, cout)
 
+    def _g16(self, name, conv, mode, col3=False):
+        """_g for the fp16 GEMM -> (halfs, e_w, rows): keys "g0f16" / "g1f16"."""
+        def build():
+            w = conv.weight.detach()
+            if col3:
+                w = w.permute(0, 2, 3, 1).reshape(int(w.shape[0]), -1, 1, 1).contiguous()
+            return ops.pack_conv1x1_weight_f16(w, mode)
+        key = ("g%df16" % mode, name)
+        if not col3:                                 # packed from the parameter itself: batchable (_repack_half_weights)
+            self.__dict__.setdefault("_half_sources", {})[key] = (conv.weight, mode)
+        return self._cached(key, [conv.weight], build)
+
+    def _repack_half_weights(self):
+        """train_gemm_precision="fp16": the half copies that earlier steps built from a parameter itself (_g16; not the patch-row forms) are
+        rewritten in place by ONE batched pack at the start of the step (three launches) and their cache entries stamped with the
+        parameters' new versions -- packed one by one, three launches per copy, they cost a 16-frame step more than the fp16 GEMMs save
+        (profiles/microbench_resnet_train_precision.txt).  Skipped on the first step (nothing is cached yet), off the GPU and during a
+        hipGraph capture; what the table does not hold stays lazy."""
+        first = next(self.parameters())
+        if not first.is_cuda or torch.cuda.is_current_stream_capturing():
+            return
+        live = {key: src for key, src in self.__dict__.get("_half_sources", {}).items() if key in self._cache}
+        if not live:
+            return
+        stamp = tuple((key, self._cache[key][1][0].data_ptr(), self._cache[key][1][1].data_ptr(), src[0].data_ptr()) for key, src in live.items())
+        st = self.__dict__.get("_pack16_state")
+        if st is None or st["stamp"] != stamp:
+            entries = [(w.detach(), self._cache[key][1], mode) for key, (w, mode) in live.items()]
+            table, scratch = ops.pack16_job_table(entries, first.device)
+            st = dict(stamp=stamp, table=table, scratch=scratch)
+            object.__setattr__(self, "_pack16_state", st)
+        tags = {key: ((w._version, w.data_ptr()),) for key, (w, _) in live.items()}
+        if any(self._cache[key][0] != tag for key, tag in tags.items()):
+            ops.pack_conv1x1_weights_f16_batched(st["table"], st["scratch"])
+            for key, tag in tags.items():
+                self._cache[key] = (tag, self._cache[key][1])
+
+    def _resolve_train_gemm_precision(self, training):
+        """Reads ``train_gemm_precision`` once for this pass -> do the covered units of a training pass run in half precision?  ValueError
+        for an unknown value (both passes) and, in a training pass, for "fp16" without the switches its units are built on."""
+        tp = self.train_gemm_precision
+        if tp not in ("fp32", "fp16"):
+            raise ValueError("unknown train_gemm_precision %r (\"fp32\" or \"fp16\")" % (tp,))
+        half = training and tp == "fp16"
+        if half and not (self.bn_fusion and self.conv1x1_algorithm == "gemm"):
+            raise ValueError("train_gemm_precision=\"fp16\" needs bn_fusion and conv1x1_algorithm=\"gemm\" (they are %r and %r)"
+                             % (self.bn_fusion, self.conv1x1_algorithm))
+        self._train16 = half
+        return half
+
+    @staticmethod
+    def _half_unit(rec):
+        """The rule of train_gemm_precision="fp16", one for the forward pass, the data gradient and the weight gradient, read from what was
+        recorded when the unit was taped: a "conv" record with bn_fusion on whose forward ran on the 1x1 GEMM kernel (stride-1 1x1, the
+        ``sub2`` downsample form, the ``col3`` patch-row form) in a pass that resolved train_gemm_precision="fp16".  Everything else -- stem,
+        Winograd and direct convs, transposed convs (their small-map GEMM form included), head, pool -- is fp32 launch for launch."""
+        return rec["kind"] == "conv" and rec.get("f16", False)
+
+    def _amax(self, device):
+        """One zero-initialised amax word per covered unit and step (ops.bn_bwd_apply_amax zeroes it again before it publishes), from a
+        persistent pool beside the ticket words (_ctr); the cursor restarts with every forward pass."""
+        buf = self._cache.get(("amaxpool",))
+        if buf is None or buf.device != device:
+            buf = self._cache[("amaxpool",)] = torch.zeros((1024,), dtype=torch.int32, device=device)
+            self._amax_pos = 0
+        if self._amax_pos >= buf.numel():
+            self._amax_pos = 0
+        self._amax_pos += 1
+        return buf[self._amax_pos - 1:self._amax_pos]
+
     def _conv_bn(self, name, x, conv, bn, relu, residual=None):
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         scale, shift = self._fold(name, bn, conv.bias)
@@ -1784,6 +1861,7 @@ class ResnetSimple(nn.Module):
     def run_forward(self, x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
+        self._resolve_train_gemm_precision(False)
         if self.precision in _HALF_OPS:
             return self.run_forward_half(x, _HALF_OPS[self.precision])
         # stem: 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused; then MaxPool(3,2,1)
@@ -1879,13 +1957,19 @@ class ResnetSimple(nn.Module):
                 col3 = (int(x.shape[1]), int(x.shape[2]))
                 x, k, stride = ops.im2col3s2(x), 1, 1
         rec = dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, src=src, pre=pre, k=k, stride=stride,
-                   has_res=residual is not None, y=None, ab=None, sub2=sub2, col3=col3, wino=self._wino_train(conv))
+                   has_res=residual is not None, y=None, ab=None, sub2=sub2, col3=col3, wino=self._wino_train(conv), f16=False)
         if col3 is not None or self._gemm1x1(conv, x, k, stride):
-            packed, rows = self._g(name, conv, 0, col3 is not None)
-            if fused:
+            rec["f16"] = fused and self.__dict__.get("_train16", False)
+            if self._half_unit(rec):
+                p16 = self._g16(name, conv, 0, col3 is not None)
+                rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn_f16(
+                    x, p16, p16[2], bn, self._ctr(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
+            elif fused:
+                packed, rows = self._g(name, conv, 0, col3 is not None)
                 rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn(
                     x, packed, rows, bn, self._ctr(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
             else:
+                packed, rows = self._g(name, conv, 0, col3 is not None)
                 rec["z"] = ops.conv1x1(x, packed, rows, None, bias, None, 0)
         else:
             assert not pre
@@ -1921,9 +2005,13 @@ class ResnetSimple(nn.Module):
     def run_forward_train(self, x):
         """-> (belief maps NCHW, tape)."""
         fused = self.bn_fusion
+        half = self._resolve_train_gemm_precision(True)
         self._repack_weights(split=fused)
+        if half:
+            self._repack_half_weights()
         if fused:
             self._ctr_pos = 0
+            self._amax_pos = 0
         tape = []
         ho, wo = (int(x.shape[2]) + 6 - 7) // 2 + 1, (int(x.shape[3]) + 6 - 7) // 2 + 1
         stem = dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, has_res=False, y=None, ab=None, k=1, stride=1,
@@ -2032,6 +2120,11 @@ class ResnetSimple(nn.Module):
         form, tile = form or self._dgrad_form(rec, dz, joins=residual is not None)
         name, conv, p = rec["name"], rec["conv"], rec["src"]
         cin = int(conv.weight.shape[1])
+        half = self._half_unit(rec)               # (then dz is the tensor _unit_bwd wrote for this record, its amax in rec["dz_amax"])
+        if form == "gemm_mask" and half:
+            return ("masked",) + ops.conv1x1_bwd_bnmask_f16(dz, rec["dz_amax"], self._g16(name, conv, 1), cin, p["z"],
+                                                            None if p["has_res"] else p["ab"], p["mean"], p["invstd"],
+                                                            self._ctr(dz.device), y_act=p["y"], residual=residual)
         if form == "gemm_mask":
             # the head's is the same form on another packed operand: the contraction is its keypoint channels, zero-padded (dz: _bwd_final).
             # The mask: the stored activation where the forward pass wrote one, else recomputed from (z, ab) -- which a residual rules out.
@@ -2047,9 +2140,15 @@ class ResnetSimple(nn.Module):
             return ops.conv3x3_winograd_tile(tile, dz, u_t, rows, None, None, residual, 0)
         if form == "col3":
             # the GEMM's data gradient is the gradient of the patch rows, summed back onto the map
+            if half:
+                p16 = self._g16(name, conv, 1, col3=True)
+                return ops.col2im3s2(ops.conv1x1_f16(dz, rec["dz_amax"], p16, p16[2]), *rec["col3"])
             packed_t, rows = self._g(name, conv, 1, col3=True)
             return ops.col2im3s2(ops.conv1x1(dz, packed_t, rows, None, None, None, 0), *rec["col3"])
-        if form == "gemm":
+        if form == "gemm" and half:
+            p16 = self._g16(name, conv, 1)
+            g = ops.conv1x1_f16(dz, rec["dz_amax"], p16, p16[2], residual=residual)
+        elif form == "gemm":
             packed_t, rows = self._g(name, conv, 1)
             g = ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
         else:
@@ -2085,6 +2184,8 @@ class ResnetSimple(nn.Module):
         kind, conv, x, grads = rec["kind"], rec["conv"], rec["x"], bw["grads"]
         pre_ab = inputs[2] if len(inputs) > 2 else None
         cout, kin = int(conv.weight.shape[0]), int(x.shape[3])
+        # (a covered unit's weight gradient stays on the fp32 kernel where the fp16 one measured slower: ops.conv1x1_wgrad_f16_pays)
+        half_amax = rec["dz_amax"] if self._half_unit(rec) and ops.conv1x1_wgrad_f16_pays(kin, cout) else None
 
         def leaf():
             db = None
@@ -2092,6 +2193,8 @@ class ResnetSimple(nn.Module):
                 dw, db = ops.convT4x4_wgrad_winograd(x, dz)
             elif form == "convT":
                 dw = ops.convT4x4_wgrad(x, dz)
+            elif form == "gemm" and half_amax is not None:
+                dw = ops.conv1x1_wgrad_f16(x, dz, half_amax, ops.round_up(cout, 4), kin, pre_ab=pre_ab)
             elif form == "gemm":              # the GEMM over positions, of the conv as it RAN: 1x1, im2col rows (stem), patch rows (col3)
                 dw = ops.conv1x1_wgrad(x, dz, ops.round_up(cout, 4), kin, pre_ab=pre_ab)
             elif form == "winograd":
@@ -2122,16 +2225,23 @@ class ResnetSimple(nn.Module):
         comes from the stored activation where the forward pass wrote one, else it is recomputed from (z, ab).  ``dy`` = ("masked", g,
         dgamma, dbeta): the consumer's data-gradient epilogue already masked and summed (_dgrad) -- one launch."""
         bn, z, g = rec["bn"], rec["z"], None
+        # a covered unit (train_gemm_precision="fp16"): the same apply pass also publishes max|dz|, the scale of the gradient operand that this
+        # record's data- and weight-gradient GEMMs round to half (no absmax pass)
+        if self._half_unit(rec):
+            amax = rec["dz_amax"] = self._amax(z.device)
+            apply = lambda *a, **kw: ops.bn_bwd_apply_amax(*a, amax, **kw)      # noqa: E731
+        else:
+            apply = ops.bn_bwd_apply
         if rec["ab"] is None:
             dz, g, dgam, dbet = ops.bn_train_bwd(z, dy, rec["y"], bn.weight, rec["mean"], rec["invstd"], rec["relu"], want_g=rec["has_res"])
         elif isinstance(dy, tuple):
             _, g, dgam, dbet = dy
-            dz, _ = ops.bn_bwd_apply(z, g, bn.weight, rec["mean"], rec["invstd"], dgam, dbet)
+            dz, _ = apply(z, g, bn.weight, rec["mean"], rec["invstd"], dgam, dbet)
         else:
             y_act = rec["y"] if rec["relu"] else None
             ab = rec["ab"] if (rec["relu"] and y_act is None) else None
             dgam, dbet = ops.bn_bwd_stats(z, dy, rec["mean"], rec["invstd"], self._ctr(z.device), y_act=y_act, ab=ab)
-            dz, g = ops.bn_bwd_apply(z, dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=rec["has_res"])
+            dz, g = apply(z, dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=rec["has_res"])
         bw["grads"][bn.weight], bw["grads"][bn.bias] = dgam, dbet
         self._wgrad(rec, dz, bw)
         return dz, g

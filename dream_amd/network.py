@@ -243,9 +243,10 @@ class DreamNetwork:
                 raise RuntimeError("dream_amd: hip_graph_train needs the model behind DreamDataParallel (what DreamNetwork builds); this "
                                    "network's model is a %s" % type(self.model).__name__)
             return
-        if on and getattr(self.model.module, "train_precision", "fp32") != "fp32":
-            raise ValueError("dream_amd: hip_graph_train does not replay train_precision=%r steps; switch one of them off"
-                             % (self.model.module.train_precision,))
+        for name in ("train_precision", "train_gemm_precision"):
+            if on and getattr(self.model.module, name, "fp32") != "fp32":
+                raise ValueError("dream_amd: hip_graph_train does not replay %s=%r steps; switch one of them off"
+                                 % (name, getattr(self.model.module, name)))
         self.model.single_device_graphs = bool(on)
 
     # ---- small getters (network.py:319-326) ------------------------------------------------------------

@@ -824,6 +824,123 @@ def conv1x1_wgrad(x_nhwc, dy_nhwc, cout, cin, pre_ab=None):
     return dw
 
 
+# ---- ResnetSimple train_gemm_precision="fp16": the same GEMMs on the fp16 matrix cores (csrc/gemm1x1_f16.hip) ------------------------------
+def pack_conv1x1_weight_f16(w_oihw, mode=0):
+    """[Cout,Cin,1,1] -> (halfs of w * 2^e_w in the fp16 GEMM's layout, e_w: device int, rows); mode as pack_conv1x1_weight."""
+    w = _f32(w_oihw)
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    rows, k = (cout, cin) if mode == 0 else (cin, cout)
+    packed = torch.empty(int(_hip.lib().dream_conv1x1_weight_halfs(rows, k)), dtype=torch.float16, device=w.device)
+    exp = torch.zeros((1,), dtype=torch.int32, device=w.device)
+    scratch = torch.zeros((1,), dtype=torch.int32, device=w.device)
+    call("dream_pack_conv1x1_weight_f16", ptr(w), ptr(packed), ptr(exp), ptr(scratch), cout, cin, mode, stream())
+    return packed, exp, rows
+
+
+def pack16_job_table(entries, device):
+    """Device-resident dream_pack16_job table for pack_conv1x1_weights_f16_batched -> (table, scratch words).  ``entries``:
+    (weight [Cout,Cin,1,1], (halfs, e_w, rows) as pack_conv1x1_weight_f16 returned it, mode)."""
+    import numpy as np
+    dt = np.dtype([("src", np.uint64), ("dst", np.uint64), ("exp", np.uint64), ("scratch", np.uint64), ("cout", np.int32),
+                   ("cin", np.int32), ("mode", np.int32), ("reserved", np.int32)])
+    if int(_hip.lib().dream_pack16_job_bytes()) != dt.itemsize:
+        raise RuntimeError("dream_pack16_job layout mismatch")
+    scratch = torch.zeros((len(entries),), dtype=torch.int32, device=device)
+    arr = np.zeros(len(entries), dt)
+    for i, (w, packed16, mode) in enumerate(entries):
+        arr[i] = (ptr(w), ptr(packed16[0]), ptr(packed16[1]), ptr(scratch[i:i + 1]), int(w.shape[0]), int(w.shape[1]), mode, 0)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device), scratch
+
+
+def pack_conv1x1_weights_f16_batched(table, scratch, workgroups_per_job=16):
+    call("dream_pack_conv1x1_weights_f16_batched", ptr(table), int(scratch.numel()), ptr(scratch), int(workgroups_per_job), stream())
+
+
+def conv1x1_f16(x_nhwc, amax_x, packed16, cout, shift=None, residual=None):
+    """conv1x1 (no scale, no ReLU) with both operands rounded to half while they are loaded; ``amax_x``: the scalar of a gradient
+    operand (bn_bwd_apply_amax), None for an activation."""
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    y = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
+    if residual is not None and tuple(residual.shape) != tuple(y.shape):
+        raise RuntimeError("conv1x1_f16: residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    call("dream_conv1x1_f16_nhwc_f32", ptr(x), ptr(amax_x), ptr(packed16[0]), ptr(packed16[1]), ptr(shift), ptr(residual), ptr(y),
+         b * h * w, cin, cout, cin, stream())
+    return y
+
+
+def conv1x1_bn_f16(x_nhwc, packed16, cout, bn, counters, pre_ab=None, shift=None):
+    """conv1x1_bn on the fp16 matrix cores -> (z, ab, save_mean, save_invstd)."""
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    m = b * h * w
+    z = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
+    ab, mean, invstd = _bn_outputs(cout, x.device)
+    ws = _workspace(_hip.lib().dream_conv1x1_bn_workspace(m, cout), x.device)
+    ctr = _ctr_words(counters, _hip.lib().dream_conv1x1_bn_counters(m, cout))
+    _bn_debug_begin(ab, mean, invstd)
+    call("dream_conv1x1_bnstats_f16_nhwc_f32", ptr(x), ptr(packed16[0]), ptr(packed16[1]), ptr(shift), ptr(pre_ab), ptr(z), m, cin, cout,
+         cin, *_bn_args(bn), ptr(ab), ptr(mean), ptr(invstd), ptr(ws), ptr(ctr), stream())
+    _bn_debug_end("conv1x1_bn_f16", ctr, ab, mean, invstd)
+    _bn_bump(bn)
+    return z, ab, mean, invstd
+
+
+def conv1x1_bwd_bnmask_f16(dy_nhwc, amax_dy, packed16_t, cin, z_nhwc, ab, mean, invstd, counters, y_act=None, residual=None):
+    """conv1x1_bwd_bnmask on the fp16 matrix cores -> (g, dgamma, dbeta); ``amax_dy``: the scalar published with dy."""
+    dy = _f32(dy_nhwc)
+    b, h, w, k = (int(v) for v in dy.shape)
+    m = b * h * w
+    if tuple(z_nhwc.shape) != (b, h, w, cin):
+        raise RuntimeError("conv1x1_bwd_bnmask_f16: z shape %s != %s" % (tuple(z_nhwc.shape), (b, h, w, cin)))
+    g = torch.empty((b, h, w, cin), dtype=torch.float32, device=dy.device)
+    dgamma = torch.empty((cin,), dtype=torch.float32, device=dy.device)
+    dbeta = torch.empty_like(dgamma)
+    ws = _workspace(_hip.lib().dream_conv1x1_bn_workspace(m, cin), dy.device)
+    ctr = _ctr_words(counters, _hip.lib().dream_conv1x1_bn_counters(m, cin))
+    if residual is not None and tuple(residual.shape) != tuple(g.shape):
+        raise RuntimeError("conv1x1_bwd_bnmask_f16: residual shape %s != %s" % (tuple(residual.shape), tuple(g.shape)))
+    _bn_debug_begin(dgamma, dbeta)
+    call("dream_conv1x1_bwd_bnmask_f16_nhwc_f32", ptr(dy), ptr(amax_dy), ptr(packed16_t[0]), ptr(packed16_t[1]), ptr(residual), ptr(g), m, k,
+         cin, k, ptr(_f32(z_nhwc)), None if y_act is not None else ptr(ab), ptr(y_act), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta),
+         ptr(ws), ptr(ctr), stream())
+    _bn_debug_end("conv1x1_bwd_bnmask_f16", ctr, dgamma, dbeta)
+    return g, dgamma, dbeta
+
+
+def conv1x1_wgrad_f16_workspace(m, cin, cout):
+    return int(_hip.lib().dream_conv1x1_wgrad_f16_workspace(m, cin, cout))
+
+
+def conv1x1_wgrad_f16_pays(cin, cout):
+    """Measured (profiles/microbench_resnet_train_precision.txt, the 16-frame step's shapes): with 64 x 256 channel pairs -- layer1,
+    160 000 positions -- the fp16 weight gradient LOSES to the fp32 kernel (0.095 against 0.063-0.075 ms: two 64 x 64 tiles per
+    8-byte load pair leave it bound by load issue); from 256 x 128 pairs on it wins (1.1x - 1.8x).  Such a unit keeps the fp32 launch."""
+    return cin * cout >= 32768
+
+
+def conv1x1_wgrad_f16(x_nhwc, dy_nhwc, amax_dy, cout, cin, pre_ab=None):
+    """conv1x1_wgrad on the fp16 matrix cores -> dW [cout, cin, 1, 1]; ``amax_dy``: the scalar published with dy."""
+    x, dy = _f32(x_nhwc), _f32(dy_nhwc)
+    m = int(x.shape[0]) * int(x.shape[1]) * int(x.shape[2])
+    ws = _workspace(conv1x1_wgrad_f16_workspace(m, cin, cout), x.device)
+    dw = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=x.device)
+    call("dream_conv1x1_wgrad_f16_nhwc_f32", ptr(x), ptr(dy), ptr(amax_dy), ptr(dw), ptr(ws), m, cin, cout, int(dy.shape[3]), ptr(pre_ab),
+         stream())
+    return dw
+
+
+def bn_bwd_apply_amax(z_nhwc, dy, gamma, mean, invstd, dgamma, dbeta, amax, y_act=None, ab=None, want_g=False):
+    """bn_bwd_apply that also publishes max|dz| into ``amax`` (one int32 word; the launch zeroes it first) -> (dz, g or None)."""
+    z = _f32(z_nhwc)
+    c = int(z.shape[-1])
+    dz = torch.empty_like(z)
+    g = torch.empty_like(z) if want_g else None
+    call("dream_bn_bwd_apply_amax_nhwc_f32", ptr(z), ptr(_f32(dy)), ptr(y_act), ptr(ab), ptr(gamma.detach()), ptr(mean), ptr(invstd),
+         ptr(dgamma), ptr(dbeta), ptr(dz), ptr(g), ptr(amax), z.numel() // c, c, _mask_mode(y_act, ab), stream())
+    return dz, g
+
+
 def conv_transpose4x4s2(x_nhwc, packed, cout, scale=None, shift=None, flags=0, direct_taps=16):
     """direct_taps: multiply-adds per (input pixel, cin, cout) of the direct algorithm this launch stands for -- 16 for a
     4x4 transposed conv, 36 when it replaces upsample + conv3x3; only used by bench.py's FLOP accounting."""

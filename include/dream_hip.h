@@ -718,6 +718,56 @@ int dream_conv3x3_winograd_bwd_bnmask_nhwc_f32(const float *dy, const float *u_p
 /* weight gradient of a 1x1 conv whose input was relu(pre_ab[0][ci] x + pre_ab[1][ci]) (x = the BN input) */
 int dream_conv1x1_wgrad_pre_nhwc_f32(const float *x, const float *dy, float *dw, void *workspace, long M, int Cin, int Cout,
                                      int Cdy, const float *pre_ab, void *stream);
+/* ---- ResnetSimple train_gemm_precision="fp16": the 1x1 GEMMs above on the fp16 matrix cores (gemm1x1_f16.hip; the torchvision Bottleneck
+ * conv1 / conv3 / downsample convs behind /root/reference/dream/models.py:22-32, trained through network.py:328-364).  Every tensor in
+ * memory stays fp32; a launch rounds each operand once while it loads it: an activation as half(clamp(x, +-65504)), a gradient as
+ * half(dy * 2^e_g) with e_g = 13 - exponent(*amax) from the scalar published by the launch that wrote it (0 for a zero tensor), the
+ * weights at pack time as half(w * 2^e_w).  fp32 accumulation; the powers of two are taken out in the epilogue.  Shape contract,
+ * K-split levels, workspace / counters (dream_conv1x1_bn_workspace / _counters) and the deterministic statistics: the fp32 forms'. */
+size_t dream_conv1x1_weight_halfs(int rows, int K);
+int dream_conv1x1_f16_set_ksplit(int ks);   /* test hook, as dream_conv1x1_set_ksplit */
+/* w_oihw [Cout][Cin][1][1] -> dream_conv1x1_weight_halfs(rows, K) halfs and *exp_out = e_w (device int); mode as
+ * dream_pack_conv1x1_weight; scratch: one device uint32 */
+int dream_pack_conv1x1_weight_f16(const float *w_oihw, void *packed, int *exp_out, unsigned *scratch, int Cout, int Cin, int mode,
+                                  void *stream);
+/* every half copy of a network by three launches per step (zero the amax words, every weight's amax, every pack) instead of three per
+ * copy, as dream_pack_weights_batched does for the fp32 copies (the optimizer of network.py:337 changed every weight).  jobs: DEVICE
+ * array; scratch fields point into the njobs words of `scratch`, one per job.  Same values as the one-tensor entry point, bit for bit. */
+typedef struct dream_pack16_job {
+    const float *src;      /* [cout][cin][1][1] */
+    void *dst;             /* dream_conv1x1_weight_halfs() halfs */
+    int *exp;              /* e_w out */
+    unsigned *scratch;     /* this job's amax word */
+    int cout, cin, mode, reserved;
+} dream_pack16_job;
+size_t dream_pack16_job_bytes(void);
+int dream_pack_conv1x1_weights_f16_batched(const dream_pack16_job *jobs_device, int njobs, unsigned *scratch, int workgroups_per_job,
+                                           void *stream);
+/* dream_conv1x1_nhwc_f32 without scale / ReLU (Bottleneck data gradients, loss.backward() of network.py:335): y = x . w^T + shift
+ * (+ residual); amax_x: the gradient operand's scalar, or NULL for an activation operand (e_x = 0) */
+int dream_conv1x1_f16_nhwc_f32(const float *x, const unsigned *amax_x, const void *w_packed, const int *w_exp, const float *shift,
+                               const float *residual, float *y, long M, int K, int N, int x_stride, void *stream);
+/* dream_conv1x1_bnstats_nhwc_f32 (Bottleneck conv -> BatchNorm2d forward, dream/models.py:22-32) */
+int dream_conv1x1_bnstats_f16_nhwc_f32(const float *x, const void *w_packed, const int *w_exp, const float *shift, const float *pre_ab,
+                                       float *y, long M, int K, int N, int x_stride, const float *gamma, const float *beta,
+                                       float *running_mean, float *running_var, long long *num_batches_tracked, float eps,
+                                       float momentum, float *out_ab, float *save_mean, float *save_invstd, void *workspace,
+                                       unsigned *counters, void *stream);
+/* dream_conv1x1_bwd_bnmask_nhwc_f32 (the same chain's backward, network.py:335); the mask is the fp32 form's, bit for bit */
+int dream_conv1x1_bwd_bnmask_f16_nhwc_f32(const float *dy, const unsigned *amax_dy, const void *w_packed_t, const int *w_exp,
+                                          const float *residual, float *g_out, long M, int K, int N, int dy_stride, const float *z,
+                                          const float *ab, const float *y_act, const float *mean, const float *invstd, float *dgamma,
+                                          float *dbeta, void *workspace, unsigned *counters, void *stream);
+/* dream_conv1x1_wgrad_nhwc_f32 / _pre_ (pre_ab NULL or [2][Cin]): dw = sum_pos half(dy 2^e_g) half(clamp(x)) * 2^-e_g; split over
+ * positions into the workspace, fixed-order reduce: two runs give the same bits */
+size_t dream_conv1x1_wgrad_f16_workspace(long M, int Cin, int Cout);
+int dream_conv1x1_wgrad_f16_nhwc_f32(const float *x, const float *dy, const unsigned *amax_dy, float *dw, void *workspace, long M,
+                                     int Cin, int Cout, int Cdy, const float *pre_ab, void *stream);
+/* dream_bn_bwd_apply_nhwc_f32 (BatchNorm2d backward of the same chain) that also publishes max|dz| into *amax_out (zeroed by the
+ * launch's own fill kernel): the scalar the three gradient-reading entry points above take.  dz / g_out: bit-equal to the plain form. */
+int dream_bn_bwd_apply_amax_nhwc_f32(const float *z, const float *dy, const float *y_act, const float *ab, const float *gamma,
+                                     const float *save_mean, const float *save_invstd, const float *dgamma, const float *dbeta,
+                                     float *dz, float *g_out, unsigned *amax_out, size_t npix, int C, int mask, void *stream);
 /* the same pool for training: also stores which element of its 3x3 window won (uint8 0..8 = 3 dy + dx, the first maximum in scan
  * order: ATen's max_pool2d_with_indices), so that the backward pass compares one byte per window instead of recomputing nine-way
  * arg-maxima; idx: [B,Ho,Wo,C] bytes */
