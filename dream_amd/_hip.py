@@ -118,6 +118,11 @@ _SIGNATURES = {
     "dream_conv3x3_first_nchw_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dream_add_f16": (_I, [_P, _P, _P, _SZ, _P, _P]),
+    "dream_conv2d_f16_res16_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_im2col_nchw_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_maxpool3s2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "dream_subsample2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "dream_im2col3s2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dream_bn_fold_f32": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _P]),
     "dream_im2col_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),

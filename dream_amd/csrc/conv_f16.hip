@@ -21,9 +21,9 @@
 namespace {
 
 // ---- the forms of the kernel ---------------------------------------------------------------------------------------------------------
-// One kernel text (conv_f16_body.inc, conv_f16_epilogue.inc), nine kernels per tile: each form is a kernel of its own from the same
+// One kernel text (conv_f16_body.inc, conv_f16_epilogue.inc), ten kernels per tile: each form is a kernel of its own from the same
 // text, so that adding one leaves the machine code of the measured ones as it is (tools/isa_same.py).  This table is the
-// one place that says what a form is: the five constants the body and the epilogue read, and what launch_f16 accepts with it.
+// one place that says what a form is: the six constants the body and the epilogue read, and what launch_f16 accepts with it.
 //   plain          fp32 x (scaled by its amax while staged), fp32 y: precision="fp16"
 //   mask           + the DREAM_CONV_RELUMASK epilogue, y = residual > 0 ? conv : 0 -- the data gradient of a conv behind a ReLU
 //                  (train_precision="fp16")
@@ -42,15 +42,22 @@ namespace {
 //                  (half g in, y * 2^-e_g stored as fp32, amax_out after the mask).  The mask, where there is one, is a half tensor; the
 //                  unmasked interior form is act16 itself.  amax_out of the half-writing forms: max|y * 2^e_g| of what is stored, before
 //                  the saturation.
-enum Form16 { kPlain, kMask, kAct16, kMask16, kKsplit, kG16Entry, kG16EntryMask, kG16Interior, kG16Exit, kNumForms };
+//   act16 + residual   act16 with a half residual of the output's shape (ResnetSimple's inference_activation_storage="fp16": a Bottleneck's
+//                  conv3): v = acc * (2^-ew * scale) + shift + float(residual), ReLU, max|v| into the peak scalar, sat_half.
+//                  The residual is read as the pair of halfs the lane stores (4-byte aligned).  Stride-1 NHWC convs only (no pool,
+//                  upsample, NCHW)
+enum Form16 { kPlain, kMask, kAct16, kMask16, kKsplit, kG16Entry, kG16EntryMask, kG16Interior, kG16Exit, kRes16, kNumForms };
 
 // the flags whose launches are never split (conv_ksplit: the large-map layers and the K-channel output)
 constexpr int kKsplitRefused = DREAM_CONV_POOL2 | DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_RELUMASK;
+// ... and those the residual form does not take
+constexpr int kRes16Refused = kKsplitRefused | DREAM_CONV_RES_AFTER_RELU;
 
 struct Form16Row {
     const char *name;
     bool EPI_MASK, ACT16, MASK16, KSPLIT;     // the kernel's constants
     int GRAD16;
+    bool RES16;
     bool affine;                              // launch_f16: scale / shift may be given
     bool residual;                            //             `residual` may be a true residual (a form with EPI_MASK: it IS the mask)
     int flags_ok;                             //             the flag bits the form accepts
@@ -60,16 +67,17 @@ struct Form16Row {
     constexpr bool needs_grad_amax() const { return GRAD16 == 1 || GRAD16 == 3; }
 };
 constexpr Form16Row kForms[kNumForms] = {
-    //  name                EPI_MASK ACT16  MASK16 KSPLIT GRAD16 affine residual flags_ok
-    {"plain",               false,   false, false, false, 0,     true,  true,    ~DREAM_CONV_RELUMASK},
-    {"mask",                true,    false, false, false, 0,     true,  false,   ~0},
-    {"act16",               false,   true,  false, false, 0,     true,  false,   ~DREAM_CONV_RELUMASK},
-    {"mask16",              true,    false, true,  false, 0,     true,  false,   ~0},
-    {"ksplit",              false,   true,  false, true,  0,     false, false,   ~kKsplitRefused},
-    {"g16 entry",           false,   false, false, false, 1,     false, false,   0},
-    {"g16 entry + mask",    true,    false, true,  false, 1,     false, false,   DREAM_CONV_RELUMASK},
-    {"g16 interior",        true,    true,  true,  false, 2,     false, false,   DREAM_CONV_RELUMASK},
-    {"g16 exit",            true,    true,  true,  false, 3,     false, false,   DREAM_CONV_RELUMASK},
+    //  name                EPI_MASK ACT16  MASK16 KSPLIT GRAD16 RES16  affine residual flags_ok
+    {"plain",               false,   false, false, false, 0,     false, true,  true,    ~DREAM_CONV_RELUMASK},
+    {"mask",                true,    false, false, false, 0,     false, true,  false,   ~0},
+    {"act16",               false,   true,  false, false, 0,     false, true,  false,   ~DREAM_CONV_RELUMASK},
+    {"mask16",              true,    false, true,  false, 0,     false, true,  false,   ~0},
+    {"ksplit",              false,   true,  false, true,  0,     false, false, false,   ~kKsplitRefused},
+    {"g16 entry",           false,   false, false, false, 1,     false, false, false,   0},
+    {"g16 entry + mask",    true,    false, true,  false, 1,     false, false, false,   DREAM_CONV_RELUMASK},
+    {"g16 interior",        true,    true,  true,  false, 2,     false, false, false,   DREAM_CONV_RELUMASK},
+    {"g16 exit",            true,    true,  true,  false, 3,     false, false, false,   DREAM_CONV_RELUMASK},
+    {"act16 + residual",    false,   true,  false, false, 0,     true,  true,  true,    ~kRes16Refused},
 };
 
 template <int FORM, int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
@@ -79,6 +87,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16P
     constexpr bool MASK16 = kForms[FORM].MASK16;
     constexpr bool KSPLIT = kForms[FORM].KSPLIT;
     constexpr int GRAD16 = kForms[FORM].GRAD16;
+    constexpr bool RES16 = kForms[FORM].RES16;
 #include "conv_f16_body.inc"
 }
 
@@ -127,7 +136,8 @@ struct Variant16h {
 #define F16_KERNELS(...) /* in the order of Form16 */ \
     {conv_f16_kernel<kPlain, __VA_ARGS__>, conv_f16_kernel<kMask, __VA_ARGS__>, conv_f16_kernel<kAct16, __VA_ARGS__>, \
      conv_f16_kernel<kMask16, __VA_ARGS__>, conv_f16_kernel<kKsplit, __VA_ARGS__>, conv_f16_kernel<kG16Entry, __VA_ARGS__>, \
-     conv_f16_kernel<kG16EntryMask, __VA_ARGS__>, conv_f16_kernel<kG16Interior, __VA_ARGS__>, conv_f16_kernel<kG16Exit, __VA_ARGS__>}
+     conv_f16_kernel<kG16EntryMask, __VA_ARGS__>, conv_f16_kernel<kG16Interior, __VA_ARGS__>, conv_f16_kernel<kG16Exit, __VA_ARGS__>, \
+     conv_f16_kernel<kRes16, __VA_ARGS__>}
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -179,6 +189,7 @@ int launch_f16(Form16 form, const void *x, const unsigned *amax_in, const void *
     DREAM_REQUIRE(f.EPI_MASK || f.residual || residual == nullptr, "conv_f16: the %s form takes no residual", f.name);
     DREAM_REQUIRE(!(f.x16() || f.y16()) || ((((size_t)x | (size_t)y) & 15) == 0), "conv_f16: half tensors must be 16-byte aligned");
     DREAM_REQUIRE(!(f.GRAD16 && f.MASK16) || ((size_t)residual & 3) == 0, "conv_f16: the half mask of the %s form must be 4-byte aligned", f.name);
+    DREAM_REQUIRE(!f.RES16 || (residual != nullptr && ((size_t)residual & 3) == 0), "conv_f16: the %s form needs its half residual, 4-byte aligned", f.name);
     DREAM_REQUIRE(!f.needs_grad_amax() || grad_amax != nullptr, "conv_f16: the %s form needs the loss gradient's amax", f.name);
     DREAM_REQUIRE(Cin % KC == 0, "conv_f16: Cin=%d must be a multiple of %d", Cin, KC);
     Conv16Params p;
@@ -298,6 +309,16 @@ extern "C" int dream_conv2d_f16_nhwc_f16(const void *x, const void *w, const int
     if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
     const Geom16 g = geom16_conv(H, W, ksize, flags);
     return launch_f16(kAct16, x, nullptr, w, w_exp, scale, shift, nullptr, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
+}
+
+// ... with a residual stored as half, [B,H,W,Cout], 4-byte aligned: y = half(sat(relu?(conv * scale + shift + float(residual)))), amax_out =
+// max|.| before the saturation.  NHWC only: a fused pool / upsample and DREAM_CONV_OUT_NCHW are refused.
+extern "C" int dream_conv2d_f16_res16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                                               const void *residual, void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout,
+                                               int CoutPad, int ksize, int stride, int flags, void *stream) {
+    if (int rc = check_conv2d_f16(H, W, ksize, stride, flags)) return rc;
+    const Geom16 g = geom16_conv(H, W, ksize, flags);
+    return launch_f16(kRes16, x, nullptr, w, w_exp, scale, shift, residual, y, amax_out, B, Cin, Cout, CoutPad, g, flags, stream);
 }
 
 extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,

@@ -6,7 +6,8 @@
 // slice blockIdx.z of the gridDim.z slices of the contraction -- a contiguous range of the (channel chunk, tap) stages, the leftover
 // spread over the first slices -- whose raw fp32 accumulators go to p.y = workspace[slice] in NHWC fp32: no scale, no shift, no ReLU,
 // no peak; conv_f16_ksplit_finish_kernel sums the slices and runs the epilogue) and GRAD16 (int constant, read by the epilogue: the
-// entry / interior / exit form of a half-stored data gradient, 0 otherwise; the loader follows ACT16 as ever).
+// entry / interior / exit form of a half-stored data gradient, 0 otherwise; the loader follows ACT16 as ever) and RES16 (bool constant,
+// read by the epilogue: `residual` is a tensor of IEEE halfs).
     constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
     constexpr int BN = 32 * NR * WN;
     constexpr int QW = ACT16 ? 8 : 4;               // elements of a 16-byte piece

@@ -8,6 +8,8 @@
 // output (the K-channel belief maps) stays fp32.
 // GRAD16 (int constant; conv_f16.hip, 0 everywhere else): the forms of a half-stored data gradient -- 1 entry: y * 2^e_g stored as half
 // whatever ACT16 says (x is fp32); 2 interior: ACT16's store with MASK16's mask; 3 exit: y * 2^-e_g stored as fp32 (x is half).
+// RES16 (bool constant; conv_f16.hip, false everywhere else): with ACT16, `residual` is a tensor of IEEE halfs of the output's shape,
+// added before the ReLU; the peak is taken behind both.  The paired store reads it as the pair of halfs that the lane stores.
     // ---- epilogue -----------------------------------------------------------------------------------------
     constexpr bool OUT16 = GRAD16 == 0 ? ACT16 : GRAD16 != 3;      // an NHWC y is IEEE half
     float gs = 1.0f;                                               // (GRAD16 entry / exit) 2^e_g / 2^-e_g, applied to the finished value
@@ -62,14 +64,28 @@
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
                             v[j] = acc[ms][ns][2 * r2 + j] * scale_v[ns] + shift_v[ns];
-                            if (relu) v[j] = fmaxf(v[j], 0.0f);
+                            if (!RES16 && relu) v[j] = fmaxf(v[j], 0.0f);     // (RES16: behind the residual, below)
                             if constexpr (GRAD16 == 1) v[j] *= gs;
-                            if constexpr (GRAD16 == 0) {
+                            if constexpr (GRAD16 == 0 && !RES16) {
                                 if (ok[j] && cok) amax = fmaxf(amax, fabsf(v[j]));
                             }
                         }
                         const float got = quad_perm_1032(odd ? v[0] : v[1]);
-                        if constexpr (GRAD16 != 0) {
+                        if constexpr (RES16) {
+                            // the lane's two channels of pixel pix[odd]: the half residual is read as the pair that is stored, then
+                            // the ReLU, the peak (before the saturation) and the store
+                            float a0 = odd ? got : v[0], a1 = odd ? v[1] : got;
+                            if (ok[odd] && cok) {
+                                const size_t o2 = pix[odd] * p.Cout + (ncol[ns] & ~1);
+                                const f16x2_ rs = *(const f16x2_ *)((const _Float16 *)p.residual + o2);
+                                a0 = a0 + (float)rs[0];
+                                a1 = a1 + (float)rs[1];
+                                if (relu) { a0 = fmaxf(a0, 0.0f); a1 = fmaxf(a1, 0.0f); }
+                                amax = fmaxf(amax, fmaxf(fabsf(a0), fabsf(a1)));
+                                const f16x2_ h = {sat_half(a0), sat_half(a1)};
+                                *(f16x2_ *)(yh + o2) = h;
+                            }
+                        } else if constexpr (GRAD16 != 0) {
                             // the lane's two channels of pixel pix[odd]: the half mask is read as the pair that is stored, the peak is
                             // taken after the mask, of what is stored
                             float a0 = odd ? got : v[0], a1 = odd ? v[1] : got;
@@ -113,6 +129,7 @@
                         if constexpr (GRAD16 == 1 || GRAD16 == 3) v *= gs;
                         if constexpr (EPI_MASK && MASK16) v = (float)((const _Float16 *)p.residual)[o] > 0.0f ? v : 0.0f;
                         else if constexpr (EPI_MASK) v = p.residual[o] > 0.0f ? v : 0.0f;
+                        else if constexpr (RES16) v = v + (float)((const _Float16 *)p.residual)[o];
                         else if (p.residual != nullptr) v = v + p.residual[o];
                         if (relu) v = fmaxf(v, 0.0f);
                         if constexpr (OUT16) {

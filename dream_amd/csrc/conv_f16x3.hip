@@ -203,6 +203,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16x3_kernel(const Conv1
     constexpr bool ACT16 = false;                   // (and so is half activation storage)
     constexpr bool MASK16 = false;                  // (and a half ReLU mask)
     constexpr int GRAD16 = 0;                       // (and the half-stored data gradients)
+    constexpr bool RES16 = false;                   // (and a half residual: here `residual` is fp32)
 #include "conv_f16_epilogue.inc"
 }
 

@@ -703,6 +703,106 @@ __global__ void __launch_bounds__(256) add_f16_kernel(const _Float16 *a, const _
     if (amax) publish_amax(amax, m);
 }
 
+// ---- ResnetSimple's half-storage walk (inference_activation_storage="fp16"): 16 bytes = 8 halfs per lane -------------
+// subsample2_kernel / im2col3s2_kernel on halfs: copies (and zeros), nothing is rounded, nothing to publish
+__global__ void __launch_bounds__(256) subsample2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8) {
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    const size_t total = (size_t)B * Ho * Wo * C8;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        size_t r = i / C8;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        y[i] = x[(((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c];
+    }
+}
+__global__ void __launch_bounds__(256) im2col3s2_f16_kernel(const f16x8 *x, f16x8 *col, int B, int H, int W, int C8) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t total = (size_t)B * Ho * Wo * 9 * C8;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        size_t r = i / C8;
+        const int t = (int)(r % 9);
+        r /= 9;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const int py = 2 * oy - 1 + t / 3, px = 2 * ox - 1 + t % 3;
+        col[i] = (py >= 0 && py < H && px >= 0 && px < W) ? x[(((size_t)b * H + py) * W + px) * C8 + c] : zero;
+    }
+}
+
+// maxpool3s2_kernel on halfs: the maximum of up to nine halfs is one of them -- exact; padding never wins (-inf), and every window
+// holds a pixel of the image
+__global__ void __launch_bounds__(256) maxpool3s2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8, int Ho, int Wo) {
+    const size_t total = (size_t)B * Ho * Wo * C8;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        size_t r = i / C8;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const float ninf = -__builtin_huge_valf();
+        float o[8] = {ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const int iy = 2 * oy - 1 + dy;
+            if (iy < 0 || iy >= H) continue;
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = 2 * ox - 1 + dx;
+                if (ix < 0 || ix >= W) continue;
+                const f16x8 v = x[(((size_t)b * H + iy) * W + ix) * C8 + c];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) o[k] = fmaxf(o[k], (float)v[k]);
+            }
+        }
+        f16x8 h;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h[k] = (_Float16)o[k];
+        y[i] = h;
+    }
+}
+
+// im2col_nchw_fixed_kernel storing halfs: the fp32 image is rounded once, at the store (saturating, to nearest even); max|v| before
+// the saturation goes to the peak scalar.  A thread produces eight consecutive k of one output pixel (one 16-byte store).
+template <int C, int KH, int KW, int STRIDE, int PAD>
+__global__ void __launch_bounds__(256) im2col_nchw_f16_fixed_kernel(const float *x, _Float16 *y, int H, int W, int Ho, int Wo, int Kpad,
+                                                                    unsigned *amax) {
+    constexpr int K = C * KH * KW;
+    const int oy = (int)blockIdx.x, b = (int)blockIdx.y;
+    const int K8 = Kpad >> 3;
+    const float *img = x + (size_t)b * C * H * W;
+    f16x8 *row = (f16x8 *)(y + ((size_t)b * Ho + oy) * (size_t)Wo * Kpad);
+    const int n = Wo * K8;
+    float m = 0.f;
+    for (int i = (int)threadIdx.x; i < n; i += 256) {
+        const int ox = (int)((unsigned)i / (unsigned)K8);
+        const int k0 = (i - ox * K8) * 8;
+        f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + e;
+            if (k < K) {
+                const int kx = k % KW, ky = (k / KW) % KH, c = k / (KW * KH);
+                const int iy = oy * STRIDE - PAD + ky, ix = ox * STRIDE - PAD + kx;
+                if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const float t = img[(c * H + iy) * W + ix];
+                    m = fmaxf(m, fabsf(t));
+                    v[e] = sat_half(t);
+                }
+            }
+        }
+        row[i] = v;
+    }
+    if (amax) publish_amax(amax, m);
+}
+
 // ---- training with the saved activations stored as IEEE half (train_activation_storage="fp16") -------------------------------------
 // maxpool2_bwd_kernel with a half forward input: dy and dx stay fp32, x is read as four halfs (8 bytes) per lane and window element.
 // A half compares as its fp32 value, so the first maximum in window scan order -- and the RELU mask -- are those of the fp32 kernel on
@@ -1063,6 +1163,47 @@ extern "C" int dream_maxpool3s2_nhwc_f32(const float *x, float *y, int B, int H,
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL(maxpool3s2_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 4))), dim3(256), 0, (hipStream_t)stream,
                        (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4, Ho, Wo);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+// ---- ResnetSimple's half-storage walk: the four streaming kernels on IEEE halfs (16-byte aligned, C % 8 == 0) --------------------
+extern "C" int dream_subsample2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "subsample2_f16: bad arguments (C=%d must be a multiple of 8)", C);
+    DREAM_REQUIRE(aligned16(x, y), "subsample2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
+    hipLaunchKernelGGL(subsample2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_im2col3s2_nhwc_f16(const void *x, void *col, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(x && col && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "im2col3s2_f16: bad arguments (C=%d must be a multiple of 8)", C);
+    DREAM_REQUIRE(aligned16(x, col), "im2col3s2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    const size_t total = (size_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 9 * (C / 8);
+    hipLaunchKernelGGL(im2col3s2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f16x8 *)x, (f16x8 *)col, B, H, W, C / 8);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_maxpool3s2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
+    DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "maxpool3s2_f16: bad arguments (C=%d must be a multiple of 8)", C);
+    DREAM_REQUIRE(aligned16(x, y), "maxpool3s2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    hipLaunchKernelGGL(maxpool3s2_f16_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+                       (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8, Ho, Wo);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+extern "C" int dream_im2col_nchw_f16(const float *x, void *y, unsigned *amax_out, int B, int C, int H, int W, int KH, int KW, int stride,
+                                     int pad, int Kpad, void *stream) {
+    DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0, "im2col_f16: bad arguments");
+    DREAM_REQUIRE(C == 3 && KH == 7 && KW == 7 && stride == 2 && pad == 3 && Kpad >= C * KH * KW && Kpad % 8 == 0,
+                  "im2col_f16: built for the ResNet stem only (3 channels, 7x7, stride 2, pad 3, Kpad %% 8 == 0)");
+    DREAM_REQUIRE(((size_t)y & 15) == 0, "im2col_f16: y must be 16-byte aligned (the kernel moves 8 halfs)");
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    DREAM_REQUIRE(Ho > 0 && Wo > 0, "im2col_f16: empty output");
+    DREAM_REQUIRE((size_t)Wo * (Kpad / 8) < ((size_t)1 << 30) && (size_t)C * H * W < ((size_t)1 << 30) && B <= 65535,
+                  "im2col_f16: the image or the batch is too large for the kernel's 32-bit indices");
+    hipLaunchKernelGGL((im2col_nchw_f16_fixed_kernel<3, 7, 7, 2, 3>), dim3((unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       x, (_Float16 *)y, H, W, Ho, Wo, Kpad, amax_out);
     DREAM_LAUNCH_OK();
     return 0;
 }

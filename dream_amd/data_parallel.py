@@ -131,7 +131,8 @@ def _buffer_stamp(module):
 
 
 def _settings(module):
-    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "conv_ksplit", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"))
+    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "inference_activation_storage", "conv_ksplit", "conv_algorithm", "conv1x1_algorithm",
+                                                       "convT_algorithm"))
 
 
 class _Busy:
@@ -431,7 +432,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "conv_ksplit", "train_precision", "train_gemm_precision", "train_activation_storage",
+            for attr in ("precision", "activation_storage", "inference_activation_storage", "conv_ksplit", "train_precision", "train_gemm_precision", "train_activation_storage",
                          "train_gradient_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))
@@ -780,8 +781,9 @@ class DreamDataParallel(nn.Module):
 
     # ---- nn.Module interface ------------------------------------------------------------------------------------------------
     def half_storage_peak(self):
-        """DreamHourglass.half_storage_peak() of the last forward over every replica that took a chunk of it: the largest value any
-        device wanted to store with activation_storage="fp16" (>= 65504: that forward saturated somewhere)."""
+        """DreamHourglass.half_storage_peak() / ResnetSimple.half_storage_peak() of the last forward over every replica that took a chunk
+        of it: the largest value any device wanted to store with activation_storage="fp16" / inference_activation_storage="fp16"
+        (>= 65504: that forward saturated somewhere)."""
         n = getattr(self, "_last_shards", 1)
         return max(m.half_storage_peak() for m in [self.module] + list(self._replicas[:n - 1]))
 

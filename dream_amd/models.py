@@ -1466,8 +1466,8 @@ class ResnetSimple(nn.Module):
     _FP32_ACTIVATIONS = "ResnetSimple stores its activations in fp32 only"
     # (the hourglass's switch: its plain 3x3 convs.  ResnetSimple's half-precision training is a switch of its own, train_gemm_precision)
     train_precision = _FixedSwitch("fp32", "ResnetSimple trains in fp32 only", "its half-precision training covers the fused 1x1 GEMMs: train_gemm_precision")
-    activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS,
-                                      "the stride-2 trunk convs, the 3x3 max-pool and the 4x4 transposed convs read and write fp32")
+    # (the hourglass's switch.  ResnetSimple's half-stored inference is a switch of its own, inference_activation_storage)
+    activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "its half-stored inference is a switch of its own: inference_activation_storage")
     conv_ksplit = _FixedSwitch("off", "ResnetSimple does not split its convs", "its convs read and write fp32")
     train_gradient_storage = _FixedSwitch("fp32", "ResnetSimple stores its gradients in fp32 only", "ResnetSimple trains in fp32 only")
     train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "ResnetSimple trains in fp32 only")
@@ -1481,6 +1481,13 @@ class ResnetSimple(nn.Module):
         # bn_fusion and conv1x1_algorithm="gemm".  Read once per forward pass (_resolve_train_gemm_precision).  Not spelled ``train_precision``:
         # that name is DreamHourglass's switch (its plain 3x3 convs), which this class exposes as fixed to "fp32" and keeps refusing.
         self.train_gemm_precision = "fp32"
+        # Inference, with precision="fp16": "fp16" = every tensor between the image and the K belief maps lives in HBM as IEEE half NHWC --
+        # half(clamp(v, +-65504)), no per-tensor scale; the stored half IS the consumer's MFMA operand -- and the six stride-2 convs run on
+        # the fp16 matrix cores over gathered pixels / patch rows (_walk_act16).  "fp32" (default): today's walk.  Read once per
+        # evaluation forward (_resolve_inference_activation_storage); a training pass ignores it.  See half_storage_peak().  Not spelled
+        # ``activation_storage``: that name is DreamHourglass's switch, which this class exposes as fixed to "fp32" and keeps refusing.
+        self.inference_activation_storage = "fp32"
+        self._storage_peak = _PeakScalar("half_storage_peak(): no forward with inference_activation_storage=\"fp16\" has run")
         self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
         # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
         self.conv1x1_algorithm = os.environ.get("DREAM_CONV1X1_ALGORITHM", "gemm")
@@ -1829,8 +1836,82 @@ class ResnetSimple(nn.Module):
         p16 = self._cached(("w" + sfx, name), [conv.weight], lambda: getattr(ops, "pack_conv_weight_" + sfx)(conv.weight.detach(), 0))
         return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], k, scale, shift, residual, flags)
 
-    def run_forward_half(self, x, sfx):
-        """The evaluation forward on the ops of _HALF_OPS suffix ``sfx`` ("f16x3" | "f16"): one walk for both."""
+    # ---- ... with the activations stored as IEEE half (inference_activation_storage="fp16") -----------------------
+    def _resolve_inference_activation_storage(self, training):
+        """Reads ``inference_activation_storage`` once for this pass -> does this evaluation forward store its activations as half?
+        ValueError for an unknown value (both passes) and, in an evaluation pass, for "fp16" without precision="fp16"."""
+        st = self.inference_activation_storage
+        if st not in ("fp32", "fp16"):
+            raise ValueError("unknown inference_activation_storage %r (\"fp32\" or \"fp16\")" % (st,))
+        half = not training and st == "fp16"
+        if half and self.precision != "fp16":
+            raise ValueError("inference_activation_storage=\"fp16\" needs precision=\"fp16\" (precision is %r)" % (self.precision,))
+        return half
+
+    def half_storage_peak(self):
+        """The largest |value|, before saturation, that any launch of the last forward with inference_activation_storage="fp16" wanted to
+        store as a half (this module's own forward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_storage_peak(), which takes
+        the maximum over the replicas).  >= 65504: that forward saturated -- go back to inference_activation_storage="fp32".  Reading it
+        is the mode's only host synchronisation, and happens only here."""
+        return self._storage_peak.read()
+
+    def _conv_bn_act16(self, name, x, conv, bn, relu, peak, residual=None):
+        """One conv + folded BatchNorm (+ half residual) (+ ReLU) of the half-storage walk -> y, torch.float16 NHWC.  A stride-2 conv is a
+        gather -- the pixels a 1x1 conv reads, the patch rows [B,Ho,Wo,9 Cin] of a 3x3 one -- followed by the 1-tap conv over the
+        gathered rows: the form training runs in fp32 (_unit: ``sub2``, ``col3``), here on the fp16 matrix cores like every other conv."""
+        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
+        scale, shift = self._fold(name, bn, conv.bias)
+        cout = int(conv.weight.shape[0])
+        if stride == 2 and k == 3:
+            x, k = ops.im2col3s2_f16(x), 1
+            p16 = self._cached(("wf16col3", name), [conv.weight], lambda: ops.pack_conv_weight_f16(
+                conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 0))
+        else:
+            if stride == 2:
+                x = ops.subsample2_f16(x)
+            p16 = self._cached(("wf16", name), [conv.weight], lambda: ops.pack_conv_weight_f16(conv.weight.detach(), 0))
+        flags = CONV_RELU if relu else 0
+        if residual is not None:
+            return ops.conv2d_f16_act16_res(x, p16, cout, k, residual, scale, shift, flags, peak=peak)
+        return ops.conv2d_f16_act16(x, p16, cout, k, scale, shift, flags, peak=peak)
+
+    def _bottleneck_act16(self, name, blk, y, peak):
+        """One Bottleneck of the half-storage walk: the downsample result is stored as half and is conv3's residual."""
+        idt = y
+        if hasattr(blk, "downsample"):
+            idt = self._conv_bn_act16(name + ".ds", y, blk.downsample[0], blk.downsample[1], False, peak)
+        o = self._conv_bn_act16(name + ".1", y, blk.conv1, blk.bn1, True, peak)
+        o = self._conv_bn_act16(name + ".2", o, blk.conv2, blk.bn2, True, peak)
+        return self._conv_bn_act16(name + ".3", o, blk.conv3, blk.bn3, True, peak, residual=idt)
+
+    def _walk_act16(self, x):
+        """run_forward_half("f16") with every tensor between the fp32 image and the fp32 belief maps stored as half; every half-writing
+        launch atomicMaxes max|v| before the saturation into the module's peak scalar (half_storage_peak())."""
+        peak = self._storage_peak.zeroed(x.device)
+        col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=peak)
+        w1 = self._cached(("wf16", "conv1"), [self.conv1.weight],
+                          lambda: ops.pack_conv_weight_f16(self.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        s1, t1 = self._fold("bn1", self.bn1)
+        y = ops.conv2d_f16_act16(col, w1, 64, 1, s1, t1, CONV_RELU, peak=peak)
+        del col
+        y = ops.maxpool3s2_f16(y)
+        for name, blk in self._trunk():
+            y = self._bottleneck_act16(name, blk, y, peak)
+        for name, m, bn in self._decoder():
+            if bn is not None:
+                p16 = self._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
+                scale, shift = self._fold(name, bn, m.bias)
+                y = ops.conv_transpose4x4s2_f16_act16(y, p16, p16[3], scale, shift, CONV_RELU, peak=peak)
+            else:                                           # the K belief maps: NCHW, fp32
+                p16 = self._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
+                y = ops.conv2d_f16_act16(y, p16, p16[3], 1, None, m.bias.detach(), CONV_OUT_NCHW)
+        return y
+
+    def run_forward_half(self, x, sfx, act16=False):
+        """The evaluation forward on the ops of _HALF_OPS suffix ``sfx`` ("f16x3" | "f16"): one walk for both.  ``act16`` ("f16" only):
+        the walk with half-stored activations (_walk_act16)."""
+        if act16:
+            return self._walk_act16(x)
         pack, packT = getattr(ops, "pack_conv_weight_" + sfx), getattr(ops, "pack_convT4x4_weight_" + sfx)
         conv2d, convT = getattr(ops, "conv2d_" + sfx), getattr(ops, "conv_transpose4x4s2_" + sfx)
         col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
@@ -1862,8 +1943,9 @@ class ResnetSimple(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
         self._resolve_train_gemm_precision(False)
+        act16 = self._resolve_inference_activation_storage(False)
         if self.precision in _HALF_OPS:
-            return self.run_forward_half(x, _HALF_OPS[self.precision])
+            return self.run_forward_half(x, _HALF_OPS[self.precision], act16)
         # stem: 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused; then MaxPool(3,2,1)
         col = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0e"])           # (= STEM_COLS["w"])
         s1, t1 = self._fold("bn1", self.bn1)
@@ -2006,6 +2088,7 @@ class ResnetSimple(nn.Module):
         """-> (belief maps NCHW, tape)."""
         fused = self.bn_fusion
         half = self._resolve_train_gemm_precision(True)
+        self._resolve_inference_activation_storage(True)         # (an inference switch: only an unknown value is refused here)
         self._repack_weights(split=fused)
         if half:
             self._repack_half_weights()

@@ -1745,6 +1745,57 @@ def add_f16(a, b, peak=None):
     return out
 
 
+# ---- ResnetSimple with its activations stored as IEEE half (inference_activation_storage="fp16") ------------------
+def conv2d_f16_act16_res(x_nhwc, packed16, cout, ksize, residual, scale=None, shift=None, flags=0, peak=None):
+    """conv2d_f16_act16 + a torch.float16 residual of the output's shape, added before the ReLU -> y torch.float16 NHWC.  No fused
+    pool / upsample, no CONV_OUT_NCHW."""
+    x, res = _f16(x_nhwc), _f16(residual)
+    b, h, w, cin = (int(v) for v in x.shape)
+    hi, _, exp = _packed_planes("conv2d_f16_act16_res", packed16, cin)
+    if tuple(res.shape) != (b, h, w, cout):
+        raise RuntimeError("conv2d_f16_act16_res: the residual must have the output's shape %s, got %s" % ((b, h, w, cout), tuple(res.shape)))
+    y = torch.empty((b, h, w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv2d_f16_res16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(res), ptr(y), ptr(peak), b, h, w, cin,
+         cout, int(hi.shape[-2]), ksize, 1, flags, stream())
+    return y
+
+
+def im2col_nchw_f16(x_nchw, kh, kw, stride, pad, kpad, peak=None):
+    """im2col_nchw storing torch.float16 rows: the fp32 image rounded (saturating) at the store.  The ResNet stem's shape only."""
+    x = _f32(x_nchw)
+    b, c, h, w = (int(v) for v in x.shape)
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    y = torch.empty((b, ho, wo, kpad), dtype=torch.float16, device=x.device)
+    call("dream_im2col_nchw_f16", ptr(x), ptr(y), ptr(peak), b, c, h, w, kh, kw, stride, pad, kpad, stream())
+    return y
+
+
+def maxpool3s2_f16(x_nhwc):
+    x = _f16(x_nhwc)
+    b, h, w, c = (int(v) for v in x.shape)
+    y = torch.empty((b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=torch.float16, device=x.device)
+    call("dream_maxpool3s2_nhwc_f16", ptr(x), ptr(y), b, h, w, c, stream())
+    return y
+
+
+def subsample2_f16(x):
+    """subsample2 on a torch.float16 tensor (a copy)."""
+    x = _f16(x)
+    b, h, w, c = (int(v) for v in x.shape)
+    y = torch.empty((b, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float16, device=x.device)
+    call("dream_subsample2_nhwc_f16", ptr(x), ptr(y), b, h, w, c, stream())
+    return y
+
+
+def im2col3s2_f16(x):
+    """im2col3s2 on a torch.float16 tensor (a copy, zeros for the padding)."""
+    x = _f16(x)
+    b, h, w, c = (int(v) for v in x.shape)
+    col = torch.empty((b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 9 * c), dtype=torch.float16, device=x.device)
+    call("dream_im2col3s2_nhwc_f16", ptr(x), ptr(col), b, h, w, c, stream())
+    return col
+
+
 # ---- training with the saved activations stored as IEEE half (train_activation_storage="fp16"): the backward's read side -----------
 def conv3x3_wgrad_f16_x16(x_nhwc, dy_nhwc, amax_dy, cout, cin, flags=0):
     """conv3x3_wgrad_f16 with x a torch.float16 tensor that IS the operand (no amax of x, no scale) -> (dW OIHW, dbias [cout])."""

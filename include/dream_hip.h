@@ -355,6 +355,28 @@ int dream_conv3x3_first_nchw_f16(const float *x_nchw, const float *w_oihw, const
 int dream_maxpool2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream);
 /* skip sums (dream/models.py:774-807) on halfs: out = half(clamp(float(a) + float(b))); amax_out as above (not zeroed) */
 int dream_add_f16(const void *a, const void *b, void *out, size_t n, unsigned *amax_out, void *stream);
+/* ---- ResnetSimple with its activations stored as IEEE half (ResnetSimple.inference_activation_storage = "fp16") -------------
+ * The evaluation forward of dream/models.py:139-155 with every tensor between the image and the K belief maps a half NHWC
+ * tensor (a stored value is half(clamp(v, +-65504)), to nearest even); amax_out as above: optional, NOT zeroed, max|v| before
+ * the saturation.  Half tensors are 16-byte aligned.
+ * Bottleneck conv3 + bn3 + identity + ReLU (torchvision Bottleneck via dream/models.py:22-32,145-148): dream_conv2d_f16_nhwc_f16
+ * with a residual [B,H,W,Cout] of halfs (4-byte aligned), y = half(sat(relu(conv * scale + shift + float(residual)))).  A
+ * fused pool / upsample, DREAM_CONV_OUT_NCHW and a null residual are refused. */
+int dream_conv2d_f16_res16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                                    const void *residual, void *y, unsigned *amax_out, int B, int H, int W, int Cin, int Cout,
+                                    int CoutPad, int ksize, int stride, int flags, void *stream);
+/* conv1 (7x7, stride 2, pad 3; dream/models.py:22-24,140) as im2col: dream_im2col_nchw_f32 whose rows are halfs -- the fp32 NCHW
+ * image rounded once, at the store.  Built for that shape only (C 3, 7x7, stride 2, pad 3); Kpad % 8 == 0. */
+int dream_im2col_nchw_f16(const float *x, void *y, unsigned *amax_out, int B, int C, int H, int W, int KH, int KW, int stride,
+                          int pad, int Kpad, void *stream);
+/* nn.MaxPool2d(3, 2, 1) of the stem (dream/models.py:27,143) on halfs: exact, padding never wins.  C % 8 == 0 */
+int dream_maxpool3s2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream);
+/* The pixels the three stride-2 downsample convs read (torchvision Bottleneck.downsample via dream/models.py:29-31,146-148):
+ * y[b,i,j,:] = x[b,2i,2j,:], Ho = (H + 1) / 2 -- dream_subsample2_nhwc_f32 on halfs, a copy.  C % 8 == 0 */
+int dream_subsample2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream);
+/* The patch rows of the three 3x3 stride-2 pad-1 convs (layer2..4 [0].conv2, same call sites): col [B,Ho,Wo,9 C], column
+ * t C + c = tap t = 3 ky + kx of channel c, zeros outside the image -- dream_im2col3s2_nhwc_f32 on halfs, a copy.  C % 8 == 0 */
+int dream_im2col3s2_nhwc_f16(const void *x, void *col, int B, int H, int W, int C, void *stream);
 /* variant selection for benchmarking: -1 = heuristic; otherwise index into the variant table */
 int dream_conv3x3_set_variant(int variant);
 int dream_conv3x3_num_variants(void);
