@@ -93,6 +93,7 @@ class _PackedCache:
 # Inference precisions that run on the fp16 matrix cores -> suffix of their ops (ops.conv2d_<suffix>, ops.conv_transpose4x4s2_<suffix>,
 # ops.conv_transpose3x3s2_<suffix>, ops.pack_conv_weight_<suffix>, ops.pack_convT4x4_weight_<suffix>) and of their packed forms.  Both
 # take the same arguments and thread the same amax side channel; what differs is the arithmetic (csrc/conv_f16x3.hip, csrc/conv_f16.hip).
+# The suffix is the ``family`` of a walk: DreamHourglass._conv_half and ResnetSimple's _EvalAmax look their ops up by it.
 _HALF_OPS = {"fp16x3": "f16x3", "fp16": "f16"}
 
 # The precision switches of DreamHourglass, as data: (attribute, allowed values -- the first is the default --, what any other value
@@ -114,6 +115,17 @@ _SWITCHES = (
 # output / the gradient with respect to whose output a training pass stores as half; ``half_storage``: the walk writes the
 # half-storage peak scalar (half_storage_peak()).
 _Walk = collections.namedtuple("_Walk", "family act16 ksplit half_train store16 grad16 half_storage")
+
+# ... and ResnetSimple's, in the order ResnetSimple._resolve_switches checks them: (attribute, allowed values, needs, the pass that reads
+# it).  An unknown value is refused in both passes; ``precision`` is not checked (None): a value outside _HALF_OPS takes the fp32 walk.
+_RESNET_SWITCHES = (
+    ("precision", None, (), "inference"),
+    ("train_gemm_precision", ("fp32", "fp16"), (("bn_fusion", True), ("conv1x1_algorithm", "gemm")), "training"),
+    ("inference_activation_storage", ("fp32", "fp16"), (("precision", "fp16"),), "inference"),
+)
+# ``family``: as in _Walk; ``act16``: the evaluation walk stores its activations as half; ``train16``: the covered units of a training
+# pass (ResnetSimple._half_unit) run in half precision.
+_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16")
 
 
 class _PeakScalar:
@@ -1414,10 +1426,151 @@ class _MultiStageFunction(torch.autograd.Function):
         return (None, None) + tuple(_reduced(reducer, grads))
 
 
+# ---- the three arithmetics of ResnetSimple.run_forward: each supplies stem, pool, conv (+ folded BatchNorm) (+ residual) (+ ReLU), stage (a
+# decoder stage) and head (-> the K belief maps, NCHW, fp32) on an activation value that the walk only hands from one operation to the next
+class _EvalFp32:
+    """fp32 on the MFMA conv, Winograd and GEMM kernels.  The value: the NHWC tensor."""
+
+    def __init__(self, net):
+        self.n = net
+
+    def stem(self, x):
+        # 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused (the rows die with this call, before the pool)
+        col = ops.im2col_nchw(x, 7, 7, 2, 3, self.n.STEM_COLS["g0e"])           # (= STEM_COLS["w"])
+        s1, t1 = self.n._fold("bn1", self.n.bn1)
+        if self.n.stem_on_gemm and self.n.conv1x1_algorithm == "gemm" and ops.conv1x1_applies(col, 64):
+            # Round 6: the im2col rows (K = 160) through the 1x1 GEMM kernel (the 1-tap direct kernel ran them at 69 TFLOP/s; this is a
+            # stream of 0.8 GB in, 0.3 GB out at 32 frames)
+            return ops.conv1x1(col, self.n._stem_weight("g0e"), 64, s1, t1, None, CONV_RELU)
+        return ops.conv2d(col, self.n._stem_weight("w"), 64, 1, 1, s1, t1, None, CONV_RELU)
+
+    def pool(self, y):
+        return ops.maxpool3s2(y)
+
+    def conv(self, name, x, conv, bn, relu, residual=None):
+        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
+        scale, shift = self.n._fold(name, bn, conv.bias)
+        cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
+        flags = CONV_RELU if relu else 0
+        if k == 3 and stride == 1 and self.n.conv_algorithm == "winograd" and cin % 16 == 0 and cout >= 64:
+            # the stride-1 3x3 convs of the bottlenecks: Winograd F(2x2,3x3) with the folded BatchNorm in the epilogue
+            tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), cin, cout, int(x.shape[0]))
+            u, rows = self.n._wino(name, conv, 0, tile)
+            return ops.conv3x3_winograd_tile(tile, x, u, rows, scale, shift, residual, flags)
+        if self.n._gemm1x1(conv, x):
+            # the 1x1 convs of the bottlenecks: a plain GEMM without LDS (gemm1x1.hip), folded BatchNorm / residual / ReLU fused
+            packed, rows = self.n._g(name, conv, 0)
+            return ops.conv1x1(x, packed, rows, scale, shift, residual, flags)
+        if self.n.ds_on_gemm and k == 1 and stride == 2 and self.n.conv1x1_algorithm == "gemm" and cin == int(x.shape[3]) and cin % 64 == 0:
+            # the stride-2 downsample convs on the GEMM over the pixels they read (as in training: _unit)
+            xs = ops.subsample2(x)
+            if ops.conv1x1_applies(xs, cout):
+                packed, rows = self.n._g(name, conv, 0)
+                return ops.conv1x1(xs, packed, rows, scale, shift, residual, flags)
+        packed, rows, _ = self.n._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
+        return ops.conv2d(x, packed, rows, k, stride, scale, shift, residual, flags)
+
+    def stage(self, name, m, bn, y):
+        scale, shift = self.n._fold(name, bn, m.bias)
+        return self.n._convT_forward(name, m, y, scale, shift, CONV_RELU)
+
+    def head(self, name, m, y):
+        packed, rows, _ = self.n._cached(("w", name), [m.weight], lambda: ops.pack_conv_weight(m.weight.detach(), 0))
+        return ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
+
+
+class _EvalAmax:
+    """The split- / half-precision conv kernels of _HALF_OPS suffix ``sfx`` ("f16x3" | "f16"): one class for both.  The value: (the fp32
+    NHWC tensor, its amax).  The six stride-2 convs of the trunk stay on the fp32 kernel, which publishes max|y| all the same."""
+
+    def __init__(self, net, sfx):
+        self.n, self.sfx = net, sfx
+        self.pack, self.conv2d = getattr(ops, "pack_conv_weight_" + sfx), getattr(ops, "conv2d_" + sfx)
+
+    def stem(self, x):
+        col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
+        amax = ops.absmax(x)                               # im2col only rearranges (and zero-pads) the image
+        w1 = self.n._cached(("w" + self.sfx, "conv1"), [self.n.conv1.weight], lambda: self.pack(self.n.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        s1, t1 = self.n._fold("bn1", self.n.bn1)
+        return self.conv2d(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
+
+    def pool(self, ya):
+        return ops.maxpool3s2(ya[0]), ya[1]                # pooling cannot raise the maximum: amax carries over
+
+    def conv(self, name, xa, conv, bn, relu, residual=None):
+        x, amax = xa
+        residual = residual and residual[0]                # (its amax -- the block input's or the .ds branch's -- is dropped)
+        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
+        scale, shift = self.n._fold(name, bn, conv.bias)
+        flags = CONV_RELU if relu else 0
+        if stride != 1:
+            packed, rows, _ = self.n._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
+            return ops.conv2d_amax(x, packed, rows, k, stride, scale, shift, residual, flags)
+        p16 = self.n._cached(("w" + self.sfx, name), [conv.weight], lambda: self.pack(conv.weight.detach(), 0))
+        return self.conv2d(x, amax, p16, p16[3], k, scale, shift, residual, flags)
+
+    def stage(self, name, m, bn, ya):
+        p16 = self.n._cached(("w" + self.sfx, name), [m.weight], lambda: getattr(ops, "pack_convT4x4_weight_" + self.sfx)(m.weight.detach()))
+        scale, shift = self.n._fold(name, bn, m.bias)
+        return getattr(ops, "conv_transpose4x4s2_" + self.sfx)(ya[0], ya[1], p16, p16[3], scale, shift, CONV_RELU)
+
+    def head(self, name, m, ya):
+        p16 = self.n._cached(("w" + self.sfx, name), [m.weight], lambda: self.pack(m.weight.detach(), 0))
+        return self.conv2d(ya[0], ya[1], p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)[0]
+
+
+class _EvalAct16:
+    """inference_activation_storage="fp16" (DESIGN.md 4.8k): the "f16" kernels with every tensor between the fp32 image and the fp32
+    belief maps stored as IEEE half.  The value: the torch.float16 NHWC tensor; every half-writing launch atomicMaxes max|v| before the
+    saturation into ``peak``, the pass's one scalar (ResnetSimple.half_storage_peak())."""
+
+    def __init__(self, net, peak):
+        self.n, self.peak = net, peak
+
+    def stem(self, x):
+        col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=self.peak)
+        w1 = self.n._cached(("wf16", "conv1"), [self.n.conv1.weight], lambda: ops.pack_conv_weight_f16(self.n.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        s1, t1 = self.n._fold("bn1", self.n.bn1)
+        return ops.conv2d_f16_act16(col, w1, 64, 1, s1, t1, CONV_RELU, peak=self.peak)
+
+    def pool(self, y):
+        return ops.maxpool3s2_f16(y)
+
+    def conv(self, name, x, conv, bn, relu, residual=None):
+        """A stride-2 conv is a gather -- the pixels a 1x1 conv reads, the patch rows [B,Ho,Wo,9 Cin] of a 3x3 one -- followed by the
+        1-tap conv over the gathered rows: the form training runs in fp32 (_unit: ``sub2``, ``col3``), here on the fp16 matrix cores like
+        every other conv.  The residual is a stored half: the block input or the downsample result."""
+        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
+        scale, shift = self.n._fold(name, bn, conv.bias)
+        cout = int(conv.weight.shape[0])
+        if stride == 2 and k == 3:
+            x, k = ops.im2col3s2_f16(x), 1
+            p16 = self.n._cached(("wf16col3", name), [conv.weight], lambda: ops.pack_conv_weight_f16(
+                conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 0))
+        else:
+            if stride == 2:
+                x = ops.subsample2_f16(x)
+            p16 = self.n._cached(("wf16", name), [conv.weight], lambda: ops.pack_conv_weight_f16(conv.weight.detach(), 0))
+        flags = CONV_RELU if relu else 0
+        if residual is not None:
+            return ops.conv2d_f16_act16_res(x, p16, cout, k, residual, scale, shift, flags, peak=self.peak)
+        return ops.conv2d_f16_act16(x, p16, cout, k, scale, shift, flags, peak=self.peak)
+
+    def stage(self, name, m, bn, y):
+        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
+        scale, shift = self.n._fold(name, bn, m.bias)
+        return ops.conv_transpose4x4s2_f16_act16(y, p16, p16[3], scale, shift, CONV_RELU, peak=self.peak)
+
+    def head(self, name, m, y):
+        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
+        return ops.conv2d_f16_act16(y, p16, p16[3], 1, None, m.bias.detach(), CONV_OUT_NCHW)
+
+
 class ResnetSimple(nn.Module):
     """The reference's ResnetSimple (models.py:17-155): torchvision ResNet101 trunk + 4 (or 5) x
     [ConvTranspose2d(4,2,1) -> BatchNorm -> ReLU] + 1x1 conv to K maps; identical ``state_dict()``.
-    Evaluation mode runs entirely on the MFMA conv kernel: 1x1 / 3x3 / strided convs with the eval-mode
+    Evaluation mode is ONE walk of the network (run_forward) over the arithmetic the switches resolve to (_resolve_switches ->
+    _EvalFp32 | _EvalAmax | _EvalAct16): 1x1 / 3x3 / strided convs with the eval-mode
     BatchNorm folded into the epilogue (y = conv*scale + shift), the Bottleneck residual add + ReLU fused
     into the third conv, the 7x7 stem as im2col + 1-tap conv, the 4x4 transposed convs by sub-pixel
     decomposition.  Training mode uses batch-statistics BatchNorm kernels (csrc/bn.hip) between the convs and
@@ -1478,13 +1631,13 @@ class ResnetSimple(nn.Module):
         # Training: "fp16" = the 1x1 convs that run on the GEMM kernel with their BatchNorm fused (_half_unit: conv1 / conv3 / the downsample
         # convs of the Bottlenecks and the patch-row form of layer4.0.conv2) multiply on the fp16 matrix cores -- forward, data gradient and
         # weight gradient (csrc/gemm1x1_f16.hip).  Tensors, BatchNorm statistics and the optimizer stay fp32; needs
-        # bn_fusion and conv1x1_algorithm="gemm".  Read once per forward pass (_resolve_train_gemm_precision).  Not spelled ``train_precision``:
+        # bn_fusion and conv1x1_algorithm="gemm".  Read once per forward pass (_resolve_switches -> _ResnetWalk.train16).  Not spelled ``train_precision``:
         # that name is DreamHourglass's switch (its plain 3x3 convs), which this class exposes as fixed to "fp32" and keeps refusing.
         self.train_gemm_precision = "fp32"
         # Inference, with precision="fp16": "fp16" = every tensor between the image and the K belief maps lives in HBM as IEEE half NHWC --
         # half(clamp(v, +-65504)), no per-tensor scale; the stored half IS the consumer's MFMA operand -- and the six stride-2 convs run on
-        # the fp16 matrix cores over gathered pixels / patch rows (_walk_act16).  "fp32" (default): today's walk.  Read once per
-        # evaluation forward (_resolve_inference_activation_storage); a training pass ignores it.  See half_storage_peak().  Not spelled
+        # the fp16 matrix cores over gathered pixels / patch rows (_EvalAct16).  "fp32" (default): today's walk.  Read once per
+        # evaluation forward (_resolve_switches -> _ResnetWalk.act16); a training pass ignores it.  See half_storage_peak().  Not spelled
         # ``activation_storage``: that name is DreamHourglass's switch, which this class exposes as fixed to "fp32" and keeps refusing.
         self.inference_activation_storage = "fp32"
         self._storage_peak = _PeakScalar("half_storage_peak(): no forward with inference_activation_storage=\"fp16\" has run")
@@ -1740,18 +1893,24 @@ class ResnetSimple(nn.Module):
             for key, tag in tags.items():
                 self._cache[key] = (tag, self._cache[key][1])
 
-    def _resolve_train_gemm_precision(self, training):
-        """Reads ``train_gemm_precision`` once for this pass -> do the covered units of a training pass run in half precision?  ValueError
-        for an unknown value (both passes) and, in a training pass, for "fp16" without the switches its units are built on."""
-        tp = self.train_gemm_precision
-        if tp not in ("fp32", "fp16"):
-            raise ValueError("unknown train_gemm_precision %r (\"fp32\" or \"fp16\")" % (tp,))
-        half = training and tp == "fp16"
-        if half and not (self.bn_fusion and self.conv1x1_algorithm == "gemm"):
-            raise ValueError("train_gemm_precision=\"fp16\" needs bn_fusion and conv1x1_algorithm=\"gemm\" (they are %r and %r)"
-                             % (self.bn_fusion, self.conv1x1_algorithm))
-        self._train16 = half
-        return half
+    def _resolve_switches(self, training):
+        """Reads the precision switches (_RESNET_SWITCHES), once per forward -> the _ResnetWalk of this pass; raises ValueError for an
+        unknown value (both passes) and, in the pass that reads the switch, for a value whose needs are not met."""
+        this_pass, read = "training" if training else "inference", {}
+        for name, allowed, needs, reader in _RESNET_SWITCHES:
+            value = read[name] = getattr(self, name)
+            if allowed is None:
+                continue
+            if value not in allowed:
+                raise ValueError("unknown %s %r (\"%s\" or \"%s\")" % ((name, value) + allowed))
+            if reader != this_pass:                    # the other pass ignores it
+                read[name] = allowed[0]
+            elif value != allowed[0] and any(getattr(self, n) != v for n, v in needs):
+                are = tuple(getattr(self, n) for n, _ in needs)
+                raise ValueError("%s=\"%s\" needs %s (%s)" % (name, value, " and ".join(n if v is True else "%s=\"%s\"" % (n, v) for n, v in needs),
+                                                            "%s is %r" % (needs[0][0], are[0]) if len(are) == 1 else "they are %r and %r" % are))
+        return _ResnetWalk(_HALF_OPS.get(read["precision"], "fp32"), read["inference_activation_storage"] == "fp16",
+                           read["train_gemm_precision"] == "fp16")
 
     @staticmethod
     def _half_unit(rec):
@@ -1772,29 +1931,6 @@ class ResnetSimple(nn.Module):
             self._amax_pos = 0
         self._amax_pos += 1
         return buf[self._amax_pos - 1:self._amax_pos]
-
-    def _conv_bn(self, name, x, conv, bn, relu, residual=None):
-        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
-        scale, shift = self._fold(name, bn, conv.bias)
-        cout, cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
-        flags = CONV_RELU if relu else 0
-        if k == 3 and stride == 1 and self.conv_algorithm == "winograd" and cin % 16 == 0 and cout >= 64:
-            # the stride-1 3x3 convs of the bottlenecks: Winograd F(2x2,3x3) with the folded BatchNorm in the epilogue
-            tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), cin, cout, int(x.shape[0]))
-            u, rows = self._wino(name, conv, 0, tile)
-            return ops.conv3x3_winograd_tile(tile, x, u, rows, scale, shift, residual, flags)
-        if self._gemm1x1(conv, x):
-            # the 1x1 convs of the bottlenecks: a plain GEMM without LDS (gemm1x1.hip), folded BatchNorm / residual / ReLU fused
-            packed, rows = self._g(name, conv, 0)
-            return ops.conv1x1(x, packed, rows, scale, shift, residual, flags)
-        if self.ds_on_gemm and k == 1 and stride == 2 and self.conv1x1_algorithm == "gemm" and cin == int(x.shape[3]) and cin % 64 == 0:
-            # the stride-2 downsample convs on the GEMM over the pixels they read (as in training: _unit)
-            xs = ops.subsample2(x)
-            if ops.conv1x1_applies(xs, cout):
-                packed, rows = self._g(name, conv, 0)
-                return ops.conv1x1(xs, packed, rows, scale, shift, residual, flags)
-        packed, rows, _ = self._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
-        return ops.conv2d(x, packed, rows, k, stride, scale, shift, residual, flags)
 
     def _convT_gemm(self, name, m, y):
         """Does this transposed conv run as one 1x1 GEMM (N = 16 Cout) + a gather (small maps: _convT_forward)?  -> packed weight or None."""
@@ -1823,31 +1959,6 @@ class ResnetSimple(nn.Module):
         packed, rows = self._cached(("w", name), [m.weight], lambda: ops.pack_convT4x4_weight(m.weight.detach()))
         return ops.conv_transpose4x4s2(y, packed, rows, scale, shift, flags)
 
-    # ---- inference on the split- / half-precision conv kernels (strided convs stay on the fp32 kernel) ------------------
-    def _conv_bn16(self, sfx, name, x, amax, conv, bn, relu, residual=None):
-        """-> (y, amax_y).  Stride-1 1x1 / 3x3 convs run on the kernel of _HALF_OPS suffix ``sfx``; the six stride-2 convs of the trunk
-        run on the fp32 kernel, which publishes max|y| all the same."""
-        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
-        scale, shift = self._fold(name, bn, conv.bias)
-        flags = CONV_RELU if relu else 0
-        if stride != 1:
-            packed, rows, _ = self._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
-            return ops.conv2d_amax(x, packed, rows, k, stride, scale, shift, residual, flags)
-        p16 = self._cached(("w" + sfx, name), [conv.weight], lambda: getattr(ops, "pack_conv_weight_" + sfx)(conv.weight.detach(), 0))
-        return getattr(ops, "conv2d_" + sfx)(x, amax, p16, p16[3], k, scale, shift, residual, flags)
-
-    # ---- ... with the activations stored as IEEE half (inference_activation_storage="fp16"; DESIGN.md 4.8k) -----------------------
-    def _resolve_inference_activation_storage(self, training):
-        """Reads ``inference_activation_storage`` once for this pass -> does this evaluation forward store its activations as half?
-        ValueError for an unknown value (both passes) and, in an evaluation pass, for "fp16" without precision="fp16"."""
-        st = self.inference_activation_storage
-        if st not in ("fp32", "fp16"):
-            raise ValueError("unknown inference_activation_storage %r (\"fp32\" or \"fp16\")" % (st,))
-        half = not training and st == "fp16"
-        if half and self.precision != "fp16":
-            raise ValueError("inference_activation_storage=\"fp16\" needs precision=\"fp16\" (precision is %r)" % (self.precision,))
-        return half
-
     def half_storage_peak(self):
         """The largest |value|, before saturation, that any launch of the last forward with inference_activation_storage="fp16" wanted to
         store as a half (this module's own forward; with ``gpu_ids`` ask the wrapper, DreamDataParallel.half_storage_peak(), which takes
@@ -1855,122 +1966,27 @@ class ResnetSimple(nn.Module):
         is the mode's only host synchronisation, and happens only here."""
         return self._storage_peak.read()
 
-    def _conv_bn_act16(self, name, x, conv, bn, relu, peak, residual=None):
-        """One conv + folded BatchNorm (+ half residual) (+ ReLU) of the half-storage walk -> y, torch.float16 NHWC.  A stride-2 conv is a
-        gather -- the pixels a 1x1 conv reads, the patch rows [B,Ho,Wo,9 Cin] of a 3x3 one -- followed by the 1-tap conv over the
-        gathered rows: the form training runs in fp32 (_unit: ``sub2``, ``col3``), here on the fp16 matrix cores like every other conv."""
-        k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
-        scale, shift = self._fold(name, bn, conv.bias)
-        cout = int(conv.weight.shape[0])
-        if stride == 2 and k == 3:
-            x, k = ops.im2col3s2_f16(x), 1
-            p16 = self._cached(("wf16col3", name), [conv.weight], lambda: ops.pack_conv_weight_f16(
-                conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 0))
-        else:
-            if stride == 2:
-                x = ops.subsample2_f16(x)
-            p16 = self._cached(("wf16", name), [conv.weight], lambda: ops.pack_conv_weight_f16(conv.weight.detach(), 0))
-        flags = CONV_RELU if relu else 0
-        if residual is not None:
-            return ops.conv2d_f16_act16_res(x, p16, cout, k, residual, scale, shift, flags, peak=peak)
-        return ops.conv2d_f16_act16(x, p16, cout, k, scale, shift, flags, peak=peak)
-
-    def _bottleneck_act16(self, name, blk, y, peak):
-        """One Bottleneck of the half-storage walk: the downsample result is stored as half and is conv3's residual."""
+    # ---- the evaluation walk: one topology over the arithmetic the switches resolve to (_EvalFp32, _EvalAmax, _EvalAct16) -----------
+    def _bottleneck(self, a, name, blk, y):
+        """One Bottleneck on arithmetic ``a``: the downsample result, where there is one, is conv3's residual."""
         idt = y
         if hasattr(blk, "downsample"):
-            idt = self._conv_bn_act16(name + ".ds", y, blk.downsample[0], blk.downsample[1], False, peak)
-        o = self._conv_bn_act16(name + ".1", y, blk.conv1, blk.bn1, True, peak)
-        o = self._conv_bn_act16(name + ".2", o, blk.conv2, blk.bn2, True, peak)
-        return self._conv_bn_act16(name + ".3", o, blk.conv3, blk.bn3, True, peak, residual=idt)
-
-    def _walk_act16(self, x):
-        """run_forward_half("f16") with every tensor between the fp32 image and the fp32 belief maps stored as half; every half-writing
-        launch atomicMaxes max|v| before the saturation into the module's peak scalar (half_storage_peak())."""
-        peak = self._storage_peak.zeroed(x.device)
-        col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=peak)
-        w1 = self._cached(("wf16", "conv1"), [self.conv1.weight],
-                          lambda: ops.pack_conv_weight_f16(self.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
-        s1, t1 = self._fold("bn1", self.bn1)
-        y = ops.conv2d_f16_act16(col, w1, 64, 1, s1, t1, CONV_RELU, peak=peak)
-        del col
-        y = ops.maxpool3s2_f16(y)
-        for name, blk in self._trunk():
-            y = self._bottleneck_act16(name, blk, y, peak)
-        for name, m, bn in self._decoder():
-            if bn is not None:
-                p16 = self._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
-                scale, shift = self._fold(name, bn, m.bias)
-                y = ops.conv_transpose4x4s2_f16_act16(y, p16, p16[3], scale, shift, CONV_RELU, peak=peak)
-            else:                                           # the K belief maps: NCHW, fp32
-                p16 = self._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
-                y = ops.conv2d_f16_act16(y, p16, p16[3], 1, None, m.bias.detach(), CONV_OUT_NCHW)
-        return y
-
-    def run_forward_half(self, x, sfx, act16=False):
-        """The evaluation forward on the ops of _HALF_OPS suffix ``sfx`` ("f16x3" | "f16"): one walk for both.  ``act16`` ("f16" only):
-        the walk with half-stored activations (_walk_act16)."""
-        if act16:
-            return self._walk_act16(x)
-        pack, packT = getattr(ops, "pack_conv_weight_" + sfx), getattr(ops, "pack_convT4x4_weight_" + sfx)
-        conv2d, convT = getattr(ops, "conv2d_" + sfx), getattr(ops, "conv_transpose4x4s2_" + sfx)
-        col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
-        amax = ops.absmax(x)                               # im2col only rearranges (and zero-pads) the image
-        w1 = self._cached(("w" + sfx, "conv1"), [self.conv1.weight],
-                          lambda: pack(self.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
-        s1, t1 = self._fold("bn1", self.bn1)
-        y, amax = conv2d(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
-        del col
-        y = ops.maxpool3s2(y)                              # pooling cannot raise the maximum: amax carries over
-        for name, blk in self._trunk():
-            idt = y
-            if hasattr(blk, "downsample"):
-                idt, _ = self._conv_bn16(sfx, name + ".ds", y, amax, blk.downsample[0], blk.downsample[1], relu=False)
-            o, a1 = self._conv_bn16(sfx, name + ".1", y, amax, blk.conv1, blk.bn1, relu=True)
-            o, a2 = self._conv_bn16(sfx, name + ".2", o, a1, blk.conv2, blk.bn2, relu=True)
-            y, amax = self._conv_bn16(sfx, name + ".3", o, a2, blk.conv3, blk.bn3, relu=True, residual=idt)
-        for name, m, bn in self._decoder():
-            if bn is not None:
-                p16 = self._cached(("w" + sfx, name), [m.weight], lambda: packT(m.weight.detach()))
-                scale, shift = self._fold(name, bn, m.bias)
-                y, amax = convT(y, amax, p16, p16[3], scale, shift, CONV_RELU)
-            else:
-                p16 = self._cached(("w" + sfx, name), [m.weight], lambda: pack(m.weight.detach(), 0))
-                y, _ = conv2d(y, amax, p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)
-        return y
+            idt = a.conv(name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
+        o = a.conv(name + ".1", y, blk.conv1, blk.bn1, relu=True)
+        o = a.conv(name + ".2", o, blk.conv2, blk.bn2, relu=True)
+        return a.conv(name + ".3", o, blk.conv3, blk.bn3, relu=True, residual=idt)
 
     def run_forward(self, x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
-        self._resolve_train_gemm_precision(False)
-        act16 = self._resolve_inference_activation_storage(False)
-        if self.precision in _HALF_OPS:
-            return self.run_forward_half(x, _HALF_OPS[self.precision], act16)
-        # stem: 7x7 s2 conv as im2col (K = 147 -> 160) + 1-tap MFMA conv, BN+ReLU fused; then MaxPool(3,2,1)
-        col = ops.im2col_nchw(x, 7, 7, 2, 3, self.STEM_COLS["g0e"])           # (= STEM_COLS["w"])
-        s1, t1 = self._fold("bn1", self.bn1)
-        if self.stem_on_gemm and self.conv1x1_algorithm == "gemm" and ops.conv1x1_applies(col, 64):
-            # Round 6: the im2col rows (K = 160) through the 1x1 GEMM kernel (the 1-tap direct kernel ran them at 69 TFLOP/s; this is a
-            # stream of 0.8 GB in, 0.3 GB out at 32 frames)
-            y = ops.conv1x1(col, self._stem_weight("g0e"), 64, s1, t1, None, CONV_RELU)
-        else:
-            y = ops.conv2d(col, self._stem_weight("w"), 64, 1, 1, s1, t1, None, CONV_RELU)
-        del col
-        y = ops.maxpool3s2(y)
+        walk = self._resolve_switches(False)
+        a = (_EvalAct16(self, self._storage_peak.zeroed(x.device)) if walk.act16 else          # (zeroed once per pass, before its first launch)
+             _EvalFp32(self) if walk.family == "fp32" else _EvalAmax(self, walk.family))
+        y = a.pool(a.stem(x))                               # then MaxPool(3,2,1)
         for name, blk in self._trunk():
-            idt = y
-            if hasattr(blk, "downsample"):
-                idt = self._conv_bn(name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False)
-            o = self._conv_bn(name + ".1", y, blk.conv1, blk.bn1, relu=True)
-            o = self._conv_bn(name + ".2", o, blk.conv2, blk.bn2, relu=True)
-            y = self._conv_bn(name + ".3", o, blk.conv3, blk.bn3, relu=True, residual=idt)
+            y = self._bottleneck(a, name, blk, y)
         for name, m, bn in self._decoder():
-            if bn is not None:
-                scale, shift = self._fold(name, bn, m.bias)
-                y = self._convT_forward(name, m, y, scale, shift, CONV_RELU)
-            else:                                           # final 1x1 conv -> K belief maps, NCHW
-                packed, rows, _ = self._cached(("w", name), [m.weight], lambda: ops.pack_conv_weight(m.weight.detach(), 0))
-                y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
+            y = a.stage(name, m, bn, y) if bn is not None else a.head(name, m, y)
         return y
 
     # ---- training: train-mode BatchNorm (batch statistics), activations kept for the backward plan --------
@@ -2013,10 +2029,11 @@ class ResnetSimple(nn.Module):
         if materialize:
             rec["y"] = ops.bn_apply_ab(rec["z"], rec["ab"], residual, rec["relu"])
 
-    def _unit(self, tape, name, x, conv, bn, relu, residual=None, src=None, pre=False, materialize=True):
+    def _unit(self, tape, name, x, conv, bn, relu, residual=None, src=None, pre=False, materialize=True, train16=False):
         """conv -> BatchNorm(batch statistics) (+ residual) (ReLU) -> the tape record (output: rec["y"]).  ``src``: the record of the unit
         that produced the conv's input (None: no BatchNorm unit did).  ``x``: the input tensor, src["y"] -- or, with ``pre``, src's
-        un-normalised output z, whose BatchNorm + ReLU this conv applies while loading.  ``materialize``: see _bn_fwd."""
+        un-normalised output z, whose BatchNorm + ReLU this conv applies while loading.  ``materialize``: see _bn_fwd.  ``train16``: what the
+        pass resolved (_ResnetWalk); taped as rec["f16"], the one thing the backward reads of it."""
         fused = self.bn_fusion
         k, stride = int(conv.kernel_size[0]), int(conv.stride[0])
         bias = conv.bias.detach() if conv.bias is not None else None
@@ -2041,7 +2058,7 @@ class ResnetSimple(nn.Module):
         rec = dict(kind="conv", name=name, conv=conv, bn=bn, relu=relu, x=x, src=src, pre=pre, k=k, stride=stride,
                    has_res=residual is not None, y=None, ab=None, sub2=sub2, col3=col3, wino=self._wino_train(conv), f16=False)
         if col3 is not None or self._gemm1x1(conv, x, k, stride):
-            rec["f16"] = fused and self.__dict__.get("_train16", False)
+            rec["f16"] = fused and train16
             if self._half_unit(rec):
                 p16 = self._g16(name, conv, 0, col3 is not None)
                 rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn_f16(
@@ -2087,8 +2104,7 @@ class ResnetSimple(nn.Module):
     def run_forward_train(self, x):
         """-> (belief maps NCHW, tape)."""
         fused = self.bn_fusion
-        half = self._resolve_train_gemm_precision(True)
-        self._resolve_inference_activation_storage(True)         # (an inference switch: only an unknown value is refused here)
+        half = self._resolve_switches(True).train16
         self._repack_weights(split=fused)
         if half:
             self._repack_half_weights()
@@ -2119,11 +2135,11 @@ class ResnetSimple(nn.Module):
         for name, blk in self._trunk():
             ds, idt = None, y
             if hasattr(blk, "downsample"):
-                ds = self._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False, src=src)
+                ds = self._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False, src=src, train16=half)
                 idt = ds["y"]
-            r1 = self._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True, src=src)
+            r1 = self._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True, src=src, train16=half)
             # fused: conv2's BatchNorm + ReLU is applied by conv3's loader when conv3 runs on the GEMM kernel (always, for ResNet-101)
-            r2 = self._unit(tape, name + ".2", r1["y"], blk.conv2, blk.bn2, relu=True, src=r1, materialize=not fused)
+            r2 = self._unit(tape, name + ".2", r1["y"], blk.conv2, blk.bn2, relu=True, src=r1, materialize=not fused, train16=half)
             pre = False
             if fused:
                 # ... and when the BACKWARD GEMM applies too: conv3's data gradient (conv1x1_bwd_bnmask) reads dz3, which has 4x the
@@ -2134,7 +2150,7 @@ class ResnetSimple(nn.Module):
                 pre = self._gemm1x1(blk.conv3, z2) and dz3_fits
                 if not pre:
                     r2["y"] = ops.bn_apply_ab(z2, r2["ab"], None, True)
-            src = self._unit(tape, name + ".3", r2["z"] if pre else r2["y"], blk.conv3, blk.bn3, relu=True, residual=idt, src=r2, pre=pre)
+            src = self._unit(tape, name + ".3", r2["z"] if pre else r2["y"], blk.conv3, blk.bn3, relu=True, residual=idt, src=r2, pre=pre, train16=half)
             # the Bottleneck, unwound as one by the backward: its units (recorded above) and the record whose output is its input
             tape.append(dict(kind="block", name=name, ds=ds, u1=r1, u2=r2, u3=src, src=r1["src"]))
             y = src["y"]

@@ -121,18 +121,18 @@ def device_block(net, name, x, gy, train_gemm_precision):
     incoming gradient -> ({parameter name | "dx": gradient}, the 3x3 conv's (input, output))."""
     blk = dict(net._trunk())[name]
     net.train_gemm_precision = train_gemm_precision
-    net._resolve_train_gemm_precision(True)
+    half = net._resolve_switches(True).train16
     net._ctr_pos = net._amax_pos = 0
     tape = []
     y = ops.nchw_to_nhwc(x)
     ds, idt = None, y
     if hasattr(blk, "downsample"):
-        ds = net._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False, src=None)
+        ds = net._unit(tape, name + ".ds", y, blk.downsample[0], blk.downsample[1], relu=False, src=None, train16=half)
         idt = ds["y"]
-    r1 = net._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True, src=None)
-    r2 = net._unit(tape, name + ".2", r1["y"], blk.conv2, blk.bn2, relu=True, src=r1, materialize=False)
+    r1 = net._unit(tape, name + ".1", y, blk.conv1, blk.bn1, relu=True, src=None, train16=half)
+    r2 = net._unit(tape, name + ".2", r1["y"], blk.conv2, blk.bn2, relu=True, src=r1, materialize=False, train16=half)
     assert net._gemm1x1(blk.conv3, r2["z"])
-    r3 = net._unit(tape, name + ".3", r2["z"], blk.conv3, blk.bn3, relu=True, residual=idt, src=r2, pre=True)
+    r3 = net._unit(tape, name + ".3", r2["z"], blk.conv3, blk.bn3, relu=True, residual=idt, src=r2, pre=True, train16=half)
     rec = dict(kind="block", name=name, ds=ds, u1=r1, u2=r2, u3=r3, src=None)
     bw = dict(grads=models._GradDict(None), side=None, reducer=None, grad_out=None)
     dx = net._bwd_block(rec, ops.nchw_to_nhwc(gy), bw)
@@ -170,10 +170,7 @@ def check_block(dev, name):
         # the Winograd 3x3 conv is not covered: on the fp32 block's own input its launch is the fp32 launch, bit for bit (its input in
         # the fp16 block differs, so the conv is run again on the fp32 block's input with the switch on)
         blk = dict(net._trunk())[name]
-        net.train_gemm_precision = "fp16"
-        net._resolve_train_gemm_precision(True)
-        again = net._unit([], name + ".2", pc.to(dev, a32), blk.conv2, blk.bn2, relu=True, src=None, materialize=False)["z"].cpu()
-        net.train_gemm_precision = "fp32"
+        again = net._unit([], name + ".2", pc.to(dev, a32), blk.conv2, blk.bn2, relu=True, src=None, materialize=False, train16=True)["z"].cpu()
         assert torch.equal(again, z32), name
 
 

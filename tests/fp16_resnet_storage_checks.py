@@ -140,7 +140,7 @@ def check_gathers_and_pool(dev):
 
 @functools.lru_cache(maxsize=None)
 def _host(dev):
-    """A ResnetSimple whose walk helpers (_conv_bn_act16, _bottleneck_act16) the launch checks borrow; its own layers are not run."""
+    """A ResnetSimple whose half-storage arithmetic (models._EvalAct16) and block step (_bottleneck) the launch checks borrow; its own layers are not run."""
     return models.ResnetSimple(7, pretrained=False).eval()
 
 
@@ -172,7 +172,7 @@ def check_strided_conv(dev, B, H, W, Cin, Cout, k, seed=0):
     name = "check.s2.%d.%d.%d.%d" % (Cin, Cout, k, seed)
     peak = ops.new_amax(conv.weight.device)
     with torch.no_grad():
-        y16 = net._conv_bn_act16(name, pc.to(dev, pc._nhwc(x16)), conv, bn, False, peak)
+        y16 = models._EvalAct16(net, peak).conv(name, pc.to(dev, pc._nhwc(x16)), conv, bn, False)
         scale, shift = _folded(net, name, bn)
     ref = F.conv2d(x16.double(), fc.q(conv.weight.detach().cpu()).double(), None, stride=2, padding=k // 2) * scale + shift
     what = ("stride 2", B, H, W, Cin, Cout, k)
@@ -216,7 +216,7 @@ def block_oracle(net, name, blk, x16):
 
 
 def check_bottleneck(dev, seed=0):
-    """Bottleneck(64, 32, stride 2, downsample) on 2 x 9 x 12 through ResnetSimple._bottleneck_act16."""
+    """Bottleneck(64, 32, stride 2, downsample) on 2 x 9 x 12 through the walk's block step on the half-storage arithmetic."""
     g = torch.Generator().manual_seed(seed)
     net = _host(dev)
     ds = nn.Sequential(nn.Conv2d(64, 128, 1, stride=2, bias=False), nn.BatchNorm2d(128))
@@ -232,7 +232,7 @@ def check_bottleneck(dev, seed=0):
     name = "check.block.%d" % seed
     peak = ops.new_amax(blk.conv1.weight.device)
     with torch.no_grad():
-        y16 = net._bottleneck_act16(name, blk, pc.to(dev, pc._nhwc(x16)), peak)
+        y16 = net._bottleneck(models._EvalAct16(net, peak), name, blk, pc.to(dev, pc._nhwc(x16)))
         ref, bound = block_oracle(net, name, blk, x16)
     assert y16.dtype == torch.float16 and tuple(y16.shape) == (2, 5, 6, 128)
     got = y16.cpu().permute(0, 3, 1, 2).double()

@@ -81,13 +81,8 @@ def _as_fp32(launch):
 
 
 def _trace(case_name, mp, train_gemm_precision):
-    case = rt.CASES[case_name]
-    net = rt._net(case["net"])
-    net.train_gemm_precision = train_gemm_precision
-    try:
-        return rt.run_case(case, mp)
-    finally:
-        net.train_gemm_precision = "fp32"
+    case = rt.CASES[case_name]                            # (run_case sets every switch: the value goes through the case's options)
+    return rt.run_case(dict(case, opts=dict(case["opts"], train_gemm_precision=train_gemm_precision)), mp)
 
 
 @pytest.mark.parametrize("case_name", ["h-16x400x400-training", "f-2x70x93-training", "h-128x400x400-training"])

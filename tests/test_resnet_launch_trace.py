@@ -36,10 +36,12 @@ from dream_amd import data_parallel, models, ops  # noqa: E402
 FIXTURE = os.path.join(ROOT, "tests", "golden", "resnet_launch_trace.json")
 NETWORKS = {"h": dict(n_keypoints=7, full=False), "f": dict(n_keypoints=17, full=True)}
 SWITCHES = dict(precision="fp32", conv_algorithm="winograd", conv1x1_algorithm="gemm", convT_algorithm="winograd", bn_fusion=True,
-                bn_fusion_3x3=True, bn_fusion_head=True, stem_on_gemm=True, ds_on_gemm=True)
+                bn_fusion_3x3=True, bn_fusion_head=True, stem_on_gemm=True, ds_on_gemm=True, train_gemm_precision="fp32",
+                inference_activation_storage="fp32")
 ONE_AT_A_TIME = [dict(bn_fusion=False), dict(bn_fusion_3x3=False), dict(bn_fusion_head=False), dict(stem_on_gemm=False), dict(ds_on_gemm=False),
                  dict(conv_algorithm="direct"), dict(conv1x1_algorithm="direct"), dict(convT_algorithm="direct")]
 BIG, SMALL = (16, 400, 400), (2, 70, 93)
+HALF_STORED = dict(precision="fp16", inference_activation_storage="fp16")
 
 
 def _base_cases():
@@ -56,6 +58,9 @@ def _base_cases():
     out += [("h", s, "training", dict(tile=2)) for s in (BIG, (128, 400, 400))]
     out.append(("h", BIG, "inference", dict(tile=4)))
     out += [("h", BIG, "inference", dict(precision="fp16x3")), ("f", SMALL, "inference", dict(precision="fp16x3"))]
+    out += [("h", BIG, "inference", dict(precision="fp16")), ("f", SMALL, "inference", dict(precision="fp16"))]
+    out += [(n, s, "inference", HALF_STORED) for n, s in (("h", BIG), ("f", SMALL), ("h", (1, 320, 320)))]
+    out += [(n, s, "training", dict(train_gemm_precision="fp16")) for n, s in (("h", BIG), ("h", (4, 128, 128)), ("f", SMALL))]
     return out
 
 
@@ -173,6 +178,16 @@ def check_properties(name, case, trace):
         assert _count_prefix(trace, "dream_conv3x3_winograd_bnstats_") == 30, name
         assert _count_prefix(trace, "dream_conv3x3_winograd_bwd_bnmask_") == 30, name
         assert _count_prefix(trace, "dream_bn_train_fwd_") == 0, name
+    if case["net"] == "h" and case["shape"] == BIG and opts == dict(train_gemm_precision="fp16"):
+        # the covered data gradients: of the 66 fused 1x1 GEMM ones of the fp32 trace (above) all but one run on the fp16 matrix cores
+        # (the one left: the head conv's behind the last decoder BatchNorm, a "final" record -- _half_unit covers "conv" records only)
+        assert _count_prefix(trace, "dream_conv1x1_bwd_bnmask_") == 66 and _count_prefix(trace, "dream_conv1x1_bwd_bnmask_f16") == 65, name
+    if opts.get("inference_activation_storage") == "fp16":
+        # the rule of test_fp16_resnet_storage_emulated.py (test_every_launch_between_the_ends_is_half_storage): behind the stem's im2col
+        # every launch reads and writes half NHWC -- no fp32 conv between the image and the head, which writes the fp32 maps
+        names = [l.split(" ", 1)[0] for l in seq if not l.startswith("dream_bn_fold_f32")]
+        assert names[0] == "dream_im2col_nchw_f16" and names[-1] == "dream_conv2d_f16_nhwc_f16", name
+        assert all(n.endswith("_nhwc_f16") for n in names[1:]) and not any(n.endswith("_nhwc_f32") for n in names), name
     if not fused:
         assert _count_infix(trace, "_bnstats_") == 0 and _count_infix(trace, "_bnmask_") == 0, name
         assert _count_prefix(trace, "dream_conv1x1_pre_") == 0, name
