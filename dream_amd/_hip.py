@@ -115,6 +115,10 @@ _SIGNATURES = {
     "dream_conv2d_f16_ksplit_workspace": (_SZ, [_I] * 5),
     "dream_conv2d_f16_ksplit_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv_f16_set_ksplit": (_I, [_I]),
+    "dream_conv2d_f16_ksplit_resnet": (_I, [_I] * 7),
+    "dream_conv_transpose4x4s2_f16_ksplit": (_I, [_I] * 5),
+    "dream_conv_transpose4x4s2_f16_ksplit_workspace": (_SZ, [_I] * 5),
+    "dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_conv3x3_first_nchw_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dream_add_f16": (_I, [_P, _P, _P, _SZ, _P, _P]),

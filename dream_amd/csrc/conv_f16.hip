@@ -128,6 +128,49 @@ __global__ void __launch_bounds__(256) conv_f16_ksplit_finish_kernel(const float
     if (amax) publish_amax(amax, m);
 }
 
+// The finishing pass of the split ConvTranspose2d(k4,s2,p1) (inference_conv_ksplit="auto"): elementwise over the OUTPUT
+// [B, 2H, 2W, Cout], 8 consecutive channels of one output pixel per lane (Cout % 8 == 0).  Output pixel (oy, ox) belongs to sub-pixel
+// phase ph = 2 (oy & 1) + (ox & 1) at position (oy >> 1, ox >> 1); the S partial tiles of phase ph lie at ws + (ph * S + s) * slice, each
+// [B, H, W, Cout] fp32 (slice = B H W Cout floats).  Added in slice order 0 .. S-1 (fp32; no atomics: two runs give the same bits), then
+// the IEEE operations of conv_f16_ksplit_finish_kernel: v * (2^-ew * scale) + shift, ReLU, max|v| before the saturation into the peak
+// scalar, sat_half.  Two 16-byte loads per slice, one 16-byte store.
+__global__ void __launch_bounds__(256) convT4_f16_ksplit_finish_kernel(const float *ws, size_t slice, int S, const int *w_exp,
+                                                                       const float *scale, const float *shift, _Float16 *y, int B, int H,
+                                                                       int W, int Cout, int relu, unsigned *amax) {
+    const int e = -*w_exp;
+    const float inv = pow2f(e < -126 ? -126 : (e > 127 ? 127 : e));
+    const int c8n = Cout / 8, Wo = 2 * W, Ho = 2 * H;
+    const size_t n8 = (size_t)B * Ho * Wo * c8n;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+        const size_t pix = i / (size_t)c8n;
+        const int c0 = (int)(i - pix * c8n) * 8;
+        const int ox = (int)(pix % (size_t)Wo);
+        const size_t row = pix / (size_t)Wo;
+        const int oy = (int)(row % (size_t)Ho);
+        const size_t b = row / (size_t)Ho;
+        const int ph = 2 * (oy & 1) + (ox & 1);
+        const float *q = ws + (size_t)ph * S * slice + ((b * H + (oy >> 1)) * W + (ox >> 1)) * (size_t)Cout + c0;
+        f32x4 lo = *(const f32x4 *)q, hi = *(const f32x4 *)(q + 4);
+        for (int s = 1; s < S; ++s) {
+            q += slice;
+            lo += *(const f32x4 *)q;
+            hi += *(const f32x4 *)(q + 4);
+        }
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int c = c0 + k;
+            float v = (k < 4 ? lo[k & 3] : hi[k & 3]) * (inv * (scale != nullptr ? scale[c] : 1.0f)) + (shift != nullptr ? shift[c] : 0.0f);
+            if (relu) v = fmaxf(v, 0.0f);
+            m = fmaxf(m, fabsf(v));
+            o[k] = sat_half(v);
+        }
+        *(f16x8 *)(y + i * 8) = o;
+    }
+    if (amax) publish_amax(amax, m);
+}
+
 struct Variant16h {
     const char *name;
     int BM, BN, NP_MAX, threads, abufs;
@@ -176,6 +219,19 @@ constexpr int kKsplitTargetWorkgroups = 384;
 constexpr int kKsplitMinStages = 24;
 constexpr int kKsplitMax = 16;
 
+// The rule is one body over a table of these three (ksplit_slices below).  The hourglass's table is the three constants above; ResnetSimple's
+// walk (inference_conv_ksplit="auto": its 1x1 / 3x3 / gathered convs without a residual and the sub-pixel phases of its 4x4 transposed
+// convs) has a table of its own, measured per layer on its own shapes (profiles/ab_resnet_ksplit.txt)
+// ... plus one stated condition: a launch of fewer than short_stages stages counts against short_target_workgroups instead (0: none).
+// ResnetSimple's numbers (per launch, 1 .. 128 frames): contractions of 64 stages and more win in 2 .. 16 slices up to ~130 unsplit
+// workgroups (the first decoder stage, 256 stages on 4 workgroups a phase and frame: 0.527 -> 0.088 ms in 16 slices at one frame, 0.531 ->
+// 0.317 in 2 at 32 frames) and down to 16 stages a slice; from ~190 workgroups on every split tied or lost.  The 32- and 36-stage
+// launches (layer3's 1024->256, a 256->256 decoder stage on 26 x 26) win in 2 slices up to ~50 workgroups and tie at 80 .. 96, hence the
+// condition; slices of 8 stages lost everywhere (the 16- and 18-stage launches are never split)
+struct KsplitRule { int target_workgroups, min_stages, max_slices, short_stages, short_target_workgroups; };
+constexpr KsplitRule kKsplitHourglass = {kKsplitTargetWorkgroups, kKsplitMinStages, kKsplitMax, 0, 0};
+constexpr KsplitRule kKsplitResnet = {256, 16, 16, 64, 128};
+
 // One launch of `form` (kForms).  `residual`: the true residual or, with DREAM_CONV_RELUMASK, the mask (fp32 or half, as the form
 // says); ksplit: the slices of the ksplit form, y = the fp32 workspace (dream_conv2d_f16_ksplit_nhwc_f16); grad_amax: the scalar the g16
 // entry / exit forms derive e_g from
@@ -209,7 +265,8 @@ int launch_f16(Form16 form, const void *x, const unsigned *amax_in, const void *
                   "ReLU mask: needs the mask tensor (residual), NHWC output, no pool");
     DREAM_REQUIRE(!f.EPI_MASK || mask, "conv_f16: the %s form goes with DREAM_CONV_RELUMASK", f.name);
     DREAM_REQUIRE(f.KSPLIT ? ksplit >= 1 && ksplit <= 1024 : ksplit == 0, "conv_f16: a split launch is the ksplit form in 1 .. 1024 slices");
-    DREAM_REQUIRE(!(f.KSPLIT || f.GRAD16) || g.out_scale == 1, "conv_f16: the %s form is a plain conv", f.name);
+    // (the ksplit form stores position coordinates [B, p.H, p.W, Cout] and never reads out_scale: a sub-pixel phase runs as it is)
+    DREAM_REQUIRE(!f.GRAD16 || g.out_scale == 1, "conv_f16: the %s form is a plain conv", f.name);
     if (f.GRAD16) p.grad_amax = grad_amax;         // (shares w_lo's slot, which these kernels do not read)
     void (*const kernel)(const Conv16Params) = var.kernel[form];
     fill_params16(p, g, var.BM, var.NP_MAX, flags);
@@ -378,25 +435,44 @@ extern "C" int dream_conv_f16_set_ksplit(int n) {
     return 0;
 }
 
-// Slices of this launch: fixed constants, no device query -- the emulator, a meta-device trace and the GPU agree.  1 wherever the
-// unsplit grid already has kKsplitTargetWorkgroups workgroups; never more than kKsplitMax, never fewer than kKsplitMinStages
-// stages a slice.  Non-increasing in B: a tile never spans frames, and the tile of a launch with more than 64 output channels
+namespace {
+
+// Slices of one launch of geometry g: fixed constants, no device query -- the emulator, a meta-device trace and the GPU agree.  1 wherever
+// the unsplit grid already has r.target_workgroups workgroups (r.short_target_workgroups for a launch of fewer than r.short_stages
+// stages); never more than r.max_slices, never fewer than r.min_stages stages a slice.
+// Non-increasing in B: a tile never spans frames, and the tile of a launch with more than 64 output channels
 // changes with B only where the answer is 1 on both sides (the tiny-grid rule of variant_f16 holds below 512 units of 256 px x 64
 // channels; above it the 128 x 128 tiles alone are >= 512 workgroups).
-extern "C" int dream_conv2d_f16_ksplit(int B, int H, int W, int Cin, int Cout, int ksize, int flags) {
-    if (B < 1 || H < 1 || W < 1 || Cin < KC || Cin % KC != 0 || Cout < 1 || (ksize != 1 && ksize != 3) || (flags & kKsplitRefused)) return 1;
-    const int nstages = (Cin / KC) * ksize * ksize;
+int ksplit_slices(const KsplitRule &r, int B, const Geom16 &g, int Cin, int Cout, int flags) {
+    const int nstages = (Cin / KC) * g.ntaps;
     if (g_forced_ksplit >= 1) return g_forced_ksplit < nstages ? g_forced_ksplit : nstages;
-    const long pixels = (long)B * H * W;
+    const long pixels = (long)B * g.H * g.W;
     if (Cout > 64 && ((pixels + 255) / 256) * ceil_div(Cout, 64) >= 512) return 1;
-    const Variant16h &var = kVariantsF16[variant_f16(pixels, Cin, Cout, ksize * ksize)];
+    const Variant16h &var = kVariantsF16[variant_f16(pixels, Cin, Cout, g.ntaps)];
     Conv16Params p;
-    fill_params16(p, geom16_conv(H, W, ksize, flags), var.BM, var.NP_MAX, flags);
+    fill_params16(p, g, var.BM, var.NP_MAX, flags);
     const long wgs = (long)B * p.tiles_x * p.tiles_y * ceil_div(Cout, var.BN);
-    long s = kKsplitTargetWorkgroups / wgs;
-    if (s > nstages / kKsplitMinStages) s = nstages / kKsplitMinStages;
-    if (s > kKsplitMax) s = kKsplitMax;
+    long s = (nstages < r.short_stages ? r.short_target_workgroups : r.target_workgroups) / wgs;
+    if (s > nstages / r.min_stages) s = nstages / r.min_stages;
+    if (s > r.max_slices) s = r.max_slices;
     return s < 1 ? 1 : (int)s;
+}
+
+// ... of a k x k conv (what both dream_conv2d_f16_ksplit* answer)
+int ksplit_conv(const KsplitRule &r, int B, int H, int W, int Cin, int Cout, int ksize, int flags) {
+    if (B < 1 || H < 1 || W < 1 || Cin < KC || Cin % KC != 0 || Cout < 1 || (ksize != 1 && ksize != 3) || (flags & kKsplitRefused)) return 1;
+    return ksplit_slices(r, B, geom16_conv(H, W, ksize, flags), Cin, Cout, flags);
+}
+
+}  // namespace
+
+extern "C" int dream_conv2d_f16_ksplit(int B, int H, int W, int Cin, int Cout, int ksize, int flags) {
+    return ksplit_conv(kKsplitHourglass, B, H, W, Cin, Cout, ksize, flags);
+}
+
+// The same rule over ResnetSimple's table (inference_conv_ksplit="auto").
+extern "C" int dream_conv2d_f16_ksplit_resnet(int B, int H, int W, int Cin, int Cout, int ksize, int flags) {
+    return ksplit_conv(kKsplitResnet, B, H, W, Cin, Cout, ksize, flags);
 }
 
 // bytes of S slices of round_up(B H W Cout, 8) floats
@@ -424,6 +500,50 @@ extern "C" int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, co
     hipLaunchKernelGGL(conv_f16_ksplit_finish_kernel, dim3((unsigned)(slice / 8 / 256 < 4096 ? slice / 8 / 256 + 1 : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)workspace, slice, S, w_exp, scale, shift, (_Float16 *)y, n, Cout,
                        (flags & DREAM_CONV_RELU) ? 1 : 0, amax_out);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+
+// ---- inference_conv_ksplit="auto": ResnetSimple's decoder, ConvTranspose2d(k4,s2,p1) -> BatchNorm -> ReLU (dream/models.py:37-136), with the
+// contraction of each sub-pixel phase divided over S slices ----------------------------------------------------------
+// Slices of one phase (4 taps, kext 3) under ResnetSimple's table; 1 when Cout % 8 != 0 (the finishing pass handles 8 channels a lane).
+// Honours dream_conv_f16_set_ksplit.
+extern "C" int dream_conv_transpose4x4s2_f16_ksplit(int B, int H, int W, int Cin, int Cout) {
+    if (B < 1 || H < 1 || W < 1 || Cin < KC || Cin % KC != 0 || Cout < 1 || Cout % 8 != 0) return 1;
+    return ksplit_slices(kKsplitResnet, B, geom16_convT4_phase(H, W, 0), Cin, Cout, 0);
+}
+
+// bytes of 4 phases x S slices of round_up(B H W Cout, 8) floats
+extern "C" size_t dream_conv_transpose4x4s2_f16_ksplit_workspace(int B, int H, int W, int Cout, int S) {
+    return 4 * dream_conv2d_f16_ksplit_workspace(B, H, W, Cout, S);
+}
+
+// dream_conv_transpose4x4s2_f16_nhwc_f16 with every phase in S slices: four ksplit-form launches (phase ph writes its slices at
+// workspace + (ph * S + s) * slice), then convT4_f16_ksplit_finish_kernel.  S == 1 is dream_conv_transpose4x4s2_f16_nhwc_f16 itself (the
+// workspace is not touched).
+extern "C" int dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                                             const float *shift, void *y, unsigned *amax_out, void *workspace, int S,
+                                                             int B, int H, int W, int Cin, int Cout, int CoutPad, int flags,
+                                                             void *stream) {
+    DREAM_REQUIRE(S >= 1, "conv_transpose4x4s2_f16_ksplit: S=%d", S);
+    if (S == 1) return dream_conv_transpose4x4s2_f16_nhwc_f16(x, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
+    DREAM_REQUIRE((flags & (DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_POOL2 | DREAM_CONV_RELUMASK)) == 0,
+                  "conv_transpose4x4s2_f16_ksplit: unsupported flags %d: such a launch is not split", flags);
+    DREAM_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cout >= 1 && Cout % 8 == 0,
+                  "conv_transpose4x4s2_f16_ksplit: Cout=%d: a split launch needs a multiple of 8 output channels", Cout);
+    DREAM_REQUIRE(workspace && y && (((size_t)workspace | (size_t)y) & 15) == 0,
+                  "conv_transpose4x4s2_f16_ksplit: workspace and y must be 16-byte aligned");
+    const size_t slice = (size_t)B * H * W * Cout;          // (Cout % 8 == 0: already a multiple of 8 floats)
+    int ph = 0;
+    if (int rc = for_convT4_phases(H, W, Cin, CoutPad, [&](const Geom16 &g, size_t off) {
+            return launch_f16(kKsplit, x, nullptr, (const _Float16 *)w + off, w_exp, nullptr, nullptr, nullptr,
+                              (float *)workspace + (size_t)(ph++) * S * slice, nullptr, B, Cin, Cout, CoutPad, g, 0, stream, S);
+        }))
+        return rc;
+    const size_t n8 = 4 * slice / 8;
+    hipLaunchKernelGGL(convT4_f16_ksplit_finish_kernel, dim3((unsigned)(n8 / 256 < 4096 ? n8 / 256 + 1 : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const float *)workspace, slice, S, w_exp, scale, shift, (_Float16 *)y, B, H, W, Cout, (flags & DREAM_CONV_RELU) ? 1 : 0,
+                       amax_out);
     DREAM_LAUNCH_OK();
     return 0;
 }

@@ -122,10 +122,11 @@ _RESNET_SWITCHES = (
     ("precision", None, (), "inference"),
     ("train_gemm_precision", ("fp32", "fp16"), (("bn_fusion", True), ("conv1x1_algorithm", "gemm")), "training"),
     ("inference_activation_storage", ("fp32", "fp16"), (("precision", "fp16"),), "inference"),
+    ("inference_conv_ksplit", ("off", "auto"), (("precision", "fp16"), ("inference_activation_storage", "fp16")), "inference"),
 )
 # ``family``: as in _Walk; ``act16``: the evaluation walk stores its activations as half; ``train16``: the covered units of a training
-# pass (ResnetSimple._half_unit) run in half precision.
-_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16")
+# pass (ResnetSimple._half_unit) run in half precision; ``ksplit``: the half-stored evaluation walk may split a small launch.
+_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16 ksplit")
 
 
 class _PeakScalar:
@@ -1522,10 +1523,12 @@ class _EvalAmax:
 class _EvalAct16:
     """inference_activation_storage="fp16" (DESIGN.md 4.8k): the "f16" kernels with every tensor between the fp32 image and the fp32
     belief maps stored as IEEE half.  The value: the torch.float16 NHWC tensor; every half-writing launch atomicMaxes max|v| before the
-    saturation into ``peak``, the pass's one scalar (ResnetSimple.half_storage_peak())."""
+    saturation into ``peak``, the pass's one scalar (ResnetSimple.half_storage_peak()).  ``ksplit`` (inference_conv_ksplit="auto"; DESIGN.md
+    4.8l): a conv without a residual and a decoder stage ask ResnetSimple's rule and divide the contraction of a launch that cannot fill the
+    chip; the stem, the head and conv3 with its residual stay the launches they are."""
 
-    def __init__(self, net, peak):
-        self.n, self.peak = net, peak
+    def __init__(self, net, peak, ksplit=False):
+        self.n, self.peak, self.ksplit = net, peak, ksplit
 
     def stem(self, x):
         col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=self.peak)
@@ -1554,12 +1557,15 @@ class _EvalAct16:
         flags = CONV_RELU if relu else 0
         if residual is not None:
             return ops.conv2d_f16_act16_res(x, p16, cout, k, residual, scale, shift, flags, peak=self.peak)
+        if self.ksplit:
+            return ops.conv2d_f16_act16_ksplit(x, p16, cout, k, scale, shift, flags, peak=self.peak, rule=ops.conv2d_f16_ksplit_resnet)
         return ops.conv2d_f16_act16(x, p16, cout, k, scale, shift, flags, peak=self.peak)
 
     def stage(self, name, m, bn, y):
         p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
         scale, shift = self.n._fold(name, bn, m.bias)
-        return ops.conv_transpose4x4s2_f16_act16(y, p16, p16[3], scale, shift, CONV_RELU, peak=self.peak)
+        launch = ops.conv_transpose4x4s2_f16_act16_ksplit if self.ksplit else ops.conv_transpose4x4s2_f16_act16
+        return launch(y, p16, p16[3], scale, shift, CONV_RELU, peak=self.peak)
 
     def head(self, name, m, y):
         p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
@@ -1640,6 +1646,13 @@ class ResnetSimple(nn.Module):
         # evaluation forward (_resolve_switches -> _ResnetWalk.act16); a training pass ignores it.  See half_storage_peak().  Not spelled
         # ``activation_storage``: that name is DreamHourglass's switch, which this class exposes as fixed to "fp32" and keeps refusing.
         self.inference_activation_storage = "fp32"
+        # Inference, with both of the above "fp16": "auto" = a launch of the half-stored walk whose grid cannot fill the chip (the deep half
+        # of the trunk and the first decoder stage at 1 .. 16 frames) divides its contraction over more workgroups -- the convs without a
+        # residual through ops.conv2d_f16_act16_ksplit, the 4x4 transposed convs through ops.conv_transpose4x4s2_f16_act16_ksplit, slices by
+        # ResnetSimple's own table of the rule (csrc/conv_f16.hip kKsplitResnet).  "off" (default): today's launches.  Read
+        # once per evaluation forward (_resolve_switches -> _ResnetWalk.ksplit); a training pass ignores it.  Not spelled ``conv_ksplit``:
+        # that name is DreamHourglass's switch, which this class exposes as fixed to "off" and keeps refusing.
+        self.inference_conv_ksplit = "off"
         self._storage_peak = _PeakScalar("half_storage_peak(): no forward with inference_activation_storage=\"fp16\" has run")
         self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
         # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
@@ -1910,7 +1923,7 @@ class ResnetSimple(nn.Module):
                 raise ValueError("%s=\"%s\" needs %s (%s)" % (name, value, " and ".join(n if v is True else "%s=\"%s\"" % (n, v) for n, v in needs),
                                                             "%s is %r" % (needs[0][0], are[0]) if len(are) == 1 else "they are %r and %r" % are))
         return _ResnetWalk(_HALF_OPS.get(read["precision"], "fp32"), read["inference_activation_storage"] == "fp16",
-                           read["train_gemm_precision"] == "fp16")
+                           read["train_gemm_precision"] == "fp16", read["inference_conv_ksplit"] == "auto")
 
     @staticmethod
     def _half_unit(rec):
@@ -1980,7 +1993,7 @@ class ResnetSimple(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
         walk = self._resolve_switches(False)
-        a = (_EvalAct16(self, self._storage_peak.zeroed(x.device)) if walk.act16 else          # (zeroed once per pass, before its first launch)
+        a = (_EvalAct16(self, self._storage_peak.zeroed(x.device), walk.ksplit) if walk.act16 else         # (zeroed once per pass, before its first launch)
              _EvalFp32(self) if walk.family == "fp32" else _EvalAmax(self, walk.family))
         y = a.pool(a.stem(x))                               # then MaxPool(3,2,1)
         for name, blk in self._trunk():

@@ -427,7 +427,8 @@ class DreamNetwork:
         state = [t._version for t in self.model.parameters()] + [t._version for t in self.model.buffers()]
         key = (tuple(x.shape), getattr(self.model.module, "precision", "fp32"),
                getattr(self.model.module, "activation_storage", "fp32"), getattr(self.model.module, "conv_ksplit", "off"),
-               getattr(self.model.module, "inference_activation_storage", "fp32"), bool(self.use_belief_peak_scores),
+               getattr(self.model.module, "inference_activation_storage", "fp32"),
+               getattr(self.model.module, "inference_conv_ksplit", "off"), bool(self.use_belief_peak_scores),
                float(self.belief_peak_next_best_score))
         entry = self._graphs.get(key)
         if entry is None or entry["state"] != state:

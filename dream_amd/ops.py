@@ -1675,14 +1675,21 @@ def conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags=0):
     return int(_hip.lib().dream_conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags))
 
 
-def conv2d_f16_act16_ksplit(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flags=0, peak=None, workspace=None):
+def conv2d_f16_ksplit_resnet(b, h, w, cin, cout, ksize, flags=0):
+    """conv2d_f16_ksplit under ResnetSimple's table of the rule's constants (inference_conv_ksplit="auto")."""
+    return int(_hip.lib().dream_conv2d_f16_ksplit_resnet(b, h, w, cin, cout, ksize, flags))
+
+
+def conv2d_f16_act16_ksplit(x_nhwc, packed16, cout, ksize, scale=None, shift=None, flags=0, peak=None, workspace=None,
+                            rule=conv2d_f16_ksplit):
     """conv2d_f16_act16 with the contraction of a small grid divided over conv2d_f16_ksplit() slices (conv_ksplit="auto"): partial
     sums in an fp32 workspace (torch.empty per call: capturable), summed in slice order.  One slice -- every launch with a fused
     pool / upsample or the NCHW output, every grid that fills the chip -- IS conv2d_f16_act16.  ``workspace`` (tests): a float32
-    tensor of at least dream_conv2d_f16_ksplit_workspace() bytes to use instead."""
+    tensor of at least dream_conv2d_f16_ksplit_workspace() bytes to use instead.  ``rule``: the function that answers the slices
+    (ResnetSimple's walk passes conv2d_f16_ksplit_resnet)."""
     x = _f16(x_nhwc)
     b, h, w, cin = (int(v) for v in x.shape)
-    s = conv2d_f16_ksplit(b, h, w, cin, cout, ksize, flags)
+    s = rule(b, h, w, cin, cout, ksize, flags)
     if s == 1:
         return conv2d_f16_act16(x, packed16, cout, ksize, scale, shift, flags, peak=peak)
     hi, _, exp = _packed_planes("conv2d_f16_act16_ksplit", packed16, cin)
@@ -1714,6 +1721,34 @@ def conv_transpose4x4s2_f16_act16(x_nhwc, packed16, cout, scale=None, shift=None
     y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
     call("dream_conv_transpose4x4s2_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak), b, h, w, cin,
          cout, int(hi.shape[-2]), flags, stream())
+    return y
+
+
+def conv_transpose4x4s2_f16_ksplit(b, h, w, cin, cout):
+    """Slices per sub-pixel phase of conv_transpose4x4s2_f16_act16_ksplit (a host computation: no GPU is touched; 1 = not split)."""
+    return int(_hip.lib().dream_conv_transpose4x4s2_f16_ksplit(b, h, w, cin, cout))
+
+
+def conv_transpose4x4s2_f16_act16_ksplit(x_nhwc, packed16, cout, scale=None, shift=None, flags=0, peak=None, workspace=None):
+    """conv_transpose4x4s2_f16_act16 with the contraction of each of its four sub-pixel phases divided over
+    conv_transpose4x4s2_f16_ksplit() slices (ResnetSimple.inference_conv_ksplit="auto"): partial sums in an fp32 workspace
+    (torch.empty per call: capturable), summed in slice order by one pass over the output.  One slice IS
+    conv_transpose4x4s2_f16_act16.  ``workspace`` (tests): a float32 tensor of at least
+    dream_conv_transpose4x4s2_f16_ksplit_workspace() bytes to use instead."""
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    s = conv_transpose4x4s2_f16_ksplit(b, h, w, cin, cout)
+    if s == 1:
+        return conv_transpose4x4s2_f16_act16(x, packed16, cout, scale, shift, flags, peak=peak)
+    hi, _, exp = _packed_planes("conv_transpose4x4s2_f16_act16_ksplit", packed16, cin)
+    nbytes = int(_hip.lib().dream_conv_transpose4x4s2_f16_ksplit_workspace(b, h, w, cout, s))
+    if workspace is None:
+        workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    elif workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
+        raise RuntimeError("conv_transpose4x4s2_f16_act16_ksplit: workspace must be float32 of at least %d bytes" % nbytes)
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
+    call("dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), ptr(peak),
+         ptr(workspace), s, b, h, w, cin, cout, int(hi.shape[-2]), flags, stream())
     return y
 
 

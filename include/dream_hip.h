@@ -348,6 +348,26 @@ int dream_conv2d_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_
                                      void *y, unsigned *amax_out, void *workspace, int S, int B, int H, int W, int Cin,
                                      int Cout, int CoutPad, int ksize, int stride, int flags, void *stream);
 int dream_conv_f16_set_ksplit(int n);
+/* ---- ... and for ResnetSimple (ResnetSimple.inference_conv_ksplit = "auto") --------------------------------------------------
+ * dream_conv2d_f16_ksplit_resnet: dream_conv2d_f16_ksplit over ResnetSimple's own table of the three constants, measured on its
+ * shapes (the 1x1 / 3x3 / gathered stride-2 convs of the torchvision Bottlenecks behind /root/reference/dream/models.py:22-32 that
+ * carry no residual); same body, same hook, same properties.  The launches themselves are dream_conv2d_f16_ksplit_nhwc_f16. */
+int dream_conv2d_f16_ksplit_resnet(int B, int H, int W, int Cin, int Cout, int ksize, int flags);
+/* nn.ConvTranspose2d(k4,s2,p1) (+ folded BatchNorm, ReLU) of ResnetSimple's decoder (/root/reference/dream/models.py:37-136) with the
+ * contraction of each sub-pixel phase (Cin/32 x 4 stages) in S slices: S of the launch under ResnetSimple's table -- a host
+ * computation, 1 when Cout % 8 != 0, honours dream_conv_f16_set_ksplit, non-increasing in B. */
+int dream_conv_transpose4x4s2_f16_ksplit(int B, int H, int W, int Cin, int Cout);
+/* bytes of `workspace` for that launch (/root/reference/dream/models.py:37-136): 4 phases x S slices of round_up(B H W Cout, 8) floats */
+size_t dream_conv_transpose4x4s2_f16_ksplit_workspace(int B, int H, int W, int Cout, int S);
+/* dream_conv_transpose4x4s2_f16_nhwc_f16 (/root/reference/dream/models.py:37-136) in S slices per phase: four split launches -- phase
+ * ph = 2 (oy & 1) + (ox & 1) writes its raw fp32 partial tiles [B,H,W,Cout] at workspace + (ph * S + s) * slice --, then one
+ * elementwise pass over the output [B,2H,2W,Cout] that adds the S partials of each output pixel's phase in the order 0 .. S-1 and
+ * applies the unsplit epilogue (2^-ew * scale, shift, ReLU, max|v| before the saturation into amax_out, half store).  No
+ * floating-point atomics.  S == 1 IS dream_conv_transpose4x4s2_f16_nhwc_f16 (workspace unused).  S > 1 needs Cout % 8 == 0, a
+ * 16-byte aligned workspace and y, and refuses the flags the unsplit entry refuses (and DREAM_CONV_RELUMASK). */
+int dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                                  const float *shift, void *y, unsigned *amax_out, void *workspace, int S, int B,
+                                                  int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream);
 /* first encoder conv (dream/models.py:592-597): the fp32 arithmetic of dream_conv3x3_first_nchw_amax_f32, y half NHWC */
 int dream_conv3x3_first_nchw_f16(const float *x_nchw, const float *w_oihw, const float *bias, void *y_nhwc,
                                  unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int relu, void *stream);
