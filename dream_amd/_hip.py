@@ -119,6 +119,8 @@ _SIGNATURES = {
     "dream_conv_transpose4x4s2_f16_ksplit": (_I, [_I] * 5),
     "dream_conv_transpose4x4s2_f16_ksplit_workspace": (_SZ, [_I] * 5),
     "dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv_transpose4x4s2_head_f16_applies": (_I, [_I] * 3),
+    "dream_conv_transpose4x4s2_head_f16_nhwc_f16": (_I, [_P] * 10 + [_I] * 9 + [_P]),
     "dream_conv3x3_first_nchw_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool2_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dream_add_f16": (_I, [_P, _P, _P, _SZ, _P, _P]),

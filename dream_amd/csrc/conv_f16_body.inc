@@ -225,4 +225,10 @@
         }
         return;
     }
+// (a kernel that includes this body may name its own epilogue: conv_head_f16.hip -- text substitution, so that every kernel of
+// conv_f16.hip keeps its machine code)
+#ifdef CONV_F16_BODY_EPILOGUE
+#include CONV_F16_BODY_EPILOGUE
+#else
 #include "conv_f16_epilogue.inc"
+#endif

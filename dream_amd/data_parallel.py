@@ -131,7 +131,7 @@ def _buffer_stamp(module):
 
 
 def _settings(module):
-    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "conv_ksplit", "conv_algorithm", "conv1x1_algorithm",
+    return tuple(getattr(module, a, None) for a in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "inference_head_fusion", "conv_ksplit", "conv_algorithm", "conv1x1_algorithm",
                                                        "convT_algorithm"))
 
 
@@ -432,7 +432,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "conv_ksplit", "train_precision", "train_gemm_precision", "train_activation_storage",
+            for attr in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "inference_head_fusion", "conv_ksplit", "train_precision", "train_gemm_precision", "train_activation_storage",
                          "train_gradient_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))

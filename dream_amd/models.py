@@ -123,10 +123,12 @@ _RESNET_SWITCHES = (
     ("train_gemm_precision", ("fp32", "fp16"), (("bn_fusion", True), ("conv1x1_algorithm", "gemm")), "training"),
     ("inference_activation_storage", ("fp32", "fp16"), (("precision", "fp16"),), "inference"),
     ("inference_conv_ksplit", ("off", "auto"), (("precision", "fp16"), ("inference_activation_storage", "fp16")), "inference"),
+    ("inference_head_fusion", ("off", "on"), (("precision", "fp16"), ("inference_activation_storage", "fp16")), "inference"),
 )
 # ``family``: as in _Walk; ``act16``: the evaluation walk stores its activations as half; ``train16``: the covered units of a training
-# pass (ResnetSimple._half_unit) run in half precision; ``ksplit``: the half-stored evaluation walk may split a small launch.
-_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16 ksplit")
+# pass (ResnetSimple._half_unit) run in half precision; ``ksplit``: the half-stored evaluation walk may split a small launch;
+# ``fuse_head``: it runs its last decoder stage and the head as one entry point where that entry applies.
+_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16 ksplit fuse_head")
 
 
 class _PeakScalar:
@@ -174,10 +176,30 @@ def _half_dgrad(dy, dy_amax, p16, mask, x16, dy16, dx16, grad_amax, peak):
     return ops.conv2d_f16(dy, dy_amax, p16, p16[3], 3, relu_mask=mask)       # (behind a pool: the pool's backward carries the ReLU gradient)
 
 
+class _FixedSwitch:
+    """A precision switch of another network class on a class that has one setting of it only: reads as ``value``, and assigning anything
+    else raises ValueError("<refusal>: <name>=<the value> is not supported").  ``why``: the reason, for the reader."""
+
+    def __init__(self, value, refusal, why):
+        self.value, self.refusal, self.__doc__ = value, refusal, "Always %r: %s." % (value, why)
+
+    def __set_name__(self, owner, name):
+        self.name = name
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else self.value
+
+    def __set__(self, obj, value):
+        if value != self.value:
+            raise ValueError("%s: %s=%r is not supported" % (self.refusal, self.name, value))
+
+
 class DreamHourglass(nn.Module):
     # input pixels per step up to which weight gradients run on a second stream: +1.4 % at 16 frames of 400x400, -0.2 % at
     # 32 (the VGG layers are large enough to fill the chip on their own; see ResnetSimple for the case where it pays)
     OVERLAP_MAX_PIXELS = int(os.environ.get("DREAM_VGG_OVERLAP_MAX_FRAMES", "16")) * 400 * 400
+    # (ResnetSimple's switch: its last decoder stage and 1x1 head as one launch per phase)
+    inference_head_fusion = _FixedSwitch("off", "DreamHourglass does not fuse its head", "the fused entry is ResnetSimple's ConvTranspose2d(256,256,4,2,1) + 1x1 head")
 
     def __init__(self, n_keypoints, n_image_input_channels=3, internalize_spatial_softmax=True,
                  learned_beta=True, initial_beta=1.0, skip_connections=False, deconv_decoder=False,
@@ -1232,24 +1254,6 @@ def _reduced(reducer, grads):
     return [reducer.result(g) for g in grads]
 
 
-class _FixedSwitch:
-    """A precision switch of DreamHourglass on a class that has one setting of it only: reads as ``value``, and assigning anything
-    else raises ValueError("<refusal>: <name>=<the value> is not supported").  ``why``: the reason, for the reader."""
-
-    def __init__(self, value, refusal, why):
-        self.value, self.refusal, self.__doc__ = value, refusal, "Always %r: %s." % (value, why)
-
-    def __set_name__(self, owner, name):
-        self.name = name
-
-    def __get__(self, obj, owner=None):
-        return self if obj is None else self.value
-
-    def __set__(self, obj, value):
-        if value != self.value:
-            raise ValueError("%s: %s=%r is not supported" % (self.refusal, self.name, value))
-
-
 class DreamHourglassMultiStage(nn.Module):
     """The reference's DreamHourglassMultiStage (models.py:350-553): ``stage1`` .. ``stageS`` hourglasses (same
     ``state_dict()`` keys); stage s > 1 reads cat([image, belief maps of stage s-1]) -- the maps nearest-upsampled x4
@@ -1298,6 +1302,7 @@ class DreamHourglassMultiStage(nn.Module):
     _FP32_ACTIVATIONS = "DreamHourglassMultiStage stores its activations in fp32 only"
     activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
     conv_ksplit = _FixedSwitch("off", "DreamHourglassMultiStage does not split its convs", "the stages run the fp32-storage walk")
+    inference_head_fusion = _FixedSwitch("off", "DreamHourglassMultiStage does not fuse its heads", "the fused entry is ResnetSimple's ConvTranspose2d(256,256,4,2,1) + 1x1 head")
     train_gradient_storage = _FixedSwitch("fp32", "DreamHourglassMultiStage stores its gradients in fp32 only",
                                           "the stages hand fp32 gradients to one another")
     train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
@@ -1525,10 +1530,11 @@ class _EvalAct16:
     belief maps stored as IEEE half.  The value: the torch.float16 NHWC tensor; every half-writing launch atomicMaxes max|v| before the
     saturation into ``peak``, the pass's one scalar (ResnetSimple.half_storage_peak()).  ``ksplit`` (inference_conv_ksplit="auto"; DESIGN.md
     4.8l): a conv without a residual and a decoder stage ask ResnetSimple's rule and divide the contraction of a launch that cannot fill the
-    chip; the stem, the head and conv3 with its residual stay the launches they are."""
+    chip; the stem, the head and conv3 with its residual stay the launches they are.  ``fuse_head`` (inference_head_fusion="on"; DESIGN.md
+    4.8m): the last decoder stage and the head behind it are one entry point where stage_head() finds that it applies."""
 
-    def __init__(self, net, peak, ksplit=False):
-        self.n, self.peak, self.ksplit = net, peak, ksplit
+    def __init__(self, net, peak, ksplit=False, fuse_head=False):
+        self.n, self.peak, self.ksplit, self.fuse_head = net, peak, ksplit, fuse_head
 
     def stem(self, x):
         col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=self.peak)
@@ -1570,6 +1576,27 @@ class _EvalAct16:
     def head(self, name, m, y):
         p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
         return ops.conv2d_f16_act16(y, p16, p16[3], 1, None, m.bias.detach(), CONV_OUT_NCHW)
+
+    def stage_head(self, name, m, bn, head_name, hm, y):
+        """stage() and head() behind it as the fused entry point -> the belief maps, or None where the walk runs the two launches: the
+        switch is off, the pair is not ConvTranspose2d(k4,s2,p1) + a biased 1x1 stride-1 Conv2d of channel counts the entry takes
+        (ops.conv_transpose4x4s2_head_f16_applies; K > 32 for instance), or inference_conv_ksplit="auto" splits this stage (a launch
+        whose grid cannot fill the chip gains more from the slices than from the traffic the fusion saves).  The same packed planes,
+        the same IEEE operations: the maps and the peak are those of the two launches bit for bit, so yielding is no error."""
+        if not (self.fuse_head and isinstance(m, nn.ConvTranspose2d) and isinstance(hm, nn.Conv2d)):
+            return None
+        cin, cmid, k = int(m.weight.shape[0]), int(m.weight.shape[1]), int(hm.weight.shape[0])
+        if not (tuple(m.kernel_size) == (4, 4) and tuple(m.stride) == (2, 2) and tuple(m.padding) == (1, 1)
+                and tuple(m.output_padding) == (0, 0) and tuple(hm.kernel_size) == (1, 1) and tuple(hm.stride) == (1, 1)
+                and tuple(hm.padding) == (0, 0) and hm.bias is not None and int(hm.weight.shape[1]) == cmid
+                and int(y.shape[3]) == cin and ops.conv_transpose4x4s2_head_f16_applies(cin, cmid, k)):
+            return None
+        if self.ksplit and ops.conv_transpose4x4s2_f16_ksplit(int(y.shape[0]), int(y.shape[1]), int(y.shape[2]), cin, cmid) > 1:
+            return None
+        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
+        h16 = self.n._cached(("wf16", head_name), [hm.weight], lambda: ops.pack_conv_weight_f16(hm.weight.detach(), 0))
+        scale, shift = self.n._fold(name, bn, m.bias)
+        return ops.conv_transpose4x4s2_head_f16_act16(y, p16, p16[3], scale, shift, h16, h16[3], hm.bias.detach(), CONV_RELU, peak=self.peak)
 
 
 class ResnetSimple(nn.Module):
@@ -1653,6 +1680,13 @@ class ResnetSimple(nn.Module):
         # once per evaluation forward (_resolve_switches -> _ResnetWalk.ksplit); a training pass ignores it.  Not spelled ``conv_ksplit``:
         # that name is DreamHourglass's switch, which this class exposes as fixed to "off" and keeps refusing.
         self.inference_conv_ksplit = "off"
+        # Inference, with precision and inference_activation_storage "fp16": "on" = the last decoder stage (ConvTranspose2d(256,256,4,2,1) +
+        # folded BatchNorm + ReLU) and the 1x1 head run as one entry point (ops.conv_transpose4x4s2_head_f16_act16, csrc/conv_head_f16.hip;
+        # DESIGN.md 4.8m): the [B,2H,2W,256] half tensor, the walk's largest, is never allocated; maps and half_storage_peak() are those
+        # of "off" bit for bit.  Where the entry does not apply (more than 32 keypoints) or inference_conv_ksplit="auto" splits that stage,
+        # the walk runs the two launches.  "off" (default): today's launches.  Read once per evaluation forward (_resolve_switches ->
+        # _ResnetWalk.fuse_head); a training pass ignores it.
+        self.inference_head_fusion = "off"
         self._storage_peak = _PeakScalar("half_storage_peak(): no forward with inference_activation_storage=\"fp16\" has run")
         self.conv_algorithm = os.environ.get("DREAM_CONV_ALGORITHM", "winograd")   # see DreamHourglass.conv_algorithm
         # stride-1 1x1 convs (forward and data gradient): "gemm" = the LDS-free GEMM kernel (gemm1x1.hip), "direct" = conv_mfma
@@ -1923,7 +1957,8 @@ class ResnetSimple(nn.Module):
                 raise ValueError("%s=\"%s\" needs %s (%s)" % (name, value, " and ".join(n if v is True else "%s=\"%s\"" % (n, v) for n, v in needs),
                                                             "%s is %r" % (needs[0][0], are[0]) if len(are) == 1 else "they are %r and %r" % are))
         return _ResnetWalk(_HALF_OPS.get(read["precision"], "fp32"), read["inference_activation_storage"] == "fp16",
-                           read["train_gemm_precision"] == "fp16", read["inference_conv_ksplit"] == "auto")
+                           read["train_gemm_precision"] == "fp16", read["inference_conv_ksplit"] == "auto",
+                           read["inference_head_fusion"] == "on")
 
     @staticmethod
     def _half_unit(rec):
@@ -1993,13 +2028,25 @@ class ResnetSimple(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError("expected [B,3,H,W] input, got %s" % (tuple(x.shape),))
         walk = self._resolve_switches(False)
-        a = (_EvalAct16(self, self._storage_peak.zeroed(x.device), walk.ksplit) if walk.act16 else         # (zeroed once per pass, before its first launch)
+        a = (_EvalAct16(self, self._storage_peak.zeroed(x.device), walk.ksplit, walk.fuse_head) if walk.act16 else     # (zeroed once per pass, before its first launch)
              _EvalFp32(self) if walk.family == "fp32" else _EvalAmax(self, walk.family))
         y = a.pool(a.stem(x))                               # then MaxPool(3,2,1)
         for name, blk in self._trunk():
             y = self._bottleneck(a, name, blk, y)
-        for name, m, bn in self._decoder():
+        return self._run_decoder(a, y)
+
+    def _run_decoder(self, a, y):
+        """The decoder on arithmetic ``a``, one entry ahead: the last (stage, head) pair is one call where ``a`` fuses it (_EvalAct16.stage_head)."""
+        entries = list(self._decoder())
+        i = 0
+        while i < len(entries):
+            name, m, bn = entries[i]
+            if bn is not None and i + 2 == len(entries) and entries[i + 1][2] is None and getattr(a, "fuse_head", False):
+                maps = a.stage_head(name, m, bn, entries[i + 1][0], entries[i + 1][1], y)
+                if maps is not None:
+                    return maps
             y = a.stage(name, m, bn, y) if bn is not None else a.head(name, m, y)
+            i += 1
         return y
 
     # ---- training: train-mode BatchNorm (batch statistics), activations kept for the backward plan --------

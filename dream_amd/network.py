@@ -423,12 +423,13 @@ class DreamNetwork:
 
     def _inference_graphed(self, x):
         """hipGraph replay of _inference_on_device for this input shape; re-captured when a parameter or buffer changed
-        (the packed weight copies the kernels read are re-created then) or a precision / storage / split switch moved."""
+        (the packed weight copies the kernels read are re-created then) or a precision / storage / split / head-fusion switch moved."""
         state = [t._version for t in self.model.parameters()] + [t._version for t in self.model.buffers()]
         key = (tuple(x.shape), getattr(self.model.module, "precision", "fp32"),
                getattr(self.model.module, "activation_storage", "fp32"), getattr(self.model.module, "conv_ksplit", "off"),
                getattr(self.model.module, "inference_activation_storage", "fp32"),
-               getattr(self.model.module, "inference_conv_ksplit", "off"), bool(self.use_belief_peak_scores),
+               getattr(self.model.module, "inference_conv_ksplit", "off"),
+               getattr(self.model.module, "inference_head_fusion", "off"), bool(self.use_belief_peak_scores),
                float(self.belief_peak_next_best_score))
         entry = self._graphs.get(key)
         if entry is None or entry["state"] != state:

@@ -1752,6 +1752,26 @@ def conv_transpose4x4s2_f16_act16_ksplit(x_nhwc, packed16, cout, scale=None, shi
     return y
 
 
+def conv_transpose4x4s2_head_f16_applies(cin, cmid, k):
+    """Does conv_transpose4x4s2_head_f16_act16 take these channel counts (a host computation: no GPU is touched)?"""
+    return bool(_hip.lib().dream_conv_transpose4x4s2_head_f16_applies(cin, cmid, k))
+
+
+def conv_transpose4x4s2_head_f16_act16(x_nhwc, packed16, cout, scale, shift, head_packed16, k, head_bias=None, flags=0, peak=None):
+    """conv_transpose4x4s2_f16_act16 (``packed16``, ``cout`` = 256 channels, ``scale`` / ``shift``, ``flags``, ``peak``) and the 1x1 head
+    conv2d_f16_act16(.., ``head_packed16``, ``k``, 1, None, ``head_bias``, CONV_OUT_NCHW) behind it as one entry point
+    (ResnetSimple.inference_head_fusion="on") -> the [B,k,2H,2W] float32 belief maps, bit-identical to the pair; the
+    [B,2H,2W,cout] half tensor between them is never allocated."""
+    x = _f16(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    hi, _, exp = _packed_planes("conv_transpose4x4s2_head_f16_act16", packed16, cin)
+    head_hi, _, head_exp = _packed_planes("conv_transpose4x4s2_head_f16_act16 (head)", head_packed16, cout)
+    maps = torch.empty((b, k, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    call("dream_conv_transpose4x4s2_head_f16_nhwc_f16", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(head_hi), ptr(head_exp),
+         ptr(head_bias), ptr(maps), ptr(peak), b, h, w, cin, cout, int(hi.shape[-2]), k, int(head_hi.shape[-2]), flags, stream())
+    return maps
+
+
 def conv3x3_first_f16(x_nchw, w_oihw, bias, relu=True, peak=None):
     """conv3x3_first (fp32 image, fp32 arithmetic) storing torch.float16 NHWC."""
     x, w = _f32(x_nchw), _f32(w_oihw)

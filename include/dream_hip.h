@@ -368,6 +368,23 @@ size_t dream_conv_transpose4x4s2_f16_ksplit_workspace(int B, int H, int W, int C
 int dream_conv_transpose4x4s2_f16_ksplit_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
                                                   const float *shift, void *y, unsigned *amax_out, void *workspace, int S, int B,
                                                   int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream);
+/* ---- the head inside the last decoder stage (ResnetSimple.inference_head_fusion = "on") -----------------------------------------
+ * nn.ConvTranspose2d(k4,s2,p1) (+ folded BatchNorm, ReLU) followed by the 1x1 nn.Conv2d to the K belief maps (the tail of
+ * ResnetSimple's decoder, dream/models.py:37-136) as ONE entry point: four launches, one per sub-pixel phase, whose workgroups keep
+ * the halfs of their 128 pixels x Cmid stage channels in LDS and contract them with the head's plane on the fp16 matrix cores.  The
+ * [B,2H,2W,Cmid] half tensor is never written.  x [B,H,W,Cin] half; w / w_exp: the stage's plane from
+ * dream_pack_convT4x4_weight_f16x3, scale / shift [Cmid] (optional) its folded BatchNorm; head_w / head_w_exp: the head's plane
+ * [KPad][Cmid] from dream_pack_conv_weight_f16x3 (mode 0), head_bias [K] (optional); maps [B,K,2H,2W] fp32; peak (optional, not
+ * zeroed): max|v| of the stage output before the saturation, as amax_out of dream_conv_transpose4x4s2_f16_nhwc_f16.  Maps and peak
+ * are bit-identical to dream_conv_transpose4x4s2_f16_nhwc_f16 followed by dream_conv2d_f16_nhwc_f16 (DREAM_CONV_OUT_NCHW): the same
+ * IEEE operations in the same order.  Accepts Cin % 32 == 0, Cmid == CmidPad == 256, 1 <= K <= 32, KPad a multiple of 32 (rows 0 .. 31 of the plane are read), flags 0 or
+ * DREAM_CONV_RELU, x / w / head_w 16-byte aligned; everything else is refused before anything is launched.
+ * dream_conv_transpose4x4s2_head_f16_applies: 1 exactly for the (Cin, Cmid, K) the entry accepts -- a host computation. */
+int dream_conv_transpose4x4s2_head_f16_applies(int Cin, int Cmid, int K);
+int dream_conv_transpose4x4s2_head_f16_nhwc_f16(const void *x, const void *w, const int *w_exp, const float *scale,
+                                                const float *shift, const void *head_w, const int *head_w_exp,
+                                                const float *head_bias, float *maps, unsigned *peak, int B, int H, int W,
+                                                int Cin, int Cmid, int CmidPad, int K, int KPad, int flags, void *stream);
 /* first encoder conv (dream/models.py:592-597): the fp32 arithmetic of dream_conv3x3_first_nchw_amax_f32, y half NHWC */
 int dream_conv3x3_first_nchw_f16(const float *x_nchw, const float *w_oihw, const float *bias, void *y_nhwc,
                                  unsigned *amax_out, int B, int H, int W, int Cin, int Cout, int relu, void *stream);
