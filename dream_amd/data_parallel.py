@@ -107,17 +107,11 @@ def flat_is_intact(module):
 
 def reset_weight_caches(module):
     """Drop every packed / folded copy of the weights a model keeps for the kernels (they are rebuilt on first use)."""
-    from . import models
+    from . import packed_weights
     for m in module.modules():
-        if "_packed" in m.__dict__:
-            m._packed = models._PackedCache()
-        if "_cache" in m.__dict__:
-            m._cache = {}
-        if m.__dict__.get("_pack_pending") is not None:
-            m._pack_join()                                  # a re-pack on the second stream still writes into the old copies
-        # ResnetSimple._repack_weights / _repack_half_weights: their tables write into the old copies
-        for name in ("_pack_state", "_pack_records", "_pack_pending", "_pack16_state", "_half_sources"):
-            m.__dict__.pop(name, None)
+        for store in m.__dict__.values():
+            if isinstance(store, (packed_weights.PackedWeights, packed_weights._PackedCache)):
+                store.reset()
 
 
 def _param_stamp(module):
@@ -401,14 +395,11 @@ class DreamDataParallel(nn.Module):
         devs = self.devices()
         while len(self._replicas) < n - 1:
             dev = devs[len(self._replicas) + 1]
-            # the master's packed weight copies and its flat record stay with the master: a replica builds its own on its device
-            memo = {id(v): None for m in self.module.modules()
-                    for v in (m.__dict__.get("_packed"), m.__dict__.get("_cache"), m.__dict__.get("_dream_flat"),
-                              m.__dict__.get("_pack_state"), m.__dict__.get("_pack_records"), m.__dict__.get("_pack_pending"))
-                    if v is not None}
+            # the master's flat record stays with the master, and a deep copy of a packed-weight store is an empty one (packed_weights.py):
+            # a replica builds its own copies on its device
+            memo = {id(m.__dict__["_dream_flat"]): None for m in self.module.modules() if m.__dict__.get("_dream_flat") is not None}
             rep = copy.deepcopy(self.module, memo)
             rep.__dict__.pop("_dream_flat", None)
-            reset_weight_caches(rep)
             if dev.type == "cuda":
                 with torch.cuda.device(dev):
                     rep = rep.to(dev)

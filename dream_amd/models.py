@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, pretrained as _pretrained
+from .packed_weights import PackedWeights, _PackedCache  # noqa: F401  (_PackedCache: data_parallel and the tests import it from here)
 from .ops import CONV_RELU, CONV_UPSAMPLE2X, CONV_OUT_NCHW, CONV_ZEROSTUFF2X, CONV_POOL2
 from .spatial_softmax import SoftArgmaxPavlo
 
@@ -47,47 +48,6 @@ class _Params(nn.Sequential):
 
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("dream_amd: parameter container, not callable; use the parent module")
-
-
-class _PackedCache:
-    """Packed copies of conv weights for the MFMA kernels, one per (weight, form, direction, tile), refreshed when the parameter
-    changes (optimizer step / load_state_dict bump ``_version``).  direction 0 / 1: the forward / the data-gradient operator
-    (transposed, flipped taps); tile 4 / 2: the Winograd kernel the operand is for (0 where the form has no tile)."""
-
-    def __init__(self):
-        self._store = {}
-
-    def get(self, weight, form, direction=0, tile=0):
-        key = (id(weight), form, direction, tile)
-        tag = (weight._version, weight.data_ptr(), weight.device)
-        hit = self._store.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                hit = (tag, self._pack(weight.detach(), form, direction, tile))
-            self._store[key] = hit
-        return hit[1]
-
-    @staticmethod
-    def _pack(w, form, direction, tile):
-        if form == "direct":                      # tap-major packing of the implicit-GEMM kernel
-            return ops.pack_weight(w, direction)
-        if form == "winograd":                    # transformed weights of the F(2x2,3x3) / F(4x4,3x3) kernel
-            return ops.pack_weight_winograd_tile(w, direction, tile)
-        if form == "ups":                         # the conv that follows a nearest x2 upsample, as the equivalent 4x4 transposed conv
-            return ops.pack_convT4x4_weight(ops.upsample_conv_weight(w))               # (sub-pixel phase packing)
-        if form == "ups_winograd":                # ... and that transposed conv by minimal filtering (9- / 25-position phase patterns)
-            return ops.pack_convT4x4_winograd_weight_tile(ops.upsample_conv_weight(w), tile, direction)
-        if form == "stride2":                     # a [Cin_T,Cout_T,3,3] ConvTranspose weight as the stride-2 conv that is its data gradient
-            return ops.pack_conv_weight(w, 0)
-        if form == "f16x3":                       # split precision: two fp16 planes of the tap-major packing
-            return ops.pack_conv_weight_f16x3(w, direction)
-        if form == "ups_f16x3":
-            return ops.pack_convT4x4_weight_f16x3(ops.upsample_conv_weight(w))
-        if form == "f16":                         # half precision: the `hi` plane and the exponent only
-            return ops.pack_conv_weight_f16(w, direction)
-        if form == "ups_f16":
-            return ops.pack_convT4x4_weight_f16(ops.upsample_conv_weight(w))
-        raise ValueError("unknown packed form %r" % (form,))
 
 
 # Inference precisions that run on the fp16 matrix cores -> suffix of their ops (ops.conv2d_<suffix>, ops.conv_transpose4x4s2_<suffix>,
@@ -1461,7 +1421,7 @@ class _EvalFp32:
         if k == 3 and stride == 1 and self.n.conv_algorithm == "winograd" and cin % 16 == 0 and cout >= 64:
             # the stride-1 3x3 convs of the bottlenecks: Winograd F(2x2,3x3) with the folded BatchNorm in the epilogue
             tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), cin, cout, int(x.shape[0]))
-            u, rows = self.n._wino(name, conv, 0, tile)
+            u, rows = self.n._w("wino", name, conv.weight, tile)
             return ops.conv3x3_winograd_tile(tile, x, u, rows, scale, shift, residual, flags)
         if self.n._gemm1x1(conv, x):
             # the 1x1 convs of the bottlenecks: a plain GEMM without LDS (gemm1x1.hip), folded BatchNorm / residual / ReLU fused
@@ -1473,7 +1433,7 @@ class _EvalFp32:
             if ops.conv1x1_applies(xs, cout):
                 packed, rows = self.n._g(name, conv, 0)
                 return ops.conv1x1(xs, packed, rows, scale, shift, residual, flags)
-        packed, rows, _ = self.n._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
+        packed, rows, _ = self.n._w("w", name, conv.weight)
         return ops.conv2d(x, packed, rows, k, stride, scale, shift, residual, flags)
 
     def stage(self, name, m, bn, y):
@@ -1481,7 +1441,7 @@ class _EvalFp32:
         return self.n._convT_forward(name, m, y, scale, shift, CONV_RELU)
 
     def head(self, name, m, y):
-        packed, rows, _ = self.n._cached(("w", name), [m.weight], lambda: ops.pack_conv_weight(m.weight.detach(), 0))
+        packed, rows, _ = self.n._w("w", name, m.weight)
         return ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
 
 
@@ -1490,13 +1450,12 @@ class _EvalAmax:
     NHWC tensor, its amax).  The six stride-2 convs of the trunk stay on the fp32 kernel, which publishes max|y| all the same."""
 
     def __init__(self, net, sfx):
-        self.n, self.sfx = net, sfx
-        self.pack, self.conv2d = getattr(ops, "pack_conv_weight_" + sfx), getattr(ops, "conv2d_" + sfx)
+        self.n, self.sfx, self.conv2d = net, sfx, getattr(ops, "conv2d_" + sfx)
 
     def stem(self, x):
         col = ops.im2col_nchw(x, 7, 7, 2, 3, 160)
         amax = ops.absmax(x)                               # im2col only rearranges (and zero-pads) the image
-        w1 = self.n._cached(("w" + self.sfx, "conv1"), [self.n.conv1.weight], lambda: self.pack(self.n.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        w1 = self.n._w("stem_w" + self.sfx, "conv1", self.n.conv1.weight)
         s1, t1 = self.n._fold("bn1", self.n.bn1)
         return self.conv2d(col, amax, w1, 64, 1, s1, t1, None, CONV_RELU)
 
@@ -1510,18 +1469,18 @@ class _EvalAmax:
         scale, shift = self.n._fold(name, bn, conv.bias)
         flags = CONV_RELU if relu else 0
         if stride != 1:
-            packed, rows, _ = self.n._cached(("w", name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), 0))
+            packed, rows, _ = self.n._w("w", name, conv.weight)
             return ops.conv2d_amax(x, packed, rows, k, stride, scale, shift, residual, flags)
-        p16 = self.n._cached(("w" + self.sfx, name), [conv.weight], lambda: self.pack(conv.weight.detach(), 0))
+        p16 = self.n._w("w" + self.sfx, name, conv.weight)
         return self.conv2d(x, amax, p16, p16[3], k, scale, shift, residual, flags)
 
     def stage(self, name, m, bn, ya):
-        p16 = self.n._cached(("w" + self.sfx, name), [m.weight], lambda: getattr(ops, "pack_convT4x4_weight_" + self.sfx)(m.weight.detach()))
+        p16 = self.n._w("w" + self.sfx + "T", name, m.weight)
         scale, shift = self.n._fold(name, bn, m.bias)
         return getattr(ops, "conv_transpose4x4s2_" + self.sfx)(ya[0], ya[1], p16, p16[3], scale, shift, CONV_RELU)
 
     def head(self, name, m, ya):
-        p16 = self.n._cached(("w" + self.sfx, name), [m.weight], lambda: self.pack(m.weight.detach(), 0))
+        p16 = self.n._w("w" + self.sfx, name, m.weight)
         return self.conv2d(ya[0], ya[1], p16, p16[3], 1, None, m.bias.detach(), None, CONV_OUT_NCHW, want_amax=False)[0]
 
 
@@ -1538,7 +1497,7 @@ class _EvalAct16:
 
     def stem(self, x):
         col = ops.im2col_nchw_f16(x, 7, 7, 2, 3, 160, peak=self.peak)
-        w1 = self.n._cached(("wf16", "conv1"), [self.n.conv1.weight], lambda: ops.pack_conv_weight_f16(self.n.conv1.weight.detach().reshape(64, 147, 1, 1), 0))
+        w1 = self.n._w("stem_wf16", "conv1", self.n.conv1.weight)
         s1, t1 = self.n._fold("bn1", self.n.bn1)
         return ops.conv2d_f16_act16(col, w1, 64, 1, s1, t1, CONV_RELU, peak=self.peak)
 
@@ -1554,12 +1513,11 @@ class _EvalAct16:
         cout = int(conv.weight.shape[0])
         if stride == 2 and k == 3:
             x, k = ops.im2col3s2_f16(x), 1
-            p16 = self.n._cached(("wf16col3", name), [conv.weight], lambda: ops.pack_conv_weight_f16(
-                conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, -1, 1, 1).contiguous(), 0))
+            p16 = self.n._w("wf16col3", name, conv.weight)
         else:
             if stride == 2:
                 x = ops.subsample2_f16(x)
-            p16 = self.n._cached(("wf16", name), [conv.weight], lambda: ops.pack_conv_weight_f16(conv.weight.detach(), 0))
+            p16 = self.n._w("wf16", name, conv.weight)
         flags = CONV_RELU if relu else 0
         if residual is not None:
             return ops.conv2d_f16_act16_res(x, p16, cout, k, residual, scale, shift, flags, peak=self.peak)
@@ -1568,13 +1526,13 @@ class _EvalAct16:
         return ops.conv2d_f16_act16(x, p16, cout, k, scale, shift, flags, peak=self.peak)
 
     def stage(self, name, m, bn, y):
-        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
+        p16 = self.n._w("wf16T", name, m.weight)
         scale, shift = self.n._fold(name, bn, m.bias)
         launch = ops.conv_transpose4x4s2_f16_act16_ksplit if self.ksplit else ops.conv_transpose4x4s2_f16_act16
         return launch(y, p16, p16[3], scale, shift, CONV_RELU, peak=self.peak)
 
     def head(self, name, m, y):
-        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_conv_weight_f16(m.weight.detach(), 0))
+        p16 = self.n._w("wf16", name, m.weight)
         return ops.conv2d_f16_act16(y, p16, p16[3], 1, None, m.bias.detach(), CONV_OUT_NCHW)
 
     def stage_head(self, name, m, bn, head_name, hm, y):
@@ -1593,8 +1551,8 @@ class _EvalAct16:
             return None
         if self.ksplit and ops.conv_transpose4x4s2_f16_ksplit(int(y.shape[0]), int(y.shape[1]), int(y.shape[2]), cin, cmid) > 1:
             return None
-        p16 = self.n._cached(("wf16", name), [m.weight], lambda: ops.pack_convT4x4_weight_f16(m.weight.detach()))
-        h16 = self.n._cached(("wf16", head_name), [hm.weight], lambda: ops.pack_conv_weight_f16(hm.weight.detach(), 0))
+        p16 = self.n._w("wf16T", name, m.weight)
+        h16 = self.n._w("wf16", head_name, hm.weight)
         scale, shift = self.n._fold(name, bn, m.bias)
         return ops.conv_transpose4x4s2_head_f16_act16(y, p16, p16[3], scale, shift, h16, h16[3], hm.bias.detach(), CONV_RELU, peak=self.peak)
 
@@ -1613,7 +1571,7 @@ class ResnetSimple(nn.Module):
         super().__init__()
         self.full = full
         self.n_keypoints = n_keypoints
-        self._cache = {}
+        self._packs = PackedWeights()             # every packed / folded copy of the weights, and their re-pack (packed_weights.py)
         self._read_switches()
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -1725,114 +1683,33 @@ class ResnetSimple(nn.Module):
         n_up = 5 if self.full else 4
         return tuple(trunk(int(v)) * (2 ** n_up) for v in input_wh)
 
-    # ---- execution (eval-mode BatchNorm folded into the conv epilogues) ----------------------------------
-    def _cached(self, key, tensors, build):
-        rec = self.__dict__.get("_pack_records")
-        if rec is not None and key[0] != "bn":
-            return self._cached_recording(key, tensors, build, rec)
-        pend = self.__dict__.get("_pack_pending")
-        if pend is not None and key not in pend[1]:
-            self._pack_join()                        # the late part of the step's re-pack runs on the second stream (_repack_weights)
-        tag = tuple((t._version, t.data_ptr()) for t in tensors)
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                hit = (tag, build())
-            self._cache[key] = hit
-        return hit[1]
+    # ---- packed weights: ResnetSimple keeps none itself.  ``_packs`` (packed_weights.PackedWeights) holds every copy under the keys of
+    # RESNET_FORMS and re-packs them per training step; _w is the one way in, _g / _stem_weight / _fold spell the forms of a use --------
+    def _w(self, form, name, param, arg=None):
+        """The copy of ``param`` (the weight of layer ``name``) in the form ``form`` of packed_weights.RESNET_FORMS."""
+        return self._packs.form(form, name, param, arg)
 
-    def _pack_join(self):
-        """The main stream waits for the late part of this step's re-pack (second stream); a no-op when none is pending."""
-        pend = self.__dict__.get("_pack_pending")
-        if pend is not None:
-            object.__setattr__(self, "_pack_pending", None)
-            torch.cuda.current_stream().wait_event(pend[0])
-
-    # ---- training: all packed weight copies of a step refreshed by ONE launch ------------------------------------------------------
-    def _cached_recording(self, key, tensors, build, rec):
-        """_cached during the recording step of _repack_weights: also notes which batchable packs build() made."""
-        tag = tuple((t._version, t.data_ptr()) for t in tensors)
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad(), ops.record_packs() as descs:
-                out = build()
-            self._cache[key] = hit = (tag, out)
-            # batchable: everything build() launched was one of the table's kinds, reading the parameter itself (not a derived copy)
-            if descs and all(any(d[1].data_ptr() == t.data_ptr() for t in tensors) for d in descs):
-                rec[key] = (tensors, out, list(descs))
-        return hit[1]
-
-    def _repack_weights(self, split=False):
-        """A training step re-packs every conv weight (the optimizer changed them all): 216 launches of 2-10 us, 6.8 % of a
-        step at 16 frames (profiles/r02_layer_profile_resnet_h_train16.txt).  The first training step records which packed copies
-        it builds from which parameter; from the second step on ONE launch (dream_pack_weights_batched: a device-resident job
-        table, blockIdx.y = job) rewrites all of them in place at the start of the step and the cache entries are stamped with
-        the parameters' new versions.  The few packs the table does not cover (tap-major copies for the direct kernel, the
-        transposed convs' phase kernels) stay lazy.  Skipped while a hipGraph capture is under way (the data-parallel replicas
-        capture their whole step, packing included)."""
-        first = next(self.parameters())
-        self._pack_join()
-        if not first.is_cuda and not os.environ.get("DREAM_PACK_BATCHED_ON_CPU"):
-            return
-        if (first.is_cuda and torch.cuda.is_current_stream_capturing()) or os.environ.get("DREAM_PACK_BATCHED", "1") == "0":
-            object.__setattr__(self, "_pack_records", None)
-            return
-        st = self.__dict__.get("_pack_state")
-        stamp = first.data_ptr()
-        if st is None or st["stamp"] != stamp:
-            st = {"stamp": stamp, "table": None, "records": {}, "steps": 0}
-            object.__setattr__(self, "_pack_state", st)
-        if st["table"] is None:
-            st["steps"] += 1
-            if st["steps"] == 1 or not st["records"]:
-                object.__setattr__(self, "_pack_records", st["records"])          # record this step's packs
-                return
-            object.__setattr__(self, "_pack_records", None)
-            st["keys"] = list(st["records"].items())
-            descs = [d for _, (_, _, ds) in st["keys"] for d in ds]
-            st["table"], st["njobs"] = ops.pack_job_table(descs, first.device), len(descs)
-            # the launch's workgroups by job size (round 6): the decoder's 2048 -> 256 transposed conv is 19 M packed floats, a 64 x 64 1x1 conv
-            # 4 K -- with 16 workgroups each the large jobs set the launch's length (0.50 ms; DREAM_PACK_SPANS=0 restores that)
-            st["spans"] = ops.pack_span_table(descs, first.device) if os.environ.get("DREAM_PACK_SPANS", "1") != "0" else None
-            # Round 6, measured and NOT adopted (DREAM_PACK_SPLIT=1 opts in): the re-pack in two launches.  The copies the stem, layer1 and
-            # layer2 read (3 % of the floats) are rewritten on the main stream; the rest -- layer3 on, the decoder, every data-gradient
-            # operator -- on the SECOND stream, which is idle during a forward pass, while the main stream runs the first seven Bottlenecks
-            # (~6 ms at 16 frames); the main stream waits for it at the first use of a late copy (_cached -> _pack_join).  One box,
-            # alternating (profiles/r06_ab_pack_split.txt): 395.4 / 395.4 / 393.9 frames/s with one launch, 392.6 / 393.4 / 396.1 with two --
-            # the 0.4-ms copy takes from the forward kernels what it saves (it moves 1.5 GB while they run).
-            st["split"] = None
-            if split and first.is_cuda and st["spans"] is not None and os.environ.get("DREAM_PACK_SPLIT", "0") == "1":
-                early = [str(key[1]).startswith(("conv1", "layer1.", "layer2.")) for key, _ in st["keys"]]
-                parts = []
-                for want in (True, False):
-                    ds = [d for (_, (_, _, dd)), e in zip(st["keys"], early) if e == want for d in dd]
-                    parts.append((ops.pack_job_table(ds, first.device), ops.pack_span_table(ds, first.device)) if ds else None)
-                if parts[0] is not None and parts[1] is not None:
-                    st["split"] = (parts[0], parts[1], frozenset(key for (key, _), e in zip(st["keys"], early) if e))
-        tags = {key: tuple((t._version, t.data_ptr()) for t in tensors) for key, (tensors, _, _) in st["keys"]}
-        if any(self._cache.get(key, (None,))[0] != tag or self._cache[key][1] is not st["records"][key][1] for key, tag in tags.items()):
-            if split and st.get("split") is not None:
-                (t0, s0), (t1, s1), early_keys = st["split"]
-                ops.pack_weights_spans(t0, s0[0], s0[1])
-                main, side = torch.cuda.current_stream(), _SideStream.live_stream(first.device)
-                side.wait_stream(main)                   # behind the optimizer step and the previous backward's reads of the old copies
-                with torch.cuda.stream(side):
-                    ops.pack_weights_spans(t1, s1[0], s1[1])
-                    object.__setattr__(self, "_pack_pending", (side.record_event(), early_keys))
-            elif st.get("spans") is not None:
-                ops.pack_weights_spans(st["table"], st["spans"][0], st["spans"][1])
-            else:
-                ops.pack_weights_batched(st["table"], st["njobs"])
-            for key, tag in tags.items():
-                self._cache[key] = (tag, st["records"][key][1])
+    def _repack_weights(self, split=False, half=False):
+        """Once per training forward pass: the store refreshes what it holds in one launch (PackedWeights.begin_step)."""
+        self._packs.begin_step(next(self.parameters()), split, half)
 
     def _fold(self, name, bn, conv_bias=None):
-        tensors = [bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv_bias] if conv_bias is not None else [])
-        return self._cached(("bn", name), tensors, lambda: ops.bn_fold(
-            bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-            conv_bias.detach() if conv_bias is not None else None))
+        """-> (scale, shift) of the eval-mode BatchNorm (and the conv's bias) for the conv's epilogue: y = conv * scale + shift."""
+        return self._w("bn", name, [bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv_bias] if conv_bias is not None else []), bn.eps)
 
-    # ---- the network, once: what every forward pass walks (the names are cache keys, _pack_state records, EARLY_BUCKET_FROM markers) ----
+    def _g(self, name, conv, mode, col3=False, half=False):
+        """-> (packed, rows) for the 1x1 GEMM, ``half``: (halfs, e_w, rows) for the fp16 one.  mode 0 = forward, 1 = data gradient;
+        ``col3``: a 3x3 conv that runs on its patch rows (ops.im2col3s2)."""
+        return self._w("g%d%s%s" % (mode, "f16" if half else "", "col3" if col3 else ""), name, conv.weight)
+
+    STEM_COLS = {"w": 160, "g0e": 160, "g0": 192}
+
+    def _stem_weight(self, kind):
+        """The 7x7 stem's weight for its im2col rows (147 taps, zero-padded to STEM_COLS[kind] columns): "w" = the 1-tap direct kernel,
+        "g0e" = the 1x1 GEMM in evaluation, "g0" = the 1x1 GEMM in training (192: the granularity of its statistics epilogue)."""
+        return self._w("stem_" + kind, "conv1", self.conv1.weight, self.STEM_COLS[kind])
+
+    # ---- the network, once: what every forward pass walks (the names are cache keys, re-pack records, EARLY_BUCKET_FROM markers) ----
     def _trunk(self):
         """(name, Bottleneck) in execution order."""
         for li in (1, 2, 3, 4):
@@ -1852,46 +1729,6 @@ class ResnetSimple(nn.Module):
                     yield "%s.%d" % (sname, i), mods[i], None
                     i += 1
 
-    # ---- packed weights: one place per cache key ----------------------------------------------------------------------------------
-    def _packed_w(self, name, conv, mode):
-        return self._cached(("w%d" % mode, name), [conv.weight], lambda: ops.pack_conv_weight(conv.weight.detach(), mode))
-
-    def _g(self, name, conv, mode, col3=False):
-        """-> (packed, rows) for the 1x1 GEMM: mode 0 = forward (key "g0"), 1 = data gradient ("g1").  ``col3``: a 3x3 conv that runs on its
-        patch rows (ops.im2col3s2), GEMM weight [Cout][t Cin + c] = w[co][c][ky][kx]."""
-        def build():
-            w = conv.weight.detach()
-            if col3:
-                w = w.permute(0, 2, 3, 1).reshape(int(w.shape[0]), -1, 1, 1).contiguous()
-            return ops.pack_conv1x1_weight(w, mode)
-        return self._cached(("g%d" % mode, name), [conv.weight], build)
-
-    def _g_head(self, name, m, mode, rows):
-        """The head conv's GEMM weight with its K output channels zero-padded to ``rows`` (keys "g0h" / "g1h") -> packed."""
-        def build():
-            cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
-            w2 = m.weight.detach().reshape(cout, cin)
-            return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((rows - cout, cin))]).reshape(rows, cin, 1, 1), mode)
-        return self._cached(("g%dh" % mode, name), [m.weight], build)[0]
-
-    def _wino(self, name, conv, mode, tile):
-        """-> (u, rows) of a stride-1 3x3 conv for the Winograd kernel of this tile: mode 0 = forward ("wino"), 1 = data gradient ("wino1")."""
-        return self._cached(("wino1" if mode else "wino", name, tile), [conv.weight],
-                            lambda: ops.pack_weight_winograd_tile(conv.weight.detach(), mode, tile))
-
-    STEM_COLS = {"w": 160, "g0e": 160, "g0": 192}
-
-    def _stem_weight(self, kind):
-        """The 7x7 stem's weight for its im2col rows (147 taps, zero-padded to STEM_COLS[kind] columns): "w" = the 1-tap direct kernel,
-        "g0e" = the 1x1 GEMM in evaluation, "g0" = the 1x1 GEMM in training (192: the granularity of its statistics epilogue)."""
-        def build():
-            w2 = self.conv1.weight.detach().reshape(64, 147)
-            if kind == "w":
-                return ops.pack_matrix_weight(w2, 160)
-            kcol = self.STEM_COLS[kind]
-            return ops.pack_conv1x1_weight(torch.cat([w2, w2.new_zeros((64, kcol - 147))], dim=1).reshape(64, kcol, 1, 1), 0)
-        return self._cached((kind, "conv1"), [self.conv1.weight], build)[0]
-
     def _gemm1x1(self, conv, x, k=None, stride=None, bwd=False):
         """Stride-1 1x1 convs with channel counts the LDS-free GEMM kernel takes (all of ResNet-101's: multiples of 64).  ``k`` / ``stride``:
         as the unit ran, where that differs from the module (a downsample conv over gathered pixels runs with stride 1).  ``bwd``: the data
@@ -1902,43 +1739,6 @@ class ResnetSimple(nn.Module):
         if bwd:
             cout, cin = cin, cout
         return self.conv1x1_algorithm == "gemm" and k == 1 and stride == 1 and cin == int(x.shape[3]) and ops.conv1x1_applies(x, cout)
-
-    def _g16(self, name, conv, mode, col3=False):
-        """_g for the fp16 GEMM -> (halfs, e_w, rows): keys "g0f16" / "g1f16"."""
-        def build():
-            w = conv.weight.detach()
-            if col3:
-                w = w.permute(0, 2, 3, 1).reshape(int(w.shape[0]), -1, 1, 1).contiguous()
-            return ops.pack_conv1x1_weight_f16(w, mode)
-        key = ("g%df16" % mode, name)
-        if not col3:                                 # packed from the parameter itself: batchable (_repack_half_weights)
-            self.__dict__.setdefault("_half_sources", {})[key] = (conv.weight, mode)
-        return self._cached(key, [conv.weight], build)
-
-    def _repack_half_weights(self):
-        """train_gemm_precision="fp16": the half copies that earlier steps built from a parameter itself (_g16; not the patch-row forms) are
-        rewritten in place by ONE batched pack at the start of the step (three launches) and their cache entries stamped with the
-        parameters' new versions -- packed one by one, three launches per copy, they cost a 16-frame step more than the fp16 GEMMs save
-        (profiles/microbench_resnet_train_precision.txt).  Skipped on the first step (nothing is cached yet), off the GPU and during a
-        hipGraph capture; what the table does not hold stays lazy."""
-        first = next(self.parameters())
-        if not first.is_cuda or torch.cuda.is_current_stream_capturing():
-            return
-        live = {key: src for key, src in self.__dict__.get("_half_sources", {}).items() if key in self._cache}
-        if not live:
-            return
-        stamp = tuple((key, self._cache[key][1][0].data_ptr(), self._cache[key][1][1].data_ptr(), src[0].data_ptr()) for key, src in live.items())
-        st = self.__dict__.get("_pack16_state")
-        if st is None or st["stamp"] != stamp:
-            entries = [(w.detach(), self._cache[key][1], mode) for key, (w, mode) in live.items()]
-            table, scratch = ops.pack16_job_table(entries, first.device)
-            st = dict(stamp=stamp, table=table, scratch=scratch)
-            object.__setattr__(self, "_pack16_state", st)
-        tags = {key: ((w._version, w.data_ptr()),) for key, (w, _) in live.items()}
-        if any(self._cache[key][0] != tag for key, tag in tags.items()):
-            ops.pack_conv1x1_weights_f16_batched(st["table"], st["scratch"])
-            for key, tag in tags.items():
-                self._cache[key] = (tag, self._cache[key][1])
 
     def _resolve_switches(self, training):
         """Reads the precision switches (_RESNET_SWITCHES), once per forward -> the _ResnetWalk of this pass; raises ValueError for an
@@ -1968,18 +1768,6 @@ class ResnetSimple(nn.Module):
         Winograd and direct convs, transposed convs (their small-map GEMM form included), head, pool -- is fp32 launch for launch."""
         return rec["kind"] == "conv" and rec.get("f16", False)
 
-    def _amax(self, device):
-        """One zero-initialised amax word per covered unit and step (ops.bn_bwd_apply_amax zeroes it again before it publishes), from a
-        persistent pool beside the ticket words (_ctr); the cursor restarts with every forward pass."""
-        buf = self._cache.get(("amaxpool",))
-        if buf is None or buf.device != device:
-            buf = self._cache[("amaxpool",)] = torch.zeros((1024,), dtype=torch.int32, device=device)
-            self._amax_pos = 0
-        if self._amax_pos >= buf.numel():
-            self._amax_pos = 0
-        self._amax_pos += 1
-        return buf[self._amax_pos - 1:self._amax_pos]
-
     def _convT_gemm(self, name, m, y):
         """Does this transposed conv run as one 1x1 GEMM (N = 16 Cout) + a gather (small maps: _convT_forward)?  -> packed weight or None."""
         co_t, npx = int(m.weight.shape[1]), int(y.shape[0]) * int(y.shape[1]) * int(y.shape[2])
@@ -1987,8 +1775,7 @@ class ResnetSimple(nn.Module):
                 and tuple(m.kernel_size) == (4, 4) and tuple(m.stride) == (2, 2) and tuple(m.padding) == (1, 1)
                 and tuple(m.output_padding) == (0, 0) and int(y.shape[3]) == int(m.weight.shape[0]) and ops.conv1x1_applies(y, 16 * co_t)):
             return None
-        return self._cached(("g0T", name), [m.weight], lambda: ops.pack_conv1x1_weight(
-            m.weight.detach().permute(2, 3, 1, 0).reshape(16 * co_t, -1, 1, 1).contiguous(), 0))
+        return self._w("g0T", name, m.weight)
 
     def _convT_forward(self, name, m, y, scale, shift, flags, gemm=True):
         """ConvTranspose2d(k4,s2,p1) * scale + shift (flags): evaluation passes the folded BatchNorm and CONV_RELU, training None, the bias
@@ -2002,9 +1789,9 @@ class ResnetSimple(nn.Module):
             return ops.col2im4s2(ops.conv1x1(y, gT[0], gT[1], None, None, None, ops.CONV_NO_KSPLIT), cout, shift, scale=scale, flags=flags)
         if self.convT_algorithm == "winograd" and ops.convT4x4_winograd_applies(y, cout):
             tile = ops.convT4x4_winograd_tile(y, cout)
-            u4, rows = self._cached(("wu4", name, tile), [m.weight], lambda: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile))
+            u4, rows = self._w("wu4", name, m.weight, tile)
             return ops.conv_transpose4x4s2_winograd_tile(tile, y, u4, rows, scale, shift, flags)
-        packed, rows = self._cached(("w", name), [m.weight], lambda: ops.pack_convT4x4_weight(m.weight.detach()))
+        packed, rows = self._w("wT", name, m.weight)
         return ops.conv_transpose4x4s2(y, packed, rows, scale, shift, flags)
 
     def half_storage_peak(self):
@@ -2059,24 +1846,6 @@ class ResnetSimple(nn.Module):
     # that produced its input.  Read again in the backward, each once per record by the two choosers (_dgrad_form, _wgrad_form):
     # ``conv1x1_algorithm``, ``bn_fusion_3x3``, ``bn_fusion_head``, ``convT_algorithm``, the forced Winograd tile and DREAM_CONVT_WGRAD
     # (ops), and ``overlap_wgrad`` / ``overlap_max_frames`` (run_backward).
-    def _ctr(self, device):
-        """Allocator of zero ticket words for the BatchNorm launches of this replica (ops.bn_counter_buffer: every launch takes its own
-        slice of one persistent buffer and leaves it zero; the cursor restarts with every forward pass)."""
-        buf = self._cache.get(("bnctr",))
-        if buf is None or buf.device != device:
-            buf = self._cache[("bnctr",)] = ops.bn_counter_buffer(device)
-            self._ctr_pos = 0
-
-        def take(n):
-            if n > buf.numel():                     # a short slice would let the kernel's ticket atomics run past the buffer
-                raise RuntimeError("dream_amd: a BatchNorm launch needs %d ticket words, the replica's buffer holds %d" % (n, buf.numel()))
-            if self._ctr_pos + n > buf.numel():
-                self._ctr_pos = 0
-            out = buf[self._ctr_pos:self._ctr_pos + n]
-            self._ctr_pos += n
-            return out
-        return take
-
     def _bn_fwd(self, rec, residual=None, materialize=True):
         """Train-mode BatchNorm (+ residual) (ReLU) of rec["z"] -> rec["y"].  bn_fusion on: the statistics in one launch of their own unless
         the producing launch finished them (rec["ab"] set), then the apply pass -- which ``materialize=False`` leaves to the consumer's
@@ -2085,7 +1854,7 @@ class ResnetSimple(nn.Module):
             rec["y"], rec["mean"], rec["invstd"] = ops.bn_train_fwd(rec["z"], rec["bn"], residual, rec["relu"])
             return
         if rec["ab"] is None:
-            rec["ab"], rec["mean"], rec["invstd"] = ops.bn_stats(rec["z"], rec["bn"], self._ctr(rec["z"].device))
+            rec["ab"], rec["mean"], rec["invstd"] = ops.bn_stats(rec["z"], rec["bn"], self._packs.tickets(rec["z"].device))
         if materialize:
             rec["y"] = ops.bn_apply_ab(rec["z"], rec["ab"], residual, rec["relu"])
 
@@ -2120,13 +1889,13 @@ class ResnetSimple(nn.Module):
         if col3 is not None or self._gemm1x1(conv, x, k, stride):
             rec["f16"] = fused and train16
             if self._half_unit(rec):
-                p16 = self._g16(name, conv, 0, col3 is not None)
+                p16 = self._g(name, conv, 0, col3 is not None, half=True)
                 rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn_f16(
-                    x, p16, p16[2], bn, self._ctr(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
+                    x, p16, p16[2], bn, self._packs.tickets(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
             elif fused:
                 packed, rows = self._g(name, conv, 0, col3 is not None)
                 rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv1x1_bn(
-                    x, packed, rows, bn, self._ctr(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
+                    x, packed, rows, bn, self._packs.tickets(x.device), pre_ab=src["ab"] if pre else None, shift=bias)
             else:
                 packed, rows = self._g(name, conv, 0, col3 is not None)
                 rec["z"] = ops.conv1x1(x, packed, rows, None, bias, None, 0)
@@ -2134,14 +1903,14 @@ class ResnetSimple(nn.Module):
             assert not pre
             if rec["wino"]:
                 tile = ops.winograd_tile(int(x.shape[1]), int(x.shape[2]), int(conv.weight.shape[1]), cout, int(x.shape[0]))
-                u, rows = self._wino(name, conv, 0, tile)
+                u, rows = self._w("wino", name, conv.weight, tile)
                 if fused and self.bn_fusion_3x3 and tile == 2 and cout % 64 == 0:
                     # the statistics ride in the F(2x2) kernel's epilogue: no separate pass over z
-                    rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv3x3_winograd_bn(x, u, rows, bn, self._ctr(x.device), shift=bias)
+                    rec["z"], rec["ab"], rec["mean"], rec["invstd"] = ops.conv3x3_winograd_bn(x, u, rows, bn, self._packs.tickets(x.device), shift=bias)
                 else:
                     rec["z"] = ops.conv3x3_winograd_tile(tile, x, u, rows, None, bias, None, 0)
             else:
-                packed, rows, _ = self._packed_w(name, conv, 0)
+                packed, rows, _ = self._w("w0", name, conv.weight)
                 rec["z"] = ops.conv2d(x, packed, rows, k, stride, None, bias, None, 0)
         tape.append(rec)
         self._bn_fwd(rec, residual, materialize)
@@ -2165,12 +1934,9 @@ class ResnetSimple(nn.Module):
         """-> (belief maps NCHW, tape)."""
         fused = self.bn_fusion
         half = self._resolve_switches(True).train16
-        self._repack_weights(split=fused)
-        if half:
-            self._repack_half_weights()
+        self._repack_weights(split=fused, half=half)
         if fused:
-            self._ctr_pos = 0
-            self._amax_pos = 0
+            self._packs.restart_pools()
         tape = []
         ho, wo = (int(x.shape[2]) + 6 - 7) // 2 + 1, (int(x.shape[3]) + 6 - 7) // 2 + 1
         stem = dict(kind="stem", conv=self.conv1, bn=self.bn1, relu=True, has_res=False, y=None, ab=None, k=1, stride=1,
@@ -2181,7 +1947,7 @@ class ResnetSimple(nn.Module):
             # for the direct kernel): the BatchNorm statistics ride in its epilogue (one pass over the 16 x 200 x 200 x 64 output less) and
             # its weight gradient runs on the GEMM-shaped kernel (0.56 -> ~0.2 ms on the MAIN stream: it is the last launch of a step)
             stem["z"], stem["ab"], stem["mean"], stem["invstd"] = ops.conv1x1_bn(
-                stem["x"], self._stem_weight("g0"), 64, self.bn1, self._ctr(stem["x"].device))
+                stem["x"], self._stem_weight("g0"), 64, self.bn1, self._packs.tickets(stem["x"].device))
         else:
             stem["z"] = ops.conv2d(stem["x"], self._stem_weight("w"), 64, 1, 1)
         self._bn_fwd(stem)
@@ -2228,14 +1994,13 @@ class ResnetSimple(nn.Module):
             elif y is None:                                   # the head conv on the 1x1 GEMM, behind the BatchNorm loader
                 cout = int(m.weight.shape[0])
                 n4 = ops.round_up(cout, 4)
-                packed = self._g_head(name, m, 0, n4)
-                bias4 = self._cached(("g0hb", name), [m.bias], lambda: torch.cat([m.bias.detach(), m.bias.new_zeros((n4 - cout,))]))
+                packed, bias4 = self._w("g0h", name, m.weight, n4), self._w("g0hb", name, m.bias, n4)
                 y = ops.nhwc_to_nchw(ops.conv1x1_pre(src["z"], packed, n4, src["ab"], bias4))
                 if n4 != cout:
                     y = y[:, :cout].contiguous()
                 tape.append(dict(kind="final", name=name, conv=m, x=src["z"], src=src, pre=True, k=1, stride=1))
             else:
-                packed, rows, _ = self._packed_w(name, m, 0)
+                packed, rows, _ = self._w("w0", name, m.weight)
                 tape.append(dict(kind="final", name=name, conv=m, x=y, src=src, pre=False, k=1, stride=1))
                 y = ops.conv2d(y, packed, rows, 1, 1, None, m.bias.detach(), None, CONV_OUT_NCHW)
         return y, tape
@@ -2281,37 +2046,37 @@ class ResnetSimple(nn.Module):
         cin = int(conv.weight.shape[1])
         half = self._half_unit(rec)               # (then dz is the tensor _unit_bwd wrote for this record, its amax in rec["dz_amax"])
         if form == "gemm_mask" and half:
-            return ("masked",) + ops.conv1x1_bwd_bnmask_f16(dz, rec["dz_amax"], self._g16(name, conv, 1), cin, p["z"],
+            return ("masked",) + ops.conv1x1_bwd_bnmask_f16(dz, rec["dz_amax"], self._g(name, conv, 1, half=True), cin, p["z"],
                                                             None if p["has_res"] else p["ab"], p["mean"], p["invstd"],
-                                                            self._ctr(dz.device), y_act=p["y"], residual=residual)
+                                                            self._packs.tickets(dz.device), y_act=p["y"], residual=residual)
         if form == "gemm_mask":
             # the head's is the same form on another packed operand: the contraction is its keypoint channels, zero-padded (dz: _bwd_final).
             # The mask: the stored activation where the forward pass wrote one, else recomputed from (z, ab) -- which a residual rules out.
-            packed_t = self._g_head(name, conv, 1, int(dz.shape[3])) if rec["kind"] == "final" else self._g(name, conv, 1)[0]
+            packed_t = self._w("g1h", name, conv.weight, int(dz.shape[3])) if rec["kind"] == "final" else self._g(name, conv, 1)[0]
             return ("masked",) + ops.conv1x1_bwd_bnmask(dz, packed_t, cin, p["z"], None if p["has_res"] else p["ab"], p["mean"], p["invstd"],
-                                                        self._ctr(dz.device), y_act=p["y"], residual=residual)
+                                                        self._packs.tickets(dz.device), y_act=p["y"], residual=residual)
         if form == "wino_mask":
             # the F(2x2) kernel; the mask is recomputed from the producer's (z, ab) exactly as its apply pass evaluated it
-            u_t, _ = self._wino(name, conv, 1, tile)
-            return ("masked",) + ops.conv3x3_winograd_bwd_bnmask(dz, u_t, cin, p["z"], p["ab"], p["mean"], p["invstd"], self._ctr(dz.device))
+            u_t, _ = self._w("wino1", name, conv.weight, tile)
+            return ("masked",) + ops.conv3x3_winograd_bwd_bnmask(dz, u_t, cin, p["z"], p["ab"], p["mean"], p["invstd"], self._packs.tickets(dz.device))
         if form == "wino":
-            u_t, rows = self._wino(name, conv, 1, tile)
+            u_t, rows = self._w("wino1", name, conv.weight, tile)
             return ops.conv3x3_winograd_tile(tile, dz, u_t, rows, None, None, residual, 0)
         if form == "col3":
             # the GEMM's data gradient is the gradient of the patch rows, summed back onto the map
             if half:
-                p16 = self._g16(name, conv, 1, col3=True)
+                p16 = self._g(name, conv, 1, col3=True, half=True)
                 return ops.col2im3s2(ops.conv1x1_f16(dz, rec["dz_amax"], p16, p16[2]), *rec["col3"])
             packed_t, rows = self._g(name, conv, 1, col3=True)
             return ops.col2im3s2(ops.conv1x1(dz, packed_t, rows, None, None, None, 0), *rec["col3"])
         if form == "gemm" and half:
-            p16 = self._g16(name, conv, 1)
+            p16 = self._g(name, conv, 1, half=True)
             g = ops.conv1x1_f16(dz, rec["dz_amax"], p16, p16[2], residual=residual)
         elif form == "gemm":
             packed_t, rows = self._g(name, conv, 1)
             g = ops.conv1x1(dz, packed_t, rows, None, None, residual, 0)
         else:
-            packed_t, rows, _ = self._packed_w(name, conv, 1)
+            packed_t, rows, _ = self._w("w1", name, conv.weight)
             g = ops.conv2d_bwd_data(dz, packed_t, cin, rec["k"], rec["stride"], (int(rec["x"].shape[1]), int(rec["x"].shape[2])), residual=residual)
         # a conv that ran on the gathered pixels (sub2): its data gradient back on the input's grid
         return g if rec.get("sub2") is None else ops.scatter2(g, *rec["sub2"])
@@ -2387,7 +2152,7 @@ class ResnetSimple(nn.Module):
         # a covered unit (train_gemm_precision="fp16"): the same apply pass also publishes max|dz|, the scale of the gradient operand that this
         # record's data- and weight-gradient GEMMs round to half (no absmax pass)
         if self._half_unit(rec):
-            amax = rec["dz_amax"] = self._amax(z.device)
+            amax = rec["dz_amax"] = self._packs.amax_word(z.device)
             apply = lambda *a, **kw: ops.bn_bwd_apply_amax(*a, amax, **kw)      # noqa: E731
         else:
             apply = ops.bn_bwd_apply
@@ -2399,7 +2164,7 @@ class ResnetSimple(nn.Module):
         else:
             y_act = rec["y"] if rec["relu"] else None
             ab = rec["ab"] if (rec["relu"] and y_act is None) else None
-            dgam, dbet = ops.bn_bwd_stats(z, dy, rec["mean"], rec["invstd"], self._ctr(z.device), y_act=y_act, ab=ab)
+            dgam, dbet = ops.bn_bwd_stats(z, dy, rec["mean"], rec["invstd"], self._packs.tickets(z.device), y_act=y_act, ab=ab)
             dz, g = apply(z, dy, bn.weight, rec["mean"], rec["invstd"], dgam, dbet, y_act=y_act, ab=ab, want_g=rec["has_res"])
         bw["grads"][bn.weight], bw["grads"][bn.bias] = dgam, dbet
         self._wgrad(rec, dz, bw)
@@ -2423,9 +2188,9 @@ class ResnetSimple(nn.Module):
         if (self.convT_algorithm == "winograd" and cout_t % 16 == 0 and cout_t >= 32 and cin_t > 64
                 and int(dz.shape[3]) == cout_t and dz.shape[1] % 2 == 0 and dz.shape[2] % 2 == 0):
             tile = ops.conv4x4s2_winograd_tile_of(dz, cin_t)
-            u4b, rows = self._cached(("wu4b", name, tile), [m.weight], lambda: ops.pack_convT4x4_winograd_weight_tile(m.weight.detach(), tile, 1))
+            u4b, rows = self._w("wu4b", name, m.weight, tile)
             return ops.conv4x4s2_winograd_tile(tile, dz, u4b, rows)
-        pk, rows = self._cached(("wTb", name), [m.weight], lambda: ops.pack_convT4x4_bwd_weight(m.weight.detach()))
+        pk, rows = self._w("wTb", name, m.weight)
         return ops.conv4x4s2(dz, pk, rows)
 
     def _bwd_block(self, blk, g, bw):

@@ -122,7 +122,7 @@ def device_block(net, name, x, gy, train_gemm_precision):
     blk = dict(net._trunk())[name]
     net.train_gemm_precision = train_gemm_precision
     half = net._resolve_switches(True).train16
-    net._ctr_pos = net._amax_pos = 0
+    net._packs.restart_pools()
     tape = []
     y = ops.nchw_to_nhwc(x)
     ds, idt = None, y

@@ -1404,10 +1404,10 @@ def test_resnet_batched_packing_equals_lazy_packing(monkeypatch):
 
     a, la, ma = run("1")
     b, lb, mb = run("0")
-    st = a.model.module._pack_state
-    assert st["table"] is not None and st["njobs"] >= 190 and "_pack_state" not in b.model.module.__dict__, st.get("njobs")
+    st = a.model.module._packs.view()
+    assert st.table_built and st.jobs >= 190 and b.model.module._packs.view().idle, st.jobs
     # round 6 (opt-in): the re-pack as two launches -- the copies layer3 and everything behind it read are rewritten on the second stream
-    assert st["split"] is not None and 0 < len(st["split"][2]) < len(st["keys"]) and a.model.module.__dict__.get("_pack_pending") is None
+    assert st.split is not None and 0 < st.split[0] < st.split[1] and not st.pending
     assert la == lb and torch.equal(ma, mb), (la, lb)
     for (k, pa), (_, pb) in zip(a.model.named_parameters(), b.model.named_parameters()):
         assert torch.equal(pa, pb), k
