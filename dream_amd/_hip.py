@@ -83,6 +83,11 @@ _SIGNATURES = {
     "dream_conv1x1_wgrad_f16_workspace": (_SZ, [_c.c_long, _I, _I]),
     "dream_conv1x1_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _c.c_long, _I, _I, _I, _P, _P]),
     "dream_bn_bwd_apply_amax_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _P]),
+    "dream_conv_transpose4x4s2_f16_sat_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_conv_transpose4x4s2_dgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_convT4x4_wgrad_f16_splitk": (_I, [_I] * 6),
+    "dream_convT4x4_wgrad_f16_workspace": (_SZ, [_I] * 6),
+    "dream_convT4x4_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

@@ -46,7 +46,15 @@ namespace {
 //                  conv3): v = acc * (2^-ew * scale) + shift + float(residual), ReLU, max|v| into the peak scalar, sat_half.
 //                  The residual is read as the pair of halfs the lane stores (4-byte aligned).  Stride-1 NHWC convs only (no pool,
 //                  upsample, NCHW)
-enum Form16 { kPlain, kMask, kAct16, kMask16, kKsplit, kG16Entry, kG16EntryMask, kG16Interior, kG16Exit, kRes16, kNumForms };
+//   convT4 dgrad   the data gradient of ConvTranspose2d(k4,s2,p1) (ResnetSimple's train_decoder_precision="fp16"): plain's
+//                  operands and epilogue over the H x W grid of dx, x = dz [B,2H,2W,Cin].  By sub-pixel phase (a, b) of dz it is four 2x2-tap
+//                  stride-1 convs whose sum is dx; ONE launch runs them into the same accumulators: the contraction is (32-channel chunk,
+//                  phase, tap), and the patch of a (chunk, phase) is gathered with position stride 2 -- dz[2 (y0 - a + py) + a][2 (x0 - b + px)
+//                  + b], (TH + 1) x (TW + 1) positions of 32 contiguous channels each.  Tap (dy, dx) of phase (a, b) multiplies slice
+//                  4 (2 dy + 1 - a) + 2 dx + 1 - b of the 16-slice plane [ky kx][CoutPad][Cin]: 16 tap products per output, no structural zeros
+//   plain, sat     plain for an operand that carries no amax (the forward of the same switch): e_a = 0, amax_in is not read, and the one rounding
+//                  saturates -- half(clamp(x, +-65504)), the activation rule of 4.8j -- so an outlier stays finite
+enum Form16 { kPlain, kMask, kAct16, kMask16, kKsplit, kG16Entry, kG16EntryMask, kG16Interior, kG16Exit, kRes16, kConvT4Dgrad, kPlainSat, kNumForms };
 
 // the flags whose launches are never split (conv_ksplit: the large-map layers and the K-channel output)
 constexpr int kKsplitRefused = DREAM_CONV_POOL2 | DREAM_CONV_UPSAMPLE2X | DREAM_CONV_ZEROSTUFF2X | DREAM_CONV_OUT_NCHW | DREAM_CONV_RELUMASK;
@@ -58,6 +66,8 @@ struct Form16Row {
     bool EPI_MASK, ACT16, MASK16, KSPLIT;     // the kernel's constants
     int GRAD16;
     bool RES16;
+    bool DGT4;                                // the convT4 dgrad loader (conv_f16_body.inc)
+    bool SAT0;                                // fp32 x rounded unscaled and saturated: amax_in is not read
     bool affine;                              // launch_f16: scale / shift may be given
     bool residual;                            //             `residual` may be a true residual (a form with EPI_MASK: it IS the mask)
     int flags_ok;                             //             the flag bits the form accepts
@@ -67,17 +77,19 @@ struct Form16Row {
     constexpr bool needs_grad_amax() const { return GRAD16 == 1 || GRAD16 == 3; }
 };
 constexpr Form16Row kForms[kNumForms] = {
-    //  name                EPI_MASK ACT16  MASK16 KSPLIT GRAD16 RES16  affine residual flags_ok
-    {"plain",               false,   false, false, false, 0,     false, true,  true,    ~DREAM_CONV_RELUMASK},
-    {"mask",                true,    false, false, false, 0,     false, true,  false,   ~0},
-    {"act16",               false,   true,  false, false, 0,     false, true,  false,   ~DREAM_CONV_RELUMASK},
-    {"mask16",              true,    false, true,  false, 0,     false, true,  false,   ~0},
-    {"ksplit",              false,   true,  false, true,  0,     false, false, false,   ~kKsplitRefused},
-    {"g16 entry",           false,   false, false, false, 1,     false, false, false,   0},
-    {"g16 entry + mask",    true,    false, true,  false, 1,     false, false, false,   DREAM_CONV_RELUMASK},
-    {"g16 interior",        true,    true,  true,  false, 2,     false, false, false,   DREAM_CONV_RELUMASK},
-    {"g16 exit",            true,    true,  true,  false, 3,     false, false, false,   DREAM_CONV_RELUMASK},
-    {"act16 + residual",    false,   true,  false, false, 0,     true,  true,  true,    ~kRes16Refused},
+    //  name                EPI_MASK ACT16  MASK16 KSPLIT GRAD16 RES16  DGT4   SAT0   affine residual flags_ok
+    {"plain",               false,   false, false, false, 0,     false, false, false, true,  true,    ~DREAM_CONV_RELUMASK},
+    {"mask",                true,    false, false, false, 0,     false, false, false, true,  false,   ~0},
+    {"act16",               false,   true,  false, false, 0,     false, false, false, true,  false,   ~DREAM_CONV_RELUMASK},
+    {"mask16",              true,    false, true,  false, 0,     false, false, false, true,  false,   ~0},
+    {"ksplit",              false,   true,  false, true,  0,     false, false, false, false, false,   ~kKsplitRefused},
+    {"g16 entry",           false,   false, false, false, 1,     false, false, false, false, false,   0},
+    {"g16 entry + mask",    true,    false, true,  false, 1,     false, false, false, false, false,   DREAM_CONV_RELUMASK},
+    {"g16 interior",        true,    true,  true,  false, 2,     false, false, false, false, false,   DREAM_CONV_RELUMASK},
+    {"g16 exit",            true,    true,  true,  false, 3,     false, false, false, false, false,   DREAM_CONV_RELUMASK},
+    {"act16 + residual",    false,   true,  false, false, 0,     true,  false, false, true,  true,    ~kRes16Refused},
+    {"convT4 dgrad",        false,   false, false, false, 0,     false, true, false,  false, false,   0},
+    {"plain, saturating",   false,   false, false, false, 0,     false, false, true,  true,  false,   ~DREAM_CONV_RELUMASK},
 };
 
 template <int FORM, int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
@@ -88,6 +100,8 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_f16_kernel(const Conv16P
     constexpr bool KSPLIT = kForms[FORM].KSPLIT;
     constexpr int GRAD16 = kForms[FORM].GRAD16;
     constexpr bool RES16 = kForms[FORM].RES16;
+    constexpr bool DGT4 = kForms[FORM].DGT4;
+    constexpr bool SAT0 = kForms[FORM].SAT0;
 #include "conv_f16_body.inc"
 }
 
@@ -180,7 +194,7 @@ struct Variant16h {
     {conv_f16_kernel<kPlain, __VA_ARGS__>, conv_f16_kernel<kMask, __VA_ARGS__>, conv_f16_kernel<kAct16, __VA_ARGS__>, \
      conv_f16_kernel<kMask16, __VA_ARGS__>, conv_f16_kernel<kKsplit, __VA_ARGS__>, conv_f16_kernel<kG16Entry, __VA_ARGS__>, \
      conv_f16_kernel<kG16EntryMask, __VA_ARGS__>, conv_f16_kernel<kG16Interior, __VA_ARGS__>, conv_f16_kernel<kG16Exit, __VA_ARGS__>, \
-     conv_f16_kernel<kRes16, __VA_ARGS__>}
+     conv_f16_kernel<kRes16, __VA_ARGS__>, conv_f16_kernel<kConvT4Dgrad, __VA_ARGS__>, conv_f16_kernel<kPlainSat, __VA_ARGS__>}
 // Tile shapes are the split kernel's; "db" / "sb": double- / single-buffered patch.
 const Variant16h kVariantsF16[] = {
     {"f16 m2n2w2x2 db", 128, 128, 192, 256, 2, F16_KERNELS(2, 2, 2, 2, 192, true)},
@@ -239,7 +253,7 @@ int launch_f16(Form16 form, const void *x, const unsigned *amax_in, const void *
                const float *shift, const void *residual, void *y, unsigned *amax_out, int B, int Cin, int Cout, int CoutPad,
                const Geom16 &g, int flags, void *stream, int ksplit = 0, const unsigned *grad_amax = nullptr) {
     const Form16Row &f = kForms[form];
-    DREAM_REQUIRE(x && (amax_in || f.x16()) && w && w_exp && y, "conv_f16: null pointer");
+    DREAM_REQUIRE(x && (amax_in || f.x16() || f.SAT0) && w && w_exp && y, "conv_f16: null pointer");
     DREAM_REQUIRE((flags & ~f.flags_ok) == 0, "conv_f16: the %s form does not take flags %d", f.name, flags & ~f.flags_ok);
     DREAM_REQUIRE(f.affine || (scale == nullptr && shift == nullptr), "conv_f16: the %s form takes no scale / shift", f.name);
     DREAM_REQUIRE(f.EPI_MASK || f.residual || residual == nullptr, "conv_f16: the %s form takes no residual", f.name);
@@ -349,11 +363,53 @@ extern "C" int dream_conv_transpose4x4s2_f16_nhwc_f32(const float *x, const unsi
     return convT4_f16(kPlain, x, amax_in, w, w_exp, scale, shift, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
 }
 
+// ... for an activation without an amax (ResnetSimple's train_decoder_precision="fp16"): x rounded as half(clamp(x, +-65504)),
+// e_x = 0 -- the saturating plain form; everything else as above.
+extern "C" int dream_conv_transpose4x4s2_f16_sat_nhwc_f32(const float *x, const void *w, const int *w_exp, const float *scale,
+                                                          const float *shift, float *y, int B, int H, int W, int Cin, int Cout, int CoutPad,
+                                                          int flags, void *stream) {
+    return convT4_f16(kPlainSat, x, nullptr, w, w_exp, scale, shift, y, nullptr, B, H, W, Cin, Cout, CoutPad, flags, stream);
+}
+
 // ConvTranspose2d(k=3,s=2,p=1,output_padding 1) on the fp16 path: the phases of dream_conv_transpose3x3s2_f16x3_nhwc_f32.
 extern "C" int dream_conv_transpose3x3s2_f16_nhwc_f32(const float *x, const unsigned *amax_in, const void *w, const int *w_exp,
                                                       const float *bias, float *y, unsigned *amax_out, int B, int H, int W,
                                                       int Cin, int Cout, int CoutPad, int flags, void *stream) {
     return convT3_f16(kPlain, x, amax_in, w, w_exp, bias, y, amax_out, B, H, W, Cin, Cout, CoutPad, flags, stream);
+}
+
+// ---- ResnetSimple's train_decoder_precision="fp16" (DESIGN.md 4.8n): the data gradient of ConvTranspose2d(k4,s2,p1) -- the 4x4 stride-2
+// pad-1 conv of dz (dream/models.py:37-136: the decoder stages, reached from loss.backward()) -- in ONE launch of the convT4 dgrad form ----
+namespace {
+
+// the H x W grid of dx; a (TH + 1) x (TW + 1) patch of one sub-pixel phase of dz and its 2 x 2 taps
+Geom16 geom16_convT4_dgrad(int H, int W) {
+    Geom16 g;
+    g.H = H; g.W = W; g.Hin = H; g.Win = W; g.Hs = 2 * H; g.Ws = 2 * W; g.Ho = H; g.Wo = W;
+    g.pad = 0; g.kext = 2; g.ntaps = 4;
+    for (int t = 0; t < 4; ++t) { g.tap_dy[t] = t >> 1; g.tap_dx[t] = t & 1; }
+    g.out_scale = 1; g.out_oy = 0; g.out_ox = 0;
+    return g;
+}
+
+}  // namespace
+
+// dz [B,Ho,Wo,Cdz] fp32 (Ho, Wo even), amax_dz: device scalar, bit pattern of (an upper bound of) max|dz| -> dx [B,Ho/2,Wo/2,Cdx] fp32:
+//   dx[b,i,j,ci] = 2^-(eg+ew) sum_{ty,tx in 0..3} sum_co fp16(dz 2^eg)[b,2i+ty-1,2j+tx-1,co] * w[4 ty + tx][ci][co],   zero outside the map,
+// w: halfs [16][CdxPad][Cdz] of wT[ci][co][ty][tx] * 2^ew (dream_pack_conv_weight_f16x3's `hi` plane of the [Cdx,Cdz,4,4] tensor, mode 0),
+// w_exp: its exponent.  Cdz % 32 == 0; dz and w 16-byte aligned; flags must be 0.
+extern "C" int dream_conv_transpose4x4s2_dgrad_f16_nhwc_f32(const float *dz, const unsigned *amax_dz, const void *w, const int *w_exp,
+                                                            float *dx, int B, int Ho, int Wo, int Cdz, int Cdx, int CdxPad, int flags,
+                                                            void *stream) {
+    DREAM_REQUIRE(flags == 0, "conv_transpose4x4s2_dgrad_f16: flags %d not supported", flags);
+    DREAM_REQUIRE(B >= 1 && Ho >= 2 && Wo >= 2 && Ho % 2 == 0 && Wo % 2 == 0,
+                  "conv_transpose4x4s2_dgrad_f16: dz of %d x %d: the output of the transposed conv has even dimensions", Ho, Wo);
+    DREAM_REQUIRE(Cdz >= KC && Cdz % KC == 0 && Cdx >= 1, "conv_transpose4x4s2_dgrad_f16: Cdz=%d must be a multiple of %d", Cdz, KC);
+    DREAM_REQUIRE((size_t)Ho * Wo * (size_t)Cdz < ((size_t)1 << 31), "conv_transpose4x4s2_dgrad_f16: a frame of dz exceeds 2^31 elements");
+    DREAM_REQUIRE(dz && w && dx && ((((size_t)dz | (size_t)w) & 15) == 0) && ((size_t)dx & 3) == 0,
+                  "conv_transpose4x4s2_dgrad_f16: dz and w must be 16-byte aligned, dx 4-byte");
+    return launch_f16(kConvT4Dgrad, dz, amax_dz, w, w_exp, nullptr, nullptr, nullptr, dx, nullptr, B, Cdz, Cdx, CdxPad,
+                      geom16_convT4_dgrad(Ho / 2, Wo / 2), 0, stream);
 }
 
 // ---- activations stored as IEEE half (activation_storage="fp16") -----------------------------------------------------------------

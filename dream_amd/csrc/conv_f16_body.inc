@@ -7,7 +7,11 @@
 // spread over the first slices -- whose raw fp32 accumulators go to p.y = workspace[slice] in NHWC fp32: no scale, no shift, no ReLU,
 // no peak; conv_f16_ksplit_finish_kernel sums the slices and runs the epilogue) and GRAD16 (int constant, read by the epilogue: the
 // entry / interior / exit form of a half-stored data gradient, 0 otherwise; the loader follows ACT16 as ever) and RES16 (bool constant,
-// read by the epilogue: `residual` is a tensor of IEEE halfs).
+// read by the epilogue: `residual` is a tensor of IEEE halfs) and DGT4 (bool constant: the data gradient of ConvTranspose2d(k4,s2,p1) -- p.x is
+// dz [B, 2 p.H, 2 p.W, Cin]; the contraction runs over (32-channel chunk, sub-pixel phase (a, b) of dz, tap): a "chunk" of the loop below is
+// one (channel chunk, phase), numbered 4 * chunk + phase, whose patch row py / column px is dz[2 (y0 - a + py) + a][2 (x0 - b + px) + b] --
+// zero outside the map -- and whose tap (dy, dx) multiplies weight slice 4 (2 dy + 1 - a) + 2 dx + 1 - b; p.tap_dy / p.tap_dx hold the 2 x 2
+// taps, p.tap_w is not read) and SAT0 (bool constant, fp32 x: p.amax_in is not read, e_a = 0, and the rounding saturates to +-65504).
     constexpr int NT = 64 * WM * WN;                // 4 or 8 wavefronts per workgroup
     constexpr int BN = 32 * NR * WN;
     constexpr int QW = ACT16 ? 8 : 4;               // elements of a 16-byte piece
@@ -42,7 +46,7 @@
 
     // input scale: max|x| * 2^ea in [2^13, 2^14); stored halfs (ACT16) are the operand as they are: ea = 0, amax_in is not read
     int ea = 0;
-    if constexpr (!ACT16) {
+    if constexpr (!ACT16 && !SAT0) {             // (SAT0: an operand without an amax, rounded unscaled and saturated below)
         const unsigned abits = *p.amax_in;
         const int aexp = (int)((abits >> 23) & 255) - 127;
         ea = (abits == 0u) ? 0 : 13 - aexp;
@@ -52,12 +56,18 @@
     const float inv = pow2f(-(ea + *p.w_exp) < -126 ? -126 : (-(ea + *p.w_exp) > 127 ? 127 : -(ea + *p.w_exp)));
 
     int a_goff[NA_IT], a_soff[NA_IT];
+    int a_pyx[DGT4 ? NA_IT : 1];                     // (DGT4) patch row << 16 | patch column: the address follows the phase
 #pragma unroll
     for (int it = 0; it < NA_IT; ++it) {
         const int idx = tid + it * NT;
         const int pp = idx / Q, q = idx % Q;
         a_soff[it] = (pp < NP) ? pp * S16 + q * QW : -1;
         const int py = pp / PW, px = pp - py * PW;
+        if constexpr (DGT4) {
+            a_goff[it] = q * QW;
+            a_pyx[it] = (py << 16) | px;
+            continue;
+        }
         const int gy = y0 * p.in_scale - p.pad_y + py * p.in_step, gx = x0 * p.in_scale - p.pad_x + px * p.in_step;
         const bool inb = (pp < NP) && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win && !(zst && ((gy | gx) & 1));
         const int sy = ups ? (gy >> 1) : gy, sx = ups ? (gx >> 1) : gx;
@@ -99,7 +109,16 @@
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
     auto load_a = [&](int c0) {
-        if constexpr (ACT16) {
+        if constexpr (DGT4) {
+            // c0 = KC * (4 * channel chunk + phase): the phase's patch, gathered with position stride 2 (32 contiguous channels a position)
+            const int sc = c0 / KC, pa = (sc >> 1) & 1, pb = sc & 1, cc = (sc >> 2) * KC;
+#pragma unroll
+            for (int it = 0; it < NA_IT; ++it) {
+                const int u = y0 - pa + (a_pyx[it] >> 16), v = x0 - pb + (a_pyx[it] & 0xffff);
+                const bool inb = a_soff[it] >= 0 && u >= 0 && u < p.H && v >= 0 && v < p.W;
+                a_reg[it] = inb ? *(const f32x4 *)(xb + ((2 * u + pa) * p.Ws + 2 * v + pb) * p.Cin + a_goff[it] + cc) : zero4;
+            }
+        } else if constexpr (ACT16) {
             const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int it = 0; it < NA_IT; ++it)
@@ -122,14 +141,23 @@
                 if (a_soff[it] >= 0) {
                     f16x4 h;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) h[k] = (_Float16)(a_reg[it][k] * sa);
+                    for (int k = 0; k < 4; ++k) {
+                        if constexpr (SAT0) h[k] = (_Float16)fminf(fmaxf(a_reg[it][k], -65504.0f), 65504.0f);
+                        else h[k] = (_Float16)(a_reg[it][k] * sa);
+                    }
                     *(f16x4 *)(d + a_soff[it]) = h;
                 }
             }
         }
     };
     auto load_b = [&](int tap, int c0) {
-        const size_t base = (size_t)((p.tap_w >> (4 * tap)) & 15) * w_tap_stride + c0;
+        size_t base;
+        if constexpr (DGT4) {
+            const int sc = c0 / KC, pa = (sc >> 1) & 1, pb = sc & 1;
+            base = (size_t)(4 * (2 * (tap >> 1) + 1 - pa) + 2 * (tap & 1) + 1 - pb) * w_tap_stride + (sc >> 2) * KC;
+        } else {
+            base = (size_t)((p.tap_w >> (4 * tap)) & 15) * w_tap_stride + c0;
+        }
 #pragma unroll
         for (int it = 0; it < NB_IT; ++it)
             if (b_soff[it] >= 0) b_reg[it] = *(const f16x8 *)(p.w_hi + base + b_goff[it]);
@@ -141,7 +169,7 @@
             if (b_soff[it] >= 0) *(f16x8 *)(d + b_soff[it]) = b_reg[it];
     };
 
-    const int nchunks = p.Cin / KC;
+    const int nchunks = DGT4 ? 4 * (p.Cin / KC) : p.Cin / KC;
     // KSPLIT: this workgroup runs the stages [ks_first, ks_end) of the launch's nchunks * ntaps
     int ks_first = 0, ks_end = 0;
     if constexpr (KSPLIT) {

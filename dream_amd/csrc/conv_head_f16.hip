@@ -26,7 +26,7 @@ struct Head16Params {
 template <int MR, int NR, int WM, int WN, int NPM, bool DB, bool PRIO = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2) convT4_head_f16_kernel(const Conv16Params p, const Head16Params h) {
     // the act16 form of conv_f16_kernel (conv_f16.hip, kForms)
-    constexpr bool EPI_MASK = false, ACT16 = true, MASK16 = false, KSPLIT = false, RES16 = false;
+    constexpr bool EPI_MASK = false, ACT16 = true, MASK16 = false, KSPLIT = false, RES16 = false, DGT4 = false, SAT0 = false;
     constexpr int GRAD16 = 0;
 #define CONV_F16_BODY_EPILOGUE "conv_f16_head.inc"
 #include "conv_f16_body.inc"

@@ -353,9 +353,39 @@ __global__ void __launch_bounds__(256) gemm1x1_f16_pack_kernel(const float *w, _
 // grid = (workgroups per job, jobs)) instead of three per copy: a training step re-packs each weight after the optimizer changed it,
 // and at 16 frames the 2 x 70 half copies of ResNet-101 packed one by one cost more than the fp16 GEMMs save (pack_batched.hip tells
 // the same story for the fp32 copies).  Same values, bit for bit: the maximum does not depend on the order it is taken in.
+// Modes 2 / 3 (ResnetSimple's train_decoder_precision="fp16"): src is a ConvTranspose2d(k4,s2,p1) weight [cout = Cin_T][cin =
+// Cout_T][4][4]; 2 = the sub-pixel phase planes [phase][tap][RowsPad][ColsPad] of dream_pack_convT4x4_weight_f16x3's `hi`, 3 = the 16-slice
+// plane [4 ty + tx][RowsPad][ColsPad] of dream_pack_conv_weight_f16x3's `hi` (mode 0 of the tensor read as [O = Cin_T, I = Cout_T]); rows padded
+// to 128 (dream_conv3x3_cout_pad), columns to 32, as ops.py allocates them.  The one-tensor packers' halfs and exponents, bit for bit.
+DREAM_DEVICE void pack16_convT4_body(const float *wT, _Float16 *hi, const unsigned *amax, int *exp_out, int CinT, int CoutT, int mode, int blk,
+                                     int nblk) {
+    const int e = scale_exponent(*amax);
+    const float s = pow2_of(e);
+    if (blk == 0 && threadIdx.x == 0) *exp_out = e;
+    const int rows = mode == 2 ? CoutT : CinT, cols = mode == 2 ? CinT : CoutT;
+    const int RowsPad = (rows + 127) / 128 * 128, ColsPad = (cols + 31) / 32 * 32;
+    const size_t total = (size_t)16 * RowsPad * ColsPad;
+    for (size_t idx = (size_t)blk * 256 + threadIdx.x; idx < total; idx += (size_t)nblk * 256) {
+        const int c = (int)(idx % ColsPad);
+        const size_t q = idx / ColsPad;
+        const int r = (int)(q % RowsPad), pt = (int)(q / RowsPad);
+        float v = 0.0f;
+        if (r < rows && c < cols) {
+            if (mode == 2) {
+                const int ph = pt >> 2, t = pt & 3;
+                const int ky = 3 - 2 * (t >> 1) - (ph >> 1), kx = 3 - 2 * (t & 1) - (ph & 1);
+                v = wT[(((size_t)c * CoutT + r) * 4 + ky) * 4 + kx];
+            } else {
+                v = wT[((size_t)r * CoutT + c) * 16 + pt];
+            }
+        }
+        hi[idx] = (_Float16)(v * s);
+    }
+}
+
 __global__ void __launch_bounds__(256) pack16_amax_batched_kernel(const dream_pack16_job *jobs) {
     const dream_pack16_job j = jobs[blockIdx.y];
-    const size_t n = (size_t)j.cout * j.cin;
+    const size_t n = (size_t)j.cout * j.cin * (j.mode >= 2 ? 16 : 1);
     float m = 0.0f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(j.src[i]));
     publish_amax(j.scratch, m);
@@ -363,6 +393,10 @@ __global__ void __launch_bounds__(256) pack16_amax_batched_kernel(const dream_pa
 
 __global__ void __launch_bounds__(256) pack16_batched_kernel(const dream_pack16_job *jobs) {
     const dream_pack16_job j = jobs[blockIdx.y];
+    if (j.mode >= 2) {
+        pack16_convT4_body(j.src, (_Float16 *)j.dst, j.scratch, j.exp, j.cout, j.cin, j.mode, (int)blockIdx.x, (int)gridDim.x);
+        return;
+    }
     pack16_body(j.src, (_Float16 *)j.dst, j.scratch, j.exp, j.cout, j.cin, j.mode, (int)blockIdx.x, (int)gridDim.x);
 }
 

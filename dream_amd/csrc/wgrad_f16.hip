@@ -113,6 +113,156 @@ __global__ void __launch_bounds__(256) wgrad_f16_reduce_g16_kernel(const float *
     }
 }
 
+// ---- ResnetSimple's train_decoder_precision="fp16" (DESIGN.md 4.8n): the weight gradient of ConvTranspose2d(k4,s2,p1) ---------------------
+//   dW[ci][co][ty][tx] = 2^-eg * sum over (b, i, j) of  fp16(clamp(x[b,i,j,ci])) * fp16(dz[b, 2i+ty-1, 2j+tx-1, co] * 2^eg)
+// Sixteen 32 x 32 tap accumulators do not fit beside the operands (the 3x3 kernel's nine sit on the 256-VGPR limit), so a workgroup owns ONE
+// sub-pixel phase (a, b) of dz: against the phase plane P[u][v] = dz[2u+a][2v+b] the four taps ty = 2 dy + 1 - a, tx = 2 dx + 1 - b are the
+// 2 x 2 taps P[i - a + dy][j - b + dx] of a stride-1 problem -- the 3x3 kernel's scheme with 4 accumulators, a 9-row patch and TWO shifted
+// copies.  x plays the unshifted operand (rows of the dW tile: ci), dz the patch (columns: co); dz is staged with position stride 2, 4
+// contiguous channels a lane and position.  x is a ReLU output: e_x = 0, clamped to +-65504 (4.8j).  Split over position tiles into
+// part[ks][16][RowsPad][Cdz] (every tap is written by exactly one phase), summed in slice order and scaled by wgrad_f16_reduce_kernel.
+constexpr int TPH = TH + 1;                              // patch rows of a phase
+constexpr int SXT = TPH * TW + 8;                        // halfs per dz channel of one shifted copy (304 B: 19 16-byte slots)
+constexpr size_t LDS_BYTES_T4 = ((size_t)RW * SY + (size_t)2 * CW * SXT) * sizeof(_Float16);
+
+struct WgradT4Params {
+    const float *x;          // [B,H,W,Cin]
+    const float *dz;         // [B,2H,2W,Cdz]
+    const unsigned *amax_dz;
+    float *part;             // [splitk][16][RowsPad][Cdz]
+    int B, H, W, Cin, Cdz, RowsPad;
+    int tiles_x, tiles_y, tiles_total, splitk, nrb, ncb;
+};
+
+__global__ void __launch_bounds__(256, 2) wgrad_convT4_f16_kernel(const WgradT4Params p) {
+    DREAM_DYNAMIC_LDS(_Float16, smem);
+    _Float16 *sY = smem;                  // [RW][SY]      x, transposed: [ci][position]
+    _Float16 *sX = smem + RW * SY;        // [2][CW][SXT]  the phase's dz patch, transposed, shifted by dx = 0 | 1
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+    const int wo = wave >> 1, wi = wave & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int nblk = p.nrb * p.ncb * 4;
+    const int blk = slot % nblk, ks = (slot / nblk) * 8 + xcd;
+    if (ks >= p.splitk) return;
+    const int ph = blk & 3, pa = ph >> 1, pb = ph & 1;
+    const int rbk = (blk >> 2) % p.nrb, cbk = (blk >> 2) / p.nrb;
+    const int ci0 = rbk * RW, co0 = cbk * CW;
+    const float sg = pow2f(scale_exponent(*p.amax_dz));
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int q = tid & 15;                          // channel quad of the staging
+    const int grp = tid >> 4;                        // x staging: the 8 positions (ty = grp >> 1, tx = 8 * (grp & 1) ..)
+    const bool x_chan_ok = ci0 + q * 4 < p.Cin;      // channel counts are multiples of 4
+    const bool g_chan_ok = co0 + q * 4 < p.Cdz;
+    const int Ho = 2 * p.H, Wo = 2 * p.W;
+
+    for (int tile = ks; tile < p.tiles_total; tile += p.splitk) {
+        int t = tile;
+        const int tix = t % p.tiles_x;
+        t /= p.tiles_x;
+        const int tiy = t % p.tiles_y;
+        const int b = t / p.tiles_y;
+        const int y0 = tiy * TH, x0 = tix * TW;
+        const float *xb = p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;
+        const float *gb = p.dz + (size_t)b * Ho * Wo * p.Cdz + co0 + q * 4;
+
+        __syncthreads();                             // previous tile fully consumed
+        // ---- x: 8 consecutive positions x 4 channels per thread (loads from clamped, always-legal addresses + a select) --------------
+        {
+            const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
+            f32x4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const bool ok = x_chan_ok && oy < p.H && ox0 + j < p.W;
+                v[j] = *(const f32x4 *)(ok ? xb + ((size_t)oy * p.W + ox0 + j) * p.Cin : p.x);
+                v[j] = ok ? v[j] : zero4;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f16x8 h;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) h[j] = (_Float16)fminf(fmaxf(v[j][c], -65504.0f), 65504.0f);      // the one rounding of x
+                *(f16x8 *)(sY + (q * 4 + c) * SY + grp * 8) = h;
+            }
+        }
+        // ---- dz: 9 positions of a patch row of the phase (position stride 2) x 4 channels per unit; two shifted copies ---------------
+        for (int u = tid >> 4; u < TPH * 2; u += 16) {
+            const int py = u >> 1, half = u & 1;
+            const int gu = y0 - pa + py, gv0 = x0 - pb + half * 8;
+            f16x4 h[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {
+                const bool ok = g_chan_ok && gu >= 0 && gu < p.H && gv0 + j >= 0 && gv0 + j < p.W;
+                f32x4 v = *(const f32x4 *)(ok ? gb + ((size_t)(2 * gu + pa) * Wo + 2 * (gv0 + j) + pb) * p.Cdz : p.dz);
+                v = ok ? v : zero4;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) h[j][c] = (_Float16)(v[c] * sg);      // the one rounding of dz
+            }
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    f16x8 piece;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) piece[j] = h[j + dx][c];
+                    *(f16x8 *)(sX + (dx * CW + q * 4 + c) * SXT + py * TW + half * 8) = piece;
+                }
+        }
+        __syncthreads();
+
+        // ---- k-steps: one tile row (16 positions) each; patch row s + dy serves tap row dy -------------------------------------------
+        const _Float16 *aY = sY + (wo * 32 + li) * SY + lh * 8;
+        const _Float16 *bX = sX + (wi * 32 + li) * SXT + lh * 8;
+        f16x8 row[2][2];                             // [patch row % 2][shift]
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) row[0][dx] = *(const f16x8 *)(bX + dx * CW * SXT);
+#pragma unroll
+        for (int s = 0; s < TH; ++s) {
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) row[(s + 1) % 2][dx] = *(const f16x8 *)(bX + dx * CW * SXT + (s + 1) * TW);
+            const f16x8 a = *(const f16x8 *)(aY + s * TW);
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) acc[dy * 2 + dx] = mfma_f32_32x32x16_f16(a, row[(s + dy) % 2][dx], acc[dy * 2 + dx]);
+        }
+    }
+
+    // ---- partials (still in the scaled domain): tap (dy, dx) of this phase is slice 4 (2 dy + 1 - a) + 2 dx + 1 - b ---------------------
+#pragma unroll
+    for (int tp = 0; tp < 4; ++tp) {
+        const int slice = 4 * (2 * (tp >> 1) + 1 - pa) + 2 * (tp & 1) + 1 - pb;
+        float *part = p.part + ((size_t)ks * 16 + slice) * p.RowsPad * p.Cdz;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = ci0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int i = co0 + wi * 32 + li;
+            if (o < p.RowsPad && i < p.Cdz) part[(size_t)o * p.Cdz + i] = acc[tp][r];
+        }
+    }
+}
+
+int plan_splitk_T4(int B, int H, int W, int Cdz, int RowsPad) {
+    const long tiles = (long)B * ceil_div(H, TH) * ceil_div(W, TW);
+    const long ctiles = (long)ceil_div(RowsPad, RW) * ceil_div(Cdz, CW) * 4;      // x 4 phases
+    long sk = wgrad_target_workgroups(512) / ctiles;
+    if (sk < 1) sk = 1;
+    if (sk > tiles) sk = tiles;
+    if (sk > 1024) sk = 1024;
+    return (int)sk;
+}
+
+bool shape_ok_T4(int B, int H, int W, int Cin, int Cdz, int RowsPad) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 32 == 0 && Cdz > 0 && Cdz % 4 == 0 && RowsPad >= Cin && RowsPad % 64 == 0;
+}
+
 int plan_splitk(int B, int H, int W, int Cin, int RowsPad) {
     const long tiles = (long)B * ceil_div(H, TH) * ceil_div(W, TW);
     const long ctiles = (long)ceil_div(RowsPad, RW) * ceil_div(Cin, CW);
@@ -219,4 +369,48 @@ extern "C" int dream_conv3x3_wgrad_f16_x16_dy16_nhwc_f32(const void *x, const vo
                                                          float *dbias, void *workspace, int B, int H, int W, int Cin, int Cdy,
                                                          int RowsPad, int flags, void *stream) {
     return launch_wgrad16(kWgradX16Dy16, x, nullptr, dy, grad_amax, dw_packed, dbias, workspace, B, H, W, Cin, Cdy, RowsPad, flags, stream);
+}
+
+// ---- the weight gradient of ConvTranspose2d(k4,s2,p1) on the fp16 matrix cores (ResnetSimple's train_decoder_precision="fp16"; replaces
+// ATen's conv-transpose backward-weight reached from loss.backward() for the decoder stages of dream/models.py:37-136) ------------------
+// position slices of this problem (a pure host computation: no GPU is touched); 0 for a shape the launch refuses
+extern "C" int dream_convT4x4_wgrad_f16_splitk(int B, int H, int W, int Cin, int Cdz, int RowsPad) {
+    return shape_ok_T4(B, H, W, Cin, Cdz, RowsPad) ? plan_splitk_T4(B, H, W, Cdz, RowsPad) : 0;
+}
+
+extern "C" size_t dream_convT4x4_wgrad_f16_workspace(int B, int H, int W, int Cin, int Cdz, int RowsPad) {
+    if (!shape_ok_T4(B, H, W, Cin, Cdz, RowsPad)) return 0;
+    return (size_t)plan_splitk_T4(B, H, W, Cdz, RowsPad) * 16 * RowsPad * Cdz * sizeof(float);
+}
+
+// x [B,H,W,Cin] fp32 (a ReLU output: rounded as it is, clamped to +-65504), dz [B,Ho,Wo,Cdz] fp32 with Ho = 2 H, Wo = 2 W, amax_dz: device
+// scalar, bit pattern of (an upper bound of) max|dz| -> dw_packed [16][RowsPad][Cdz], slice 4 ty + tx (dream_unpack_conv_weight gives
+// [Cin,Cdz,4,4]).  Cin % 32 == 0, Cdz % 4 == 0, RowsPad >= Cin a multiple of 64; x, dz, dw_packed and the workspace 16-byte aligned; flags 0.
+extern "C" int dream_convT4x4_wgrad_f16_nhwc_f32(const float *x, const float *dz, const unsigned *amax_dz, float *dw_packed, void *workspace,
+                                                 int B, int Ho, int Wo, int Cin, int Cdz, int RowsPad, int flags, void *stream) {
+    DREAM_REQUIRE(flags == 0, "convT4x4_wgrad_f16: flags %d not supported", flags);
+    DREAM_REQUIRE(Ho >= 2 && Wo >= 2 && Ho % 2 == 0 && Wo % 2 == 0,
+                  "convT4x4_wgrad_f16: dz of %d x %d: the output of the transposed conv has even dimensions", Ho, Wo);
+    const int H = Ho / 2, W = Wo / 2;
+    DREAM_REQUIRE(shape_ok_T4(B, H, W, Cin, Cdz, RowsPad),
+                  "convT4x4_wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdz %d, pad %d): Cin %% 32, Cdz %% 4, pad %% 64", B, H, W, Cin, Cdz, RowsPad);
+    DREAM_REQUIRE((size_t)B * Ho * Wo * (size_t)(Cin > Cdz ? Cin : Cdz) < ((size_t)1 << 40), "convT4x4_wgrad_f16: tensor too large");
+    DREAM_REQUIRE(x && dz && amax_dz && dw_packed && workspace, "convT4x4_wgrad_f16: null pointer");
+    DREAM_REQUIRE((((size_t)x | (size_t)dz | (size_t)dw_packed | (size_t)workspace) & 15) == 0, "convT4x4_wgrad_f16: pointers must be 16-byte aligned");
+    WgradT4Params p;
+    p.x = x; p.dz = dz; p.amax_dz = amax_dz; p.part = (float *)workspace;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cdz = Cdz; p.RowsPad = RowsPad;
+    p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
+    p.tiles_total = B * p.tiles_x * p.tiles_y;
+    p.splitk = plan_splitk_T4(B, H, W, Cdz, RowsPad);
+    p.nrb = ceil_div(RowsPad, RW); p.ncb = ceil_div(Cdz, CW);
+    if (dream_allow_full_lds((const void *)wgrad_convT4_f16_kernel)) return 2;
+    const dim3 grid((unsigned)(p.nrb * p.ncb * 4 * ceil_div(p.splitk, 8) * 8));
+    hipLaunchKernelGGL(wgrad_convT4_f16_kernel, grid, dim3(256), LDS_BYTES_T4, (hipStream_t)stream, p);
+    DREAM_LAUNCH_OK();
+    const size_t n = (size_t)16 * RowsPad * Cdz;
+    hipLaunchKernelGGL(wgrad_f16_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256 > 2048 ? 2048 : (n / 4 + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const float *)p.part, dw_packed, n, p.splitk, (const unsigned *)nullptr, amax_dz);
+    DREAM_LAUNCH_OK();
+    return 0;
 }

@@ -81,6 +81,8 @@ _Walk = collections.namedtuple("_Walk", "family act16 ksplit half_train store16 
 _RESNET_SWITCHES = (
     ("precision", None, (), "inference"),
     ("train_gemm_precision", ("fp32", "fp16"), (("bn_fusion", True), ("conv1x1_algorithm", "gemm")), "training"),
+    # (needs bn_fusion: the scale of a covered record's gradient operand is published by the fused BatchNorm backward's apply pass)
+    ("train_decoder_precision", ("fp32", "fp16"), (("bn_fusion", True),), "training"),
     ("inference_activation_storage", ("fp32", "fp16"), (("precision", "fp16"),), "inference"),
     ("inference_conv_ksplit", ("off", "auto"), (("precision", "fp16"), ("inference_activation_storage", "fp16")), "inference"),
     ("inference_head_fusion", ("off", "on"), (("precision", "fp16"), ("inference_activation_storage", "fp16")), "inference"),
@@ -88,7 +90,7 @@ _RESNET_SWITCHES = (
 # ``family``: as in _Walk; ``act16``: the evaluation walk stores its activations as half; ``train16``: the covered units of a training
 # pass (ResnetSimple._half_unit) run in half precision; ``ksplit``: the half-stored evaluation walk may split a small launch;
 # ``fuse_head``: it runs its last decoder stage and the head as one entry point where that entry applies.
-_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16 ksplit fuse_head")
+_ResnetWalk = collections.namedtuple("_ResnetWalk", "family act16 train16 ksplit fuse_head dec16")
 
 
 class _PeakScalar:
@@ -160,6 +162,7 @@ class DreamHourglass(nn.Module):
     OVERLAP_MAX_PIXELS = int(os.environ.get("DREAM_VGG_OVERLAP_MAX_FRAMES", "16")) * 400 * 400
     # (ResnetSimple's switch: its last decoder stage and 1x1 head as one launch per phase)
     inference_head_fusion = _FixedSwitch("off", "DreamHourglass does not fuse its head", "the fused entry is ResnetSimple's ConvTranspose2d(256,256,4,2,1) + 1x1 head")
+    train_decoder_precision = _FixedSwitch("fp32", "DreamHourglass has no ConvTranspose2d(k4,s2,p1) decoder", "its half-precision training is train_precision")
 
     def __init__(self, n_keypoints, n_image_input_channels=3, internalize_spatial_softmax=True,
                  learned_beta=True, initial_beta=1.0, skip_connections=False, deconv_decoder=False,
@@ -1263,6 +1266,7 @@ class DreamHourglassMultiStage(nn.Module):
     activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
     conv_ksplit = _FixedSwitch("off", "DreamHourglassMultiStage does not split its convs", "the stages run the fp32-storage walk")
     inference_head_fusion = _FixedSwitch("off", "DreamHourglassMultiStage does not fuse its heads", "the fused entry is ResnetSimple's ConvTranspose2d(256,256,4,2,1) + 1x1 head")
+    train_decoder_precision = _FixedSwitch("fp32", "DreamHourglassMultiStage has no ConvTranspose2d(k4,s2,p1) decoder", "its half-precision training is train_precision")
     train_gradient_storage = _FixedSwitch("fp32", "DreamHourglassMultiStage stores its gradients in fp32 only",
                                           "the stages hand fp32 gradients to one another")
     train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "the glue between the stages (stage_input) is fp32")
@@ -1625,6 +1629,12 @@ class ResnetSimple(nn.Module):
         # bn_fusion and conv1x1_algorithm="gemm".  Read once per forward pass (_resolve_switches -> _ResnetWalk.train16).  Not spelled ``train_precision``:
         # that name is DreamHourglass's switch (its plain 3x3 convs), which this class exposes as fixed to "fp32" and keeps refusing.
         self.train_gemm_precision = "fp32"
+        # Training: "fp16" = the decoder's ConvTranspose2d(k4,s2,p1) stages that did not take the small-map GEMM form (_half_convT) multiply on
+        # the fp16 matrix cores -- forward (the saturating plain sub-pixel phases), data gradient (one launch, dz staged with position stride 2) and
+        # weight gradient (by sub-pixel phase; csrc/conv_f16.hip, csrc/wgrad_f16.hip).  Tensors, BatchNorm statistics, bias
+        # gradients and the optimizer stay fp32; needs bn_fusion.  Independent of train_gemm_precision.  Read once per forward pass
+        # (_resolve_switches -> _ResnetWalk.dec16) and taped as rec["f16"] of the "convT" records.
+        self.train_decoder_precision = "fp32"
         # Inference, with precision="fp16": "fp16" = every tensor between the image and the K belief maps lives in HBM as IEEE half NHWC --
         # half(clamp(v, +-65504)), no per-tensor scale; the stored half IS the consumer's MFMA operand -- and the six stride-2 convs run on
         # the fp16 matrix cores over gathered pixels / patch rows (_EvalAct16).  "fp32" (default): today's walk.  Read once per
@@ -1758,7 +1768,7 @@ class ResnetSimple(nn.Module):
                                                             "%s is %r" % (needs[0][0], are[0]) if len(are) == 1 else "they are %r and %r" % are))
         return _ResnetWalk(_HALF_OPS.get(read["precision"], "fp32"), read["inference_activation_storage"] == "fp16",
                            read["train_gemm_precision"] == "fp16", read["inference_conv_ksplit"] == "auto",
-                           read["inference_head_fusion"] == "on")
+                           read["inference_head_fusion"] == "on", read["train_decoder_precision"] == "fp16")
 
     @staticmethod
     def _half_unit(rec):
@@ -1767,6 +1777,21 @@ class ResnetSimple(nn.Module):
         ``sub2`` downsample form, the ``col3`` patch-row form) in a pass that resolved train_gemm_precision="fp16".  Everything else -- stem,
         Winograd and direct convs, transposed convs (their small-map GEMM form included), head, pool -- is fp32 launch for launch."""
         return rec["kind"] == "conv" and rec.get("f16", False)
+
+    @staticmethod
+    def _half_decoder(rec):
+        """The taped decision of train_decoder_precision="fp16": a "convT" record whose forward ran on the fp16 matrix cores (_half_convT)."""
+        return rec["kind"] == "convT" and rec.get("f16", False)
+
+    def _half_convT(self, name, m, y, gemm):
+        """The rule of train_decoder_precision="fp16" for one decoder stage: a ConvTranspose2d(k4,s2,p1) that does not take the small-map GEMM
+        form (``gemm``: whether that form is eligible at all), with Cin % 32 == 0 and Cout % 32 == 0 (the contractions of the three launches
+        in whole chunks) and an output of even extent."""
+        cin, cout = int(m.weight.shape[0]), int(m.weight.shape[1])
+        return ((not gemm or self._convT_gemm(name, m, y) is None)
+                and tuple(m.kernel_size) == (4, 4) and tuple(m.stride) == (2, 2) and tuple(m.padding) == (1, 1)
+                and tuple(m.output_padding) == (0, 0) and int(y.shape[3]) == cin
+                and ops.convT4x4_f16_train_applies(cin, cout, 2 * int(y.shape[1]), 2 * int(y.shape[2])))
 
     def _convT_gemm(self, name, m, y):
         """Does this transposed conv run as one 1x1 GEMM (N = 16 Cout) + a gather (small maps: _convT_forward)?  -> packed weight or None."""
@@ -1916,6 +1941,23 @@ class ResnetSimple(nn.Module):
         self._bn_fwd(rec, residual, materialize)
         return rec
 
+    def _stage(self, tape, name, m, bn, y, src, dec16, head=None):
+        """One decoder stage, ConvTranspose2d(k4,s2,p1) -> BatchNorm(batch statistics) -> ReLU -> its tape record.  ``dec16``: what the pass
+        resolved of train_decoder_precision (_ResnetWalk); the decision for this stage (_half_convT) is taped as rec["f16"], the one thing
+        the backward reads of it.  ``head``: the module behind the stage, whose loader may apply the BatchNorm (then y stays None)."""
+        fused = self.bn_fusion
+        bias = m.bias.detach() if m.bias is not None else None
+        half_t = dec16 and self._half_convT(name, m, y, fused)
+        if half_t:
+            # the four sub-pixel phases on the fp16 matrix cores; y is an activation: rounded unscaled and saturated (e_x = 0 with a clamp)
+            z = ops.conv_transpose4x4s2_f16_sat(y, self._w("wT16", name, m.weight), int(m.weight.shape[1]), None, bias, 0)
+        else:
+            z = self._convT_forward(name, m, y, None, bias, 0, gemm=fused)
+        rec = dict(kind="convT", name=name, conv=m, bn=bn, relu=True, has_res=False, x=y, src=src, z=z, y=None, ab=None, f16=half_t)
+        self._bn_fwd(rec, materialize=not self._head_on_gemm(head, z))
+        tape.append(rec)
+        return rec
+
     def _wino_train(self, conv):
         """Training: the stride-1 3x3 convs of the bottlenecks (forward and data gradient) on the Winograd kernel (rec["wino"])."""
         return (self.conv_algorithm == "winograd" and int(conv.kernel_size[0]) == 3 and int(conv.stride[0]) == 1
@@ -1933,8 +1975,9 @@ class ResnetSimple(nn.Module):
     def run_forward_train(self, x):
         """-> (belief maps NCHW, tape)."""
         fused = self.bn_fusion
-        half = self._resolve_switches(True).train16
-        self._repack_weights(split=fused, half=half)
+        walk = self._resolve_switches(True)
+        half = walk.train16
+        self._repack_weights(split=fused, half=half or walk.dec16)
         if fused:
             self._packs.restart_pools()
         tape = []
@@ -1983,13 +2026,9 @@ class ResnetSimple(nn.Module):
         stages = list(self._decoder())
         for j, (name, m, bn) in enumerate(stages):
             if bn is not None:
-                z = self._convT_forward(name, m, y, None, m.bias.detach() if m.bias is not None else None, 0, gemm=fused)
-                rec = dict(kind="convT", name=name, conv=m, bn=bn, relu=True, has_res=False, x=y, src=src, z=z, y=None, ab=None)
                 # Round 6: the LAST decoder layer's normalised activation is consumed by the head conv only -- which applies the
                 # BatchNorm + ReLU in its loader (and so do its weight gradient and the mask of its data gradient): never stored
-                head = stages[j + 1][1] if j + 1 < len(stages) else None
-                self._bn_fwd(rec, materialize=not self._head_on_gemm(head, z))
-                tape.append(rec)
+                rec = self._stage(tape, name, m, bn, y, src, walk.dec16, head=stages[j + 1][1] if j + 1 < len(stages) else None)
                 y, src = rec["y"], rec
             elif y is None:                                   # the head conv on the 1x1 GEMM, behind the BatchNorm loader
                 cout = int(m.weight.shape[0])
@@ -2087,6 +2126,8 @@ class ResnetSimple(nn.Module):
         kind, x = rec["kind"], rec["x"]
         cout = int(rec["conv"].weight.shape[0])
         if kind == "convT":
+            if self._half_decoder(rec) and ops.convT4x4_wgrad_f16_pays(*(int(v) for v in x.shape), int(dz.shape[3])):
+                return "convT_f16", [x, dz]
             return ("convT_winograd" if ops.convT4x4_wgrad_winograd_applies(x, dz) else "convT"), [x, dz]
         if kind == "stem":
             return ("gemm" if rec["gemm"] else "direct"), [x, dz]
@@ -2117,6 +2158,8 @@ class ResnetSimple(nn.Module):
                 dw, db = ops.convT4x4_wgrad_winograd(x, dz)
             elif form == "convT":
                 dw = ops.convT4x4_wgrad(x, dz)
+            elif form == "convT_f16":         # by sub-pixel phase on the fp16 matrix cores; the bias gradient stays the fp32 channel sum
+                dw = ops.convT4x4_wgrad_f16(x, dz, rec["dz_amax"])
             elif form == "gemm" and half_amax is not None:
                 dw = ops.conv1x1_wgrad_f16(x, dz, half_amax, ops.round_up(cout, 4), kin, pre_ab=pre_ab)
             elif form == "gemm":              # the GEMM over positions, of the conv as it RAN: 1x1, im2col rows (stem), patch rows (col3)
@@ -2151,7 +2194,7 @@ class ResnetSimple(nn.Module):
         bn, z, g = rec["bn"], rec["z"], None
         # a covered unit (train_gemm_precision="fp16"): the same apply pass also publishes max|dz|, the scale of the gradient operand that this
         # record's data- and weight-gradient GEMMs round to half (no absmax pass)
-        if self._half_unit(rec):
+        if self._half_unit(rec) or self._half_decoder(rec):      # (... or train_decoder_precision="fp16": a covered decoder stage)
             amax = rec["dz_amax"] = self._packs.amax_word(z.device)
             apply = lambda *a, **kw: ops.bn_bwd_apply_amax(*a, amax, **kw)      # noqa: E731
         else:
@@ -2181,10 +2224,13 @@ class ResnetSimple(nn.Module):
             gy = ops.nchw_to_nhwc(bw["grad_out"], cpad=ops.round_up(cout, 32))
         return self._dgrad(rec, gy, form=form)
 
-    def _bwd_convT(self, rec, g, bw):
+    def _convT_dgrad(self, rec, dz):
+        """The data gradient of a "convT" record -- the 4x4 stride-2 conv of dz -- in the form the record and the switches choose."""
         m, name = rec["conv"], rec["name"]
-        dz, _ = self._unit_bwd(rec, g, bw)
         cin_t, cout_t = int(m.weight.shape[0]), int(m.weight.shape[1])
+        if self._half_decoder(rec):
+            # one launch on the fp16 matrix cores: the 4x4 stride-2 conv of dz by its sub-pixel phases, 16 tap products per output
+            return ops.conv_transpose4x4s2_dgrad_f16(dz, rec["dz_amax"], self._w("wT16b", name, m.weight), cin_t)
         if (self.convT_algorithm == "winograd" and cout_t % 16 == 0 and cout_t >= 32 and cin_t > 64
                 and int(dz.shape[3]) == cout_t and dz.shape[1] % 2 == 0 and dz.shape[2] % 2 == 0):
             tile = ops.conv4x4s2_winograd_tile_of(dz, cin_t)
@@ -2192,6 +2238,10 @@ class ResnetSimple(nn.Module):
             return ops.conv4x4s2_winograd_tile(tile, dz, u4b, rows)
         pk, rows = self._w("wTb", name, m.weight)
         return ops.conv4x4s2(dz, pk, rows)
+
+    def _bwd_convT(self, rec, g, bw):
+        dz, _ = self._unit_bwd(rec, g, bw)
+        return self._convT_dgrad(rec, dz)
 
     def _bwd_block(self, blk, g, bw):
         """A Bottleneck: .3, .2, .1, the downsample branch, then the gradients that meet at the block's input -- conv1's data gradient joins

@@ -837,9 +837,15 @@ def pack_conv1x1_weight_f16(w_oihw, mode=0):
     return packed, exp, rows
 
 
+def half_planes(packed16):
+    """(halfs, e_w) of a half copy: (halfs, e_w, rows) of the fp16 GEMM, (hi, None, e_w, rows) of the conv_f16 planes."""
+    return packed16[0], packed16[1] if packed16[1] is not None else packed16[2]
+
+
 def pack16_job_table(entries, device):
     """Device-resident dream_pack16_job table for pack_conv1x1_weights_f16_batched -> (table, scratch words).  ``entries``:
-    (weight [Cout,Cin,1,1], (halfs, e_w, rows) as pack_conv1x1_weight_f16 returned it, mode)."""
+    (weight [Cout,Cin,1,1], (halfs, e_w, rows) as pack_conv1x1_weight_f16 returned it, mode 0 | 1) or (ConvTranspose2d weight [Cin,Cout,4,4],
+    (hi, None, e_w, rows) as pack_convT4x4_weight_f16 (mode 2) / pack_convT4x4_dgrad_weight_f16 (mode 3) returned it, mode)."""
     import numpy as np
     dt = np.dtype([("src", np.uint64), ("dst", np.uint64), ("exp", np.uint64), ("scratch", np.uint64), ("cout", np.int32),
                    ("cin", np.int32), ("mode", np.int32), ("reserved", np.int32)])
@@ -848,7 +854,8 @@ def pack16_job_table(entries, device):
     scratch = torch.zeros((len(entries),), dtype=torch.int32, device=device)
     arr = np.zeros(len(entries), dt)
     for i, (w, packed16, mode) in enumerate(entries):
-        arr[i] = (ptr(w), ptr(packed16[0]), ptr(packed16[1]), ptr(scratch[i:i + 1]), int(w.shape[0]), int(w.shape[1]), mode, 0)
+        halfs, exp = half_planes(packed16)
+        arr[i] = (ptr(w), ptr(halfs), ptr(exp), ptr(scratch[i:i + 1]), int(w.shape[0]), int(w.shape[1]), mode, 0)
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device), scratch
 
 
@@ -939,6 +946,78 @@ def bn_bwd_apply_amax(z_nhwc, dy, gamma, mean, invstd, dgamma, dbeta, amax, y_ac
     call("dream_bn_bwd_apply_amax_nhwc_f32", ptr(z), ptr(_f32(dy)), ptr(y_act), ptr(ab), ptr(gamma.detach()), ptr(mean), ptr(invstd),
          ptr(dgamma), ptr(dbeta), ptr(dz), ptr(g), ptr(amax), z.numel() // c, c, _mask_mode(y_act, ab), stream())
     return dz, g
+
+
+# ---- ResnetSimple train_decoder_precision="fp16": the decoder's transposed convs on the fp16 matrix cores -----------------
+# forward: the saturating plain form of csrc/conv_f16.hip on pack_convT4x4_weight_f16; backward: the two launches further down
+def conv_transpose4x4s2_f16_sat(x_nhwc, packed16, cout, scale=None, shift=None, flags=0):
+    """conv_transpose4x4s2_f16 for an activation that carries no amax: x rounded as half(clamp(x, +-65504)), e_x = 0 (the saturating plain
+    form) -> y [B,2H,2W,cout] fp32; no amax is published."""
+    hi, _, exp, _ = packed16
+    x = _f32(x_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    if cin != int(hi.shape[-1]):
+        raise RuntimeError("conv_transpose4x4s2_f16_sat: input has %d channels, packed weights expect %d" % (cin, int(hi.shape[-1])))
+    y = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+    call("dream_conv_transpose4x4s2_f16_sat_nhwc_f32", ptr(x), ptr(hi), ptr(exp), ptr(scale), ptr(shift), ptr(y), b, h, w, cin, cout,
+         int(hi.shape[-2]), flags, stream())
+    return y
+
+
+def pack_convT4x4_dgrad_weight_f16(wT):
+    """ConvTranspose2d weight [Cin,Cout,4,4] -> (hi, None, exp, cin): the half plane [16][rows_pad >= Cin][Cout] of wT * 2^exp, slice
+    4 ty + tx, that conv_transpose4x4s2_dgrad_f16 reads (pack_conv_weight_f16 of the tensor read as [O = Cin, I = Cout, 4, 4])."""
+    return pack_conv_weight_f16(wT, 0)
+
+
+def convT4x4_f16_train_applies(cin, cout, ho, wo):
+    """The shapes the three fp16 launches of a decoder stage take: the contractions (Cin forward and weight gradient, Cout data
+    gradient) in whole 32-channel chunks, a gradient tensor of even extent."""
+    return cin % 32 == 0 and cout % 32 == 0 and ho % 2 == 0 and wo % 2 == 0 and ho >= 2 and wo >= 2
+
+
+def convT4x4_wgrad_f16_pays(b, h, w, cin, cout):
+    """Does the fp16 weight gradient beat the fp32 launch on this problem?  Measured (profiles/microbench_resnet_decoder_precision.txt):
+    256 x 256 channel pairs win on every map; 2048 x 256 on the 13 x 13 maps of the 128-frame step LOSES: its channel tiles x 4 phases alone
+    fill the workgroup slots, so the launch's own plan (convT4x4_wgrad_f16_splitk) leaves no split over positions and every workgroup walks
+    all 256 position tiles (13 x 13 in two 8 x 16 tiles: 40 % of the staged positions are padding).  Covered while a split remains."""
+    return convT4x4_wgrad_f16_splitk(b, h, w, cin, cout) > 1
+
+
+def conv_transpose4x4s2_dgrad_f16(dz_nhwc, amax_dz, packed16, cin, flags=0):
+    """Data gradient of ConvTranspose2d(k4,s2,p1) on the fp16 matrix cores, one launch: dz [B,2H,2W,Cout] fp32 rounded to fp16(dz 2^e_g)
+    while it is staged with position stride 2, ``amax_dz`` the scalar published with it -> dx [B,H,W,cin] fp32."""
+    dz = _f32(dz_nhwc)
+    b, ho, wo, cdz = (int(v) for v in dz.shape)
+    hi, _, exp = _packed_planes("conv_transpose4x4s2_dgrad_f16", packed16, cdz)
+    if int(hi.shape[0]) != 16:
+        raise RuntimeError("conv_transpose4x4s2_dgrad_f16: expected the 16-slice plane of pack_convT4x4_dgrad_weight_f16")
+    dx = torch.empty((b, ho // 2, wo // 2, cin), dtype=torch.float32, device=dz.device)
+    call("dream_conv_transpose4x4s2_dgrad_f16_nhwc_f32", ptr(dz), ptr(amax_dz), ptr(hi), ptr(exp), ptr(dx), b, ho, wo, cdz, cin,
+         int(hi.shape[-2]), flags, stream())
+    return dx
+
+
+def convT4x4_wgrad_f16_splitk(b, h, w, cin, cout):
+    """Position slices the fp16 weight gradient of this problem is split into (a host computation: no GPU is touched)."""
+    return int(_hip.lib().dream_convT4x4_wgrad_f16_splitk(b, h, w, cin, cout, round_up(cin, 64)))
+
+
+def convT4x4_wgrad_f16(x_nhwc, dz_nhwc, amax_dz, flags=0):
+    """ConvTranspose2d(4,2,1) weight gradient on the fp16 matrix cores -> [Cin,Cout,4,4]: x [B,H,W,Cin] rounded unscaled (clamped), dz
+    [B,2H,2W,Cout] as fp16(dz 2^e_g) from ``amax_dz``; split over position tiles, fixed-order reduce (two runs give the same bits)."""
+    x, dz = _f32(x_nhwc), _f32(dz_nhwc)
+    b, h, w, cin = (int(v) for v in x.shape)
+    ho, wo, cout = int(dz.shape[1]), int(dz.shape[2]), int(dz.shape[3])
+    if (int(dz.shape[0]), ho, wo) != (b, 2 * h, 2 * w):
+        raise RuntimeError("convT4x4_wgrad_f16: dz %s does not go with x %s" % (tuple(dz.shape), tuple(x.shape)))
+    rows_pad = round_up(cin, 64)
+    ws = _workspace(_hip.lib().dream_convT4x4_wgrad_f16_workspace(b, h, w, cin, cout, rows_pad), x.device)
+    dwp = torch.empty((16, rows_pad, cout), dtype=torch.float32, device=x.device)
+    call("dream_convT4x4_wgrad_f16_nhwc_f32", ptr(x), ptr(dz), ptr(amax_dz), ptr(dwp), ptr(ws), b, ho, wo, cin, cout, rows_pad, flags, stream())
+    dw = torch.empty((cin, cout, 4, 4), dtype=torch.float32, device=x.device)
+    call("dream_unpack_conv_weight", ptr(dwp), ptr(dw), cin, cout, 16, rows_pad, cout, stream())
+    return dw
 
 
 def conv_transpose4x4s2(x_nhwc, packed, cout, scale=None, shift=None, flags=0, direct_taps=16):

@@ -107,6 +107,11 @@ RESNET_FORMS = {
     "stem_w": ("w", lambda w, cols: ops.pack_matrix_weight(w.reshape(64, 147), cols)[0]),                 # the 1-tap direct kernel
     "stem_g0e": ("g0e", lambda w, cols: ops.pack_conv1x1_weight(_stem_cols(w, cols), 0)[0]),             # the 1x1 GEMM in evaluation
     "stem_g0": ("g0", lambda w, cols: ops.pack_conv1x1_weight(_stem_cols(w, cols), 0)[0]),               # ... in training
+    # train_decoder_precision="fp16": the half planes of a decoder stage -- sub-pixel phases (forward) and the 16-slice transposed plane
+    # (data gradient) -> (halfs, None, e_w, rows); keys of their own: the evaluation copy "wf16T" is not shared.  Both join the batched
+    # fp16 re-pack from the second step on (HALF_SOURCES modes 2 / 3)
+    "wT16": ("wT16", lambda w, _: ops.pack_convT4x4_weight_f16(w)),
+    "wT16b": ("wT16b", lambda w, _: ops.pack_convT4x4_dgrad_weight_f16(w)),
     "wf16col3": ("wf16col3", lambda w, _: ops.pack_conv_weight_f16(_col3(w), 0)),
     # eval-mode BatchNorm (+ the conv's bias) folded to (scale, shift): the one form of several tensors
     "bn": ("bn", lambda t, eps: ops.bn_fold(t[0], t[1], t[2], t[3], eps, t[4] if len(t) > 4 else None)),
@@ -116,7 +121,7 @@ for _sfx in ("f16x3", "f16"):                     # the split- / half-precision 
     RESNET_FORMS["w" + _sfx + "T"] = ("w" + _sfx, lambda w, _, pack=getattr(ops, "pack_convT4x4_weight_" + _sfx): pack(w))
     RESNET_FORMS["stem_w" + _sfx] = ("w" + _sfx, lambda w, _, pack=getattr(ops, "pack_conv_weight_" + _sfx): pack(w.reshape(64, 147, 1, 1), 0))
 TILED = frozenset(("wino", "wino1", "wu4", "wu4b"))
-HALF_SOURCES = {"g0f16": 0, "g1f16": 1}           # packed from the parameter itself: batchable (PackedWeights.half_source)
+HALF_SOURCES = {"g0f16": 0, "g1f16": 1, "wT16": 2, "wT16b": 3}           # packed from the parameter itself: batchable (PackedWeights.half_source)
 
 # What a test may ask of a store: copies held; keys recorded for the fp32 table, is it built, its jobs; (early keys, all keys) of a split
 # re-pack or None; is its late launch still pending; is the fp16 table built; idle: no re-pack state at all (every pack so far was lazy).
@@ -282,7 +287,7 @@ class PackedWeights:
                 self._copies[key] = (tag, st.records[key][1])
 
     def _repack_half(self, first):
-        """train_gemm_precision="fp16": the half copies that earlier steps built from a parameter itself (HALF_SOURCES; not the patch-row
+        """train_gemm_precision="fp16" / train_decoder_precision="fp16": the half copies that earlier steps built from a parameter itself (HALF_SOURCES; not the patch-row
         forms) are rewritten in place by ONE batched pack at the start of the step (three launches) and their entries stamped with the
         parameters' new versions -- packed one by one, three launches per copy, they cost a 16-frame step more than the fp16 GEMMs save
         (profiles/microbench_resnet_train_precision.txt).  Skipped on the first step (nothing is held yet), off the GPU and during a
@@ -290,12 +295,16 @@ class PackedWeights:
         live = {key: src for key, src in self._half.items() if key in self._copies}
         if not live:
             return
-        stamp = tuple((key, self._copies[key][1][0].data_ptr(), self._copies[key][1][1].data_ptr(), src[0].data_ptr()) for key, src in live.items())
+        stamp = tuple((key,) + tuple(t.data_ptr() for t in ops.half_planes(self._copies[key][1])) + (src[0].data_ptr(),) for key, src in live.items())
         if self._table16 is None or self._table16[0] != stamp:
             entries = [(w.detach(), self._copies[key][1], mode) for key, (w, mode) in live.items()]
-            self._table16 = (stamp,) + ops.pack16_job_table(entries, first.device)
+            # workgroups per job: 16 for the GEMM copies (4.8j's measured launch); with a decoder plane in the table one per 32 K halfs of
+            # the largest plane, at most 256 -- the 2048 -> 256 planes of the 128-frame step are 8.4 M halfs each
+            planes = [int(self._copies[key][1][0].numel()) for key, (_, mode) in live.items() if mode >= 2]
+            wgs = min(256, max(16, max(planes) >> 15)) if planes else 16
+            self._table16 = (stamp,) + ops.pack16_job_table(entries, first.device) + (wgs,)
         tags = {key: ((w._version, w.data_ptr()),) for key, (w, _) in live.items()}
         if any(self._copies[key][0] != tag for key, tag in tags.items()):
-            ops.pack_conv1x1_weights_f16_batched(self._table16[1], self._table16[2])
+            ops.pack_conv1x1_weights_f16_batched(self._table16[1], self._table16[2], workgroups_per_job=self._table16[3])
             for key, tag in tags.items():
                 self._copies[key] = (tag, self._copies[key][1])

@@ -793,8 +793,9 @@ int dream_pack_conv1x1_weight_f16(const float *w_oihw, void *packed, int *exp_ou
  * copy, as dream_pack_weights_batched does for the fp32 copies (the optimizer of network.py:337 changed every weight).  jobs: DEVICE
  * array; scratch fields point into the njobs words of `scratch`, one per job.  Same values as the one-tensor entry point, bit for bit. */
 typedef struct dream_pack16_job {
-    const float *src;      /* [cout][cin][1][1] */
-    void *dst;             /* dream_conv1x1_weight_halfs() halfs */
+    const float *src;      /* [cout][cin][1][1]; modes 2 / 3: a ConvTranspose2d(k4,s2,p1) weight [cout = Cin_T][cin = Cout_T][4][4] */
+    void *dst;             /* dream_conv1x1_weight_halfs() halfs; mode 2: the `hi` plane of dream_pack_convT4x4_weight_f16x3, mode 3: that of
+                              dream_pack_conv_weight_f16x3 (16 taps, mode 0), rows padded to 128 and columns to 32 */
     int *exp;              /* e_w out */
     unsigned *scratch;     /* this job's amax word */
     int cout, cin, mode, reserved;
@@ -827,6 +828,31 @@ int dream_conv1x1_wgrad_f16_nhwc_f32(const float *x, const float *dy, const unsi
 int dream_bn_bwd_apply_amax_nhwc_f32(const float *z, const float *dy, const float *y_act, const float *ab, const float *gamma,
                                      const float *save_mean, const float *save_invstd, const float *dgamma, const float *dbeta,
                                      float *dz, float *g_out, unsigned *amax_out, size_t npix, int C, int mask, void *stream);
+/* ---- ResnetSimple.train_decoder_precision = "fp16": the decoder's ConvTranspose2d(k4,s2,p1) stages (dream/models.py:37-136) in training,
+ * all three products on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  The forward is dream_conv_transpose4x4s2_f16_nhwc_f32 (bias as
+ * shift) in its saturating form below; the two entry points after it are its backward (replace ATen's conv-transpose backward reached from loss.backward(),
+ * dream/network.py:335).  Tensors stay fp32; an operand is rounded once, while it is staged. ------------------------------------ */
+/* forward: dream_conv_transpose4x4s2_f16_nhwc_f32 for an activation that carries no amax -- x rounded as half(clamp(x, +-65504)), e_x = 0
+ * (the saturating plain form of csrc/conv_f16.hip); no amax_in, no amax_out. */
+int dream_conv_transpose4x4s2_f16_sat_nhwc_f32(const float *x, const void *w, const int *w_exp, const float *scale, const float *shift,
+                                               float *y, int B, int H, int W, int Cin, int Cout, int CoutPad, int flags, void *stream);
+/* data gradient: dz [B,Ho,Wo,Cdz] (Ho, Wo even), amax_dz: device scalar with the bit pattern of (an upper bound of) max|dz|
+ * (dream_bn_bwd_apply_amax_nhwc_f32) -> dx [B,Ho/2,Wo/2,Cdx]:
+ *   dx[b,i,j,ci] = 2^-(eg+ew) sum_{ty,tx} sum_co fp16(dz 2^eg)[b,2i+ty-1,2j+tx-1,co] * w[4 ty + tx][ci][co], zero outside the map.
+ * w: halfs [16][CdxPad][Cdz] of wT[ci][co][ty][tx] 2^ew = the `hi` plane of dream_pack_conv_weight_f16x3 on the [Cdx,Cdz,4,4] weight
+ * (16 taps, mode 0), w_exp its exponent.  One launch; 16 tap products per output.  Cdz % 32 == 0, dz and w 16-byte aligned, flags 0. */
+int dream_conv_transpose4x4s2_dgrad_f16_nhwc_f32(const float *dz, const unsigned *amax_dz, const void *w, const int *w_exp, float *dx,
+                                                 int B, int Ho, int Wo, int Cdz, int Cdx, int CdxPad, int flags, void *stream);
+/* weight gradient: x [B,Ho/2,Wo/2,Cin] (a ReLU output: rounded unscaled, clamped to +-65504), dz and amax_dz as above ->
+ * dw_packed [16][RowsPad][Cdz], slice 4 ty + tx (dream_unpack_conv_weight -> [Cin,Cdz,4,4]):
+ *   dW[ci,co,ty,tx] = 2^-eg sum_{b,i,j} fp16(x)[b,i,j,ci] * fp16(dz 2^eg)[b,2i+ty-1,2j+tx-1,co].
+ * Cin % 32 == 0, Cdz % 4 == 0, RowsPad >= Cin a multiple of 64, pointers 16-byte aligned, flags 0.  Split over position tiles
+ * (dream_convT4x4_wgrad_f16_splitk() slices: a host computation) into `workspace` (dream_convT4x4_wgrad_f16_workspace() bytes), summed in
+ * a fixed order: no atomics, two runs give the same bits.  The bias gradient stays dream_channel_sum_nhwc_f32(dz). */
+int dream_convT4x4_wgrad_f16_splitk(int B, int H, int W, int Cin, int Cdz, int RowsPad);
+size_t dream_convT4x4_wgrad_f16_workspace(int B, int H, int W, int Cin, int Cdz, int RowsPad);
+int dream_convT4x4_wgrad_f16_nhwc_f32(const float *x, const float *dz, const unsigned *amax_dz, float *dw_packed, void *workspace, int B,
+                                      int Ho, int Wo, int Cin, int Cdz, int RowsPad, int flags, void *stream);
 /* the same pool for training: also stores which element of its 3x3 window won (uint8 0..8 = 3 dy + dx, the first maximum in scan
  * order: ATen's max_pool2d_with_indices), so that the backward pass compares one byte per window instead of recomputing nine-way
  * arg-maxima; idx: [B,Ho,Wo,C] bytes */
