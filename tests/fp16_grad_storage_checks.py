@@ -244,11 +244,15 @@ def _loss_with_scale(model, x, t, record):
     return F.mse_loss(out, t)
 
 
+def grad_stored_training_oracle(out_wh, shape=tc.TRAIN_SHAPE):
+    """({parameter name: E_p}, peak = the largest |g * 2^e_g| any hook stored); computed once per process and shape."""
+    return _grad_stored_training_oracle(out_wh, shape)
+
+
 @functools.lru_cache(maxsize=None)
-def grad_stored_training_oracle(out_wh):
-    """({parameter name: E_p}, peak = the largest |g * 2^e_g| any hook stored); computed once per process."""
-    wts, x = tc.training_case()
-    t = sc._oracle_target(out_wh)
+def _grad_stored_training_oracle(out_wh, shape):
+    wts, x = tc.training_case(shape)
+    t = sc._oracle_target(out_wh, shape)
     E, peak = {}, 0.0
     for dtype in (torch.float32, torch.float64):
         plain = sc._oracle_model(wts, dtype, "plain")
@@ -265,8 +269,8 @@ def grad_stored_training_oracle(out_wh):
 
 def check_reference_sanity(out_wh):
     """The extended oracle adds next to nothing to 4.8e's: E_p within 1.05x, the stored values stay 2^4 below saturation."""
-    E, peak = grad_stored_training_oracle(out_wh)
-    E0 = sc.stored_training_oracle(out_wh)
+    E, peak = grad_stored_training_oracle(out_wh, tc.TRAIN_SHAPE)        # (the cache keys of check_training_step at the default shape)
+    E0 = sc.stored_training_oracle(out_wh, tc.TRAIN_SHAPE)
     worst = max(E[n] / E0[n] for n in E0)
     print("half-gradient oracle: worst E_p / E_p(stored activations) %.5f, peak 2^%.2f" % (worst, math.log2(peak)))
     assert set(E) == set(E0) and worst <= 1.05, worst
@@ -294,29 +298,30 @@ def oracle_loss_gap(out_wh, steps=20):
     return rho, runs
 
 
-def training_network(dev, gradient_storage="fp16", storage="fp16", train_precision="fp16", optimizer="sgd", lr=0.0):
-    net = sc.training_network(dev, storage, train_precision, optimizer=optimizer, lr=lr)
+def training_network(dev, gradient_storage="fp16", storage="fp16", train_precision="fp16", optimizer="sgd", lr=0.0, shape=tc.TRAIN_SHAPE):
+    net = sc.training_network(dev, storage, train_precision, optimizer=optimizer, lr=lr, shape=shape)
     net.model.module.train_gradient_storage = gradient_storage
     return net
 
 
-def step_gradients(dev, gradient_storage, storage="fp16", train_precision="fp16"):
-    net = training_network(dev, gradient_storage, storage, train_precision)
-    _, x = tc.training_case()
-    t, out_wh = tc._target(net, dev)
+def step_gradients(dev, gradient_storage, storage="fp16", train_precision="fp16", shape=tc.TRAIN_SHAPE):
+    net = training_network(dev, gradient_storage, storage, train_precision, shape=shape)
+    _, x = tc.training_case(shape)
+    t, out_wh = tc._target(net, dev, shape)
     loss = float(net.train([pc.to(dev, x)], t).item())
     grads = {n: p.grad.detach().cpu().clone() for n, p in net.model.module.named_parameters()}
     return grads, loss, out_wh, net
 
 
-def check_training_step(dev):
-    """One vgg_q step at 2 x 64 x 96 with the three switches "fp16" against the fp32 step of the same build, every parameter to 3 E_p.
+def check_training_step(dev, shape=tc.TRAIN_SHAPE):
+    """One vgg_q step at ``shape`` (2 x 64 x 96) with the three switches "fp16" against the fp32 step of the same build, every parameter
+    to 3 E_p.
 
     Measured (r_p / E_p worst, distance to the two-switch step): see DESIGN.md 4.8g."""
-    g32, loss32, out_wh, _ = step_gradients(dev, "fp32", "fp32", "fp32")
-    g2, loss2, _, _ = step_gradients(dev, "fp32")                            # the two-switch step: half activations, fp32 gradients
-    gs, loss_s, _, net = step_gradients(dev, "fp16")
-    E, _ = grad_stored_training_oracle(out_wh)
+    g32, loss32, out_wh, _ = step_gradients(dev, "fp32", "fp32", "fp32", shape=shape)
+    g2, loss2, _, _ = step_gradients(dev, "fp32", shape=shape)               # the two-switch step: half activations, fp32 gradients
+    gs, loss_s, _, net = step_gradients(dev, "fp16", shape=shape)
+    E, _ = grad_stored_training_oracle(out_wh, shape)
     m = net.model.module
     peak = m.half_gradient_peak()
     assert 0.0 < peak < 65504.0 and peak == peak, peak
@@ -350,8 +355,8 @@ def check_training_step(dev):
           "largest distance to the two-switch step %.3g" % (loss32, loss2, loss_s, peak, math.log2(peak), worst, dist))
     assert loss_s == loss2                                                    # the forward is the two-switch forward
     # a second step (lr = 0: same parameters) gives the same bits: no state is carried from step to step
-    _, x = tc.training_case()
-    t, _ = tc._target(net, dev)
+    _, x = tc.training_case(shape)
+    t, _ = tc._target(net, dev, shape)
     assert float(net.train([pc.to(dev, x)], t).item()) == loss_s
     for n, p in m.named_parameters():
         assert torch.equal(p.grad.detach().cpu(), gs[n]), n

@@ -346,30 +346,34 @@ def _reference_model(dtype, decoder, gemm):
     return model
 
 
-def network(dev, decoder, gemm="fp32", optimizer="sgd", lr=0.0):
-    net = sc.network(dev, gemm, optimizer=optimizer, lr=lr)
+def network(dev, decoder, gemm="fp32", optimizer="sgd", lr=0.0, shape=sc.STEP_SHAPE):
+    net = sc.network(dev, gemm, optimizer=optimizer, lr=lr, shape=shape)
     net.model.module.CONVT_GEMM_MAX_PIXELS = 0
     net.model.module.train_decoder_precision = decoder
     return net
 
 
-def _device_step(dev, decoder, gemm="fp32"):
-    net = network(dev, decoder, gemm)
+def _device_step(dev, decoder, gemm="fp32", shape=sc.STEP_SHAPE):
+    net = network(dev, decoder, gemm, shape=shape)
     ow, oh = net.trained_net_output_resolution()
-    loss = float(net.train([pc.to(dev, sc.step_case())], pc.to(dev, sc._target((ow, oh)))).item())
+    loss = float(net.train([pc.to(dev, sc.step_case(shape))], pc.to(dev, sc._target((ow, oh), shape))).item())
     return loss, {n: p.grad.detach().cpu().clone() for n, p in net.model.module.named_parameters()}, (ow, oh)
 
 
-@functools.lru_cache(maxsize=None)
-def step_yardstick(out_wh, gemm):
+def step_yardstick(out_wh, gemm, shape=sc.STEP_SHAPE):
     """-> ({parameter: E_p}, the rounded reference's relative move of the loss) against the reference with the decoder unrounded (and the
-    1x1 GEMMs rounded in both where ``gemm``): the larger of float32 / float64."""
+    1x1 GEMMs rounded in both where ``gemm``): the larger of float32 / float64; computed once per process and shape."""
+    return _step_yardstick(out_wh, gemm, shape)
+
+
+@functools.lru_cache(maxsize=None)
+def _step_yardstick(out_wh, gemm, shape):
     E, move = {}, 0.0
     for dtype in (torch.float32, torch.float64):
         res = []
         for decoder in (False, True):
             model = _reference_model(dtype, decoder, gemm)
-            loss = F.mse_loss(model(sc.step_case().to(dtype))[0], sc._target(out_wh).to(dtype))
+            loss = F.mse_loss(model(sc.step_case(shape).to(dtype))[0], sc._target(out_wh, shape).to(dtype))
             loss.backward()
             res.append((float(loss), {n: p.grad.double() for n, p in model.named_parameters()}))
         (l0, g0), (l1, g1) = res
@@ -379,22 +383,26 @@ def step_yardstick(out_wh, gemm):
     return E, move
 
 
-def check_step(dev, both):
-    """The switch alone (against the fp32 step) or both training switches (against the step with train_gemm_precision alone)."""
+def check_step(dev, both, shape=sc.STEP_SHAPE, conditioned=sc.CONDITIONED):
+    """The switch alone (against the fp32 step) or both training switches (against the step with train_gemm_precision alone).
+    ``conditioned``: the tensors held at ``shape`` (fp16_resnet_step_checks.check_step)."""
     gemm = "fp16" if both else "fp32"
-    l32, g32, out_wh = _device_step(dev, "fp32", gemm)
-    l16, g16, _ = _device_step(dev, "fp16", gemm)
-    E, move = step_yardstick(out_wh, both)
+    l32, g32, out_wh = _device_step(dev, "fp32", gemm, shape=shape)
+    l16, g16, _ = _device_step(dev, "fp16", gemm, shape=shape)
+    E, move = step_yardstick(out_wh, both, shape)
     print("loss off %.9g on %.9g (relative %.3g; the rounded reference moves %.3g); E_p of the conditioned tensors %s"
-          % (l32, l16, abs(l16 - l32) / l32, move, {n: "%.3g" % E[n] for n in sc.CONDITIONED}))
-    assert move > 0 and all(E[n] > 0 for n in sc.CONDITIONED)
+          % (l32, l16, abs(l16 - l32) / l32, move, {n: "%.3g" % E[n] for n in conditioned}))
+    assert move > 0 and all(E[n] > 0 for n in conditioned)
     assert abs(l16 - l32) <= 3 * move * abs(l32)
     for n in g32:
         assert bool(torch.isfinite(g16[n]).all()), n
-    for n in sc.CONDITIONED:
+    worst = 0.0
+    for n in conditioned:
         d = sc._rel(g16[n], g32[n])
+        worst = max(worst, d / E[n])
         print("  %-20s device on against off %.3g   (3 E_p = %.3g)" % (n, d, 3 * E[n]))
         assert d <= 3 * E[n], (n, d, E[n])
+    print("  worst r_p / E_p %.3g" % worst)
     assert not torch.equal(g16["upsample.9.weight"], g32["upsample.9.weight"])
 
 

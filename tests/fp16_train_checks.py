@@ -200,19 +200,28 @@ def _reference_grads(weights, x, target, dtype, rounded):
 TRAIN_SHAPE = (2, 64, 96)
 
 
+def training_case(shape=TRAIN_SHAPE):
+    """(weights, input batch) of the training checks at ``shape`` = (B, H, W); computed once per process and shape."""
+    return _training_case(tuple(shape))
+
+
 @functools.lru_cache(maxsize=None)
-def training_case():
-    b, h, w = TRAIN_SHAPE
+def _training_case(shape):
+    b, h, w = shape
     wts = om.recipe_weights(om.build_model("vgg_q", 7).state_dict(), cases.TRAIN_FINAL_KEYS, cases.TRAIN_FINAL_SCALE)
     x = torch.from_numpy(cases.image_batch(b, h, w, seed=7))
     return wts, x
 
 
+def rounded_training_oracle(out_wh, shape=TRAIN_SHAPE):
+    """{parameter name: E_p}, and the number of plain convs the reference has; computed once per process and shape."""
+    return _rounded_training_oracle(out_wh, shape)
+
+
 @functools.lru_cache(maxsize=None)
-def rounded_training_oracle(out_wh):
-    """{parameter name: E_p}, and the number of plain convs the reference has; computed once per process."""
-    wts, x = training_case()
-    b, h, w = TRAIN_SHAPE
+def _rounded_training_oracle(out_wh, shape):
+    wts, x = training_case(shape)
+    b, h, w = shape
     t = torch.from_numpy(cases.target_batch(b, 7, out_wh, in_wh=(w, h), seed=7))
     E, nplain = {}, 0
     for dtype in (torch.float32, torch.float64):
@@ -224,9 +233,9 @@ def rounded_training_oracle(out_wh):
     return E, nplain
 
 
-def training_network(dev, train_precision="fp32", precision="fp32", optimizer="sgd", lr=0.0):
-    wts, _ = training_case()
-    b, h, w = TRAIN_SHAPE
+def training_network(dev, train_precision="fp32", precision="fp32", optimizer="sgd", lr=0.0, shape=TRAIN_SHAPE):
+    wts, _ = training_case(shape)
+    b, h, w = shape
     net = pc.build_network("vgg_q", dev, weights=wts, optimizer=optimizer, lr=lr, in_res=(w, h))
     net.model.module.precision = precision
     net.model.module.train_precision = train_precision
@@ -234,27 +243,27 @@ def training_network(dev, train_precision="fp32", precision="fp32", optimizer="s
     return net
 
 
-def _target(net, dev):
-    b, h, w = TRAIN_SHAPE
+def _target(net, dev, shape=TRAIN_SHAPE):
+    b, h, w = shape
     ow, oh = net.trained_net_output_resolution()
     return pc.to(dev, torch.from_numpy(cases.target_batch(b, 7, (ow, oh), in_wh=(w, h), seed=7))), (ow, oh)
 
 
-def step_gradients(dev, train_precision="fp32", precision="fp32"):
+def step_gradients(dev, train_precision="fp32", precision="fp32", shape=TRAIN_SHAPE):
     """{parameter name: gradient} of one training step (SGD with lr = 0: the parameters stay, .grad is read), and the loss."""
-    net = training_network(dev, train_precision, precision)
-    _, x = training_case()
-    t, out_wh = _target(net, dev)
+    net = training_network(dev, train_precision, precision, shape=shape)
+    _, x = training_case(shape)
+    t, out_wh = _target(net, dev, shape)
     loss = float(net.train([pc.to(dev, x)], t).item())
     grads = {n: p.grad.detach().cpu().clone() for n, p in net.model.module.named_parameters()}
     return grads, loss, out_wh, net
 
 
-def check_training_step(dev):
-    """One vgg_q training step at 2 x 64 x 96 with train_precision="fp16" against the fp32 step of the same build."""
-    g32, loss32, out_wh, net = step_gradients(dev, "fp32")
-    g16, loss16, _, _ = step_gradients(dev, "fp16")
-    E, nplain_ref = rounded_training_oracle(out_wh)
+def check_training_step(dev, shape=TRAIN_SHAPE):
+    """One vgg_q training step at ``shape`` (2 x 64 x 96) with train_precision="fp16" against the fp32 step of the same build."""
+    g32, loss32, out_wh, net = step_gradients(dev, "fp32", shape=shape)
+    g16, loss16, _, _ = step_gradients(dev, "fp16", shape=shape)
+    E, nplain_ref = rounded_training_oracle(out_wh, shape)
     module = net.model.module
     names = {id(p): n for n, p in module.named_parameters()}
     plain_w = {names[id(mod.weight)] for kind, mod, flags in module.plan_layers() if mod is not None and is_plain(kind, mod, flags)}
@@ -269,7 +278,7 @@ def check_training_step(dev):
             assert not torch.equal(g16[n], g32[n]), n          # (the half-precision weight gradient really ran)
     print("fp16 training: losses %.9g (fp32) %.9g (fp16), worst r_p / E_p %.3g" % (loss32, loss16, worst))
     # precision="fp16" alone stays an inference mode: the fp32 step bit for bit
-    g_inf, loss_inf, _, _ = step_gradients(dev, "fp32", precision="fp16")
+    g_inf, loss_inf, _, _ = step_gradients(dev, "fp32", precision="fp16", shape=shape)
     assert loss_inf == loss32
     for n in g32:
         assert torch.equal(g_inf[n], g32[n]), n

@@ -202,16 +202,20 @@ def _oracle_model(weights, dtype, mode):
     return model
 
 
-def _oracle_target(out_wh):
-    b, h, w = tc.TRAIN_SHAPE
+def _oracle_target(out_wh, shape=tc.TRAIN_SHAPE):
+    b, h, w = shape
     return torch.from_numpy(cases.target_batch(b, 7, out_wh, in_wh=(w, h), seed=7))
 
 
+def stored_training_oracle(out_wh, shape=tc.TRAIN_SHAPE):
+    """{parameter name: E_p}; computed once per process and shape."""
+    return _stored_training_oracle(out_wh, shape)
+
+
 @functools.lru_cache(maxsize=None)
-def stored_training_oracle(out_wh):
-    """{parameter name: E_p}; computed once per process."""
-    wts, x = tc.training_case()
-    t = _oracle_target(out_wh)
+def _stored_training_oracle(out_wh, shape):
+    wts, x = tc.training_case(shape)
+    t = _oracle_target(out_wh, shape)
     E = {}
     for dtype in (torch.float32, torch.float64):
         grads = {}
@@ -246,27 +250,28 @@ def oracle_loss_gap(out_wh, steps=20):
     return rho, runs
 
 
-def training_network(dev, storage="fp16", train_precision="fp16", optimizer="sgd", lr=0.0):
-    net = tc.training_network(dev, train_precision, optimizer=optimizer, lr=lr)
+def training_network(dev, storage="fp16", train_precision="fp16", optimizer="sgd", lr=0.0, shape=tc.TRAIN_SHAPE):
+    net = tc.training_network(dev, train_precision, optimizer=optimizer, lr=lr, shape=shape)
     net.model.module.train_activation_storage = storage
     return net
 
 
-def step_gradients(dev, storage, train_precision="fp16"):
-    net = training_network(dev, storage, train_precision)
-    _, x = tc.training_case()
-    t, out_wh = tc._target(net, dev)
+def step_gradients(dev, storage, train_precision="fp16", shape=tc.TRAIN_SHAPE):
+    net = training_network(dev, storage, train_precision, shape=shape)
+    _, x = tc.training_case(shape)
+    t, out_wh = tc._target(net, dev, shape)
     loss = float(net.train([pc.to(dev, x)], t).item())
     grads = {n: p.grad.detach().cpu().clone() for n, p in net.model.module.named_parameters()}
     return grads, loss, out_wh, net
 
 
-def check_training_step(dev):
-    """One vgg_q step at 2 x 64 x 96 with both switches "fp16" against the fp32 step of the same build, every parameter to 3 E_p."""
-    g32, loss32, out_wh, _ = step_gradients(dev, "fp32", "fp32")
-    g16, loss16, _, _ = step_gradients(dev, "fp32", "fp16")                   # fp16 products, fp32 storage
-    gs, loss_s, _, net = step_gradients(dev, "fp16", "fp16")
-    E = stored_training_oracle(out_wh)
+def check_training_step(dev, shape=tc.TRAIN_SHAPE):
+    """One vgg_q step at ``shape`` (2 x 64 x 96) with both switches "fp16" against the fp32 step of the same build, every parameter
+    to 3 E_p."""
+    g32, loss32, out_wh, _ = step_gradients(dev, "fp32", "fp32", shape=shape)
+    g16, loss16, _, _ = step_gradients(dev, "fp32", "fp16", shape=shape)      # fp16 products, fp32 storage
+    gs, loss_s, _, net = step_gradients(dev, "fp16", "fp16", shape=shape)
+    E = stored_training_oracle(out_wh, shape)
     m = net.model.module
     peak = m.half_storage_peak()
     assert 0.0 < peak < 65504.0 and peak == peak, peak
@@ -288,8 +293,8 @@ def check_training_step(dev):
     print("half-stored training: losses %.9g (fp32) %.9g (fp16) %.9g (fp16, half storage), peak %.6g, worst r_p / E_p %.3g, "
           "largest distance to the fp32-storage fp16 step %.3g" % (loss32, loss16, loss_s, peak, worst, dist))
     # a second step (lr = 0: same parameters) gives the same bits
-    _, x = tc.training_case()
-    t, _ = tc._target(net, dev)
+    _, x = tc.training_case(shape)
+    t, _ = tc._target(net, dev, shape)
     loss_again = float(net.train([pc.to(dev, x)], t).item())
     assert loss_again == loss_s
     for n, p in m.named_parameters():

@@ -804,6 +804,8 @@ def check_resnet_train_step(dev, arch="resnet_h", shape=(2, 64, 64), steps=1):
     l64 = F.mse_loss(ref64(x.double())[0], t.double())
     l64.backward()
     loss = net.train([to(dev, x)], to(dev, t))
+    print("resnet-train-step %s %s: loss %.8g, fp64 oracle %.8g, |difference| %.3g (torch fp32: %.3g)"
+          % (arch, shape, loss.item(), l64.item(), abs(loss.item() - l64.item()), abs(l32.item() - l64.item())))
     assert abs(loss.item() - l64.item()) <= 3 * abs(l32.item() - l64.item()) + 1e-4 * abs(l64.item())
     # direction of every parameter gradient vs the fp64 truth: a wiring error (missing branch, wrong tap, wrong
     # BN term) drops the cosine far below what fp32 round-off + ReLU-mask flips cost torch's own fp32 path
@@ -994,9 +996,10 @@ def check_resnet_training_ops(dev):
     assert float((ops.channel_sum(to(dev, cs)).cpu() - cs.sum((0, 1, 2))).abs().max()) < 1e-4
 
 
-def check_vgg_train_grads(dev, arch="vgg_f", shape=(2, 32, 48)):
-    """One training step of a VGG-type network against torch autograd on the CPU oracle (well-conditioned: no BN)."""
-    k = cases.CNN_CASES[arch][0]
+def check_vgg_train_grads(dev, arch="vgg_f", shape=(2, 32, 48), k=None):
+    """One training step of a VGG-type network against torch autograd on the CPU oracle (well-conditioned: no BN).
+    k: the keypoint count where ``arch`` is not a shipped architecture (a single-stage entry of oracle.models.VARIANTS: 7)."""
+    k = cases.CNN_CASES[arch][0] if k is None else k
     b, h, w = shape
     wts = om.recipe_weights(om.build_model(arch, k).state_dict(), cases.TRAIN_FINAL_KEYS, cases.TRAIN_FINAL_SCALE)
     ref = om.build_model(arch, k)
@@ -1010,6 +1013,8 @@ def check_vgg_train_grads(dev, arch="vgg_f", shape=(2, 32, 48)):
     lref = F.mse_loss(ref(x)[0], t)
     lref.backward()
     loss = net.train([to(dev, x)], to(dev, t))
+    print("vgg-train-grads %s %s: loss %.8g, oracle %.8g, relative difference %.3g"
+          % (arch, shape, loss.item(), lref.item(), abs(loss.item() - lref.item()) / abs(lref.item())))
     assert abs(loss.item() - lref.item()) <= 1e-5 * abs(lref.item()) + 1e-9
     # One ReLU whose fp32 pre-activation lands on the other side of 0 than the oracle's (measured: 1 element in 98 304 at
     # this size) changes every upstream gradient by ~1e-3 of its maximum, so element-wise equality at 1e-5 is not a
