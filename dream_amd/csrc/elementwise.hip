@@ -6,6 +6,7 @@
 // Reference call sites: nn.MaxPool2d(2) dream/models.py:589,765-771; nn.Upsample dream/models.py:691,703;
 // nn.ReLU(inplace) throughout models.py; torch.nn.MSELoss dream/network.py:260-261,359;
 // torch.optim.Adam / SGD dream/network.py:666-685.
+#include <type_traits>
 #include <dream_cdna4.h>
 #include "common.h"
 #include "half_store.h"
@@ -25,22 +26,61 @@ inline unsigned grid_for(size_t work_items, int block = 256) {
     return (unsigned)g;
 }
 
-// ---- max-pool 2x2, NHWC, channels in float4 groups ------------------------------------------------
-__global__ void __launch_bounds__(256) maxpool2_kernel(const f32x4 *x, f32x4 *y, int B, int H, int W, int C4) {
+// The tail of an entry point: the launch on 256-lane workgroups, then the runtime's verdict (0 = launched; 2 = refused, error text set).
+// launch_stream sizes the capped grid of a grid-stride kernel from its `total` work items.
+template <typename K, typename... A>
+int launch_grid(K kernel, dim3 grid, void *stream, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args...);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+template <typename K, typename... A>
+int launch_stream(K kernel, size_t total, void *stream, A... args) {
+    return launch_grid(kernel, dim3(grid_for(total)), stream, args...);
+}
+
+// A storage form of a streaming kernel is the vector type one lane moves: f32x4 (fp32 tensors), f16x8 (tensors stored as IEEE half:
+// activation_storage / inference_activation_storage / train_gradient_storage = "fp16"; 16 bytes each) or f16x4 (a half tensor read
+// beside an fp32 one, train_activation_storage="fp16": 8 bytes).  Its element type and lane count:
+template <typename V> using elem_t = std::decay_t<decltype(V()[0])>;
+template <typename V> constexpr int lanes_of = sizeof(V) / sizeof(elem_t<V>);
+
+// Where work item i of a grid-stride loop over a dense NHWC tensor sits.  split_bhwtc: [B][rows][cols][taps][Cv] (im2col3s2's patch
+// rows) -> channel group c, tap t, column x, row y, frame b; split_bhwc: [B][rows][cols][Cv] -> c, x, y, b.
+//     const auto [c, ox, oy, b] = split_bhwc(i, C4, Wo, Ho);
+struct Bhwtc { int c, t, x, y, b; };
+struct Bhwc { int c, x, y, b; };
+DREAM_DEVICE Bhwtc split_bhwtc(size_t i, int Cv, int taps, int cols, int rows) {
+    Bhwtc p;
+    p.c = (int)(i % Cv);
+    size_t r = i / Cv;
+    p.t = (int)(r % taps);
+    r /= taps;
+    p.x = (int)(r % cols);
+    r /= cols;
+    p.y = (int)(r % rows);
+    p.b = (int)(r / rows);
+    return p;
+}
+DREAM_DEVICE Bhwc split_bhwc(size_t i, int Cv, int cols, int rows) {
+    const Bhwtc p = split_bhwtc(i, Cv, 1, cols, rows);
+    return {p.c, p.x, p.y, p.b};
+}
+
+// ---- max-pool 2x2, NHWC, one vector of channels per lane -------------------------------------------
+// On halfs: the maximum of four halfs is one of them -- exact, no rounding, nothing to publish
+template <typename V>
+__global__ void __launch_bounds__(256) maxpool2_kernel(const V *x, V *y, int B, int H, int W, int Cv) {
     const int Ho = H / 2, Wo = W / 2;
-    const size_t total = (size_t)B * Ho * Wo * C4;
+    const size_t total = (size_t)B * Ho * Wo * Cv;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const f32x4 *s = x + (((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c;
-        const f32x4 v00 = s[0], v01 = s[C4], v10 = s[(size_t)W * C4], v11 = s[(size_t)W * C4 + C4];
-        f32x4 o;
+        const auto [c, ox, oy, b] = split_bhwc(i, Cv, Wo, Ho);
+        const V *s = x + (((size_t)b * H + 2 * oy) * W + 2 * ox) * Cv + c;
+        const V v00 = s[0], v01 = s[Cv], v10 = s[(size_t)W * Cv], v11 = s[(size_t)W * Cv + Cv];
+        V o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaxf(v00[k], v01[k]), fmaxf(v10[k], v11[k]));
+        for (int k = 0; k < lanes_of<V>; ++k)
+            o[k] = (elem_t<V>)fmaxf(fmaxf((float)v00[k], (float)v01[k]), fmaxf((float)v10[k], (float)v11[k]));
         y[i] = o;
     }
 }
@@ -50,61 +90,57 @@ __global__ void __launch_bounds__(256) maxpool2_kernel(const f32x4 *x, f32x4 *y,
 // One thread per 2x2 WINDOW (and channel quad): its four inputs are loaded once, the window's gradient goes to the first maximum, the
 // other three outputs are zeros (round 4: one thread per INPUT pixel loaded every window four times over: 3.9 TB/s on 64 x 400 x 400).
 // The thread of the last window of a row / column also zeroes the odd extent's leftover column / row.
-template <bool RELU>
-__global__ void __launch_bounds__(256) maxpool2_bwd_kernel(const f32x4 *dy, const f32x4 *x, f32x4 *dx,
-                                                           int B, int H, int W, int C4) {
+// Storage forms <GV of dy and dx, XV of x>: <f32x4, f32x4>; <f32x4, f16x4>, the forward input stored as half
+// (train_activation_storage="fp16"); <f16x8, f16x8>, the gradients half as well (train_gradient_storage="fp16": stored times 2^e_g).
+// A half compares as its fp32 value, so the first maximum and the RELU mask are those of the fp32 form on the widened x; every dx is a
+// copy of a dy or zero -- exact in every form, so no scale is read and none is applied.
+template <bool RELU, typename GV, typename XV>
+__global__ void __launch_bounds__(256) maxpool2_bwd_kernel(const GV *dy, const XV *x, GV *dx, int B, int H, int W, int Cv) {
+    static_assert(lanes_of<GV> == lanes_of<XV>, "dy and x are cut into the same channel groups");
     const int Ho = H / 2, Wo = W / 2;
-    const size_t total = (size_t)B * Ho * Wo * C4;
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    const size_t total = (size_t)B * Ho * Wo * Cv;
+    const GV zero = {};
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c, row = (size_t)W * C4;
-        const f32x4 v[4] = {x[base], x[base + C4], x[base + row], x[base + row + C4]};
-        const f32x4 g = dy[i];
-        f32x4 o[4] = {zero, zero, zero, zero};
+        const auto [c, ox, oy, b] = split_bhwc(i, Cv, Wo, Ho);
+        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * Cv + c, row = (size_t)W * Cv;
+        const XV v[4] = {x[base], x[base + Cv], x[base + row], x[base + row + Cv]};
+        const GV g = dy[i];
+        GV o[4] = {zero, zero, zero, zero};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < lanes_of<GV>; ++k) {
             int arg = 0;
-            float best = v[0][k];
+            float best = (float)v[0][k];
 #pragma unroll
             for (int j = 1; j < 4; ++j)
-                if (v[j][k] > best) { best = v[j][k]; arg = j; }
+                if ((float)v[j][k] > best) { best = (float)v[j][k]; arg = j; }
             // RELU: x is a ReLU output, and the gradient continues through that ReLU (mask x > 0) in the same pass
-            const float gk = (!RELU || best > 0.0f) ? g[k] : 0.0f;
+            const elem_t<GV> gk = (!RELU || best > 0.0f) ? g[k] : (elem_t<GV>)0;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : 0.0f;
+            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : (elem_t<GV>)0;
         }
         dx[base] = o[0];
-        dx[base + C4] = o[1];
+        dx[base + Cv] = o[1];
         dx[base + row] = o[2];
-        dx[base + row + C4] = o[3];
+        dx[base + row + Cv] = o[3];
         const bool last_x = (ox == Wo - 1) && (W & 1), last_y = (oy == Ho - 1) && (H & 1);
-        if (last_x) { dx[base + 2 * C4] = zero; dx[base + row + 2 * C4] = zero; }
-        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + C4] = zero; }
-        if (last_x && last_y) dx[base + 2 * row + 2 * C4] = zero;
+        if (last_x) { dx[base + 2 * Cv] = zero; dx[base + row + 2 * Cv] = zero; }
+        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + Cv] = zero; }
+        if (last_x && last_y) dx[base + 2 * row + 2 * Cv] = zero;
     }
 }
 
 // Every second pixel of every second row (the positions a stride-2 1x1 conv reads): y[b,i,j,:] = x[b,2i,2j,:], Ho = (H + 1) / 2.  The
 // ResNet trunk's three stride-2 downsample convs (dream/models.py:22-32 -> torchvision Bottleneck.downsample) then run as plain GEMMs
 // over the gathered rows (round 6) -- and the transpose: x[b,y,x,:] = ys[b,y/2,x/2,:] at even (y, x), zeros elsewhere (their data
-// gradient back on the block input's grid).
-__global__ void __launch_bounds__(256) subsample2_kernel(const f32x4 *x, f32x4 *y, int B, int H, int W, int C4) {
+// gradient back on the block input's grid).  subsample2 is a copy: on halfs (ResnetSimple's half-storage walk) nothing is
+// rounded and nothing published.
+template <typename V>
+__global__ void __launch_bounds__(256) subsample2_kernel(const V *x, V *y, int B, int H, int W, int Cv) {
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    const size_t total = (size_t)B * Ho * Wo * C4;
+    const size_t total = (size_t)B * Ho * Wo * Cv;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        y[i] = x[(((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c];
+        const auto [c, ox, oy, b] = split_bhwc(i, Cv, Wo, Ho);
+        y[i] = x[(((size_t)b * H + 2 * oy) * W + 2 * ox) * Cv + c];
     }
 }
 __global__ void __launch_bounds__(256) scatter2_kernel(const f32x4 *ys, f32x4 *x, int B, int H, int W, int C4) {
@@ -112,12 +148,7 @@ __global__ void __launch_bounds__(256) scatter2_kernel(const f32x4 *ys, f32x4 *x
     const size_t total = (size_t)B * H * W * C4;
     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int px = (int)(r % W);
-        r /= W;
-        const int py = (int)(r % H);
-        const int b = (int)(r / H);
+        const auto [c, px, py, b] = split_bhwc(i, C4, W, H);
         x[i] = ((px | py) & 1) ? zero : ys[(((size_t)b * Ho + (py >> 1)) * Wo + (px >> 1)) * C4 + c];
     }
 }
@@ -126,34 +157,23 @@ __global__ void __launch_bounds__(256) scatter2_kernel(const f32x4 *ys, f32x4 *x
 // t = 3 ky + kx, zeros outside the image; Ho = (H - 1) / 2 + 1.  On small maps (ResNet-101's layer4.0.conv2 at 16 frames: 2704 output pixels)
 // the direct kernel cannot fill the chip (36 TFLOP/s); as a GEMM over these rows the conv, its weight gradient and its data gradient run
 // on the 1x1 GEMM kernels.  col2im3s2 is the transpose: dx[b,y,x,:] = sum of the (one, two or four) patch entries that read pixel (y, x),
-// added in a fixed order (ky, then kx).
-__global__ void __launch_bounds__(256) im2col3s2_kernel(const f32x4 *x, f32x4 *col, int B, int H, int W, int C4) {
+// added in a fixed order (ky, then kx).  im2col3s2 copies (and zeros): on halfs nothing is rounded and nothing published.
+template <typename V>
+__global__ void __launch_bounds__(256) im2col3s2_kernel(const V *x, V *col, int B, int H, int W, int Cv) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const size_t total = (size_t)B * Ho * Wo * 9 * C4;
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    const size_t total = (size_t)B * Ho * Wo * 9 * Cv;
+    const V zero = {};
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int t = (int)(r % 9);
-        r /= 9;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
+        const auto [c, t, ox, oy, b] = split_bhwtc(i, Cv, 9, Wo, Ho);
         const int py = 2 * oy - 1 + t / 3, px = 2 * ox - 1 + t % 3;
-        col[i] = (py >= 0 && py < H && px >= 0 && px < W) ? x[(((size_t)b * H + py) * W + px) * C4 + c] : zero;
+        col[i] = (py >= 0 && py < H && px >= 0 && px < W) ? x[(((size_t)b * H + py) * W + px) * Cv + c] : zero;
     }
 }
 __global__ void __launch_bounds__(256) col2im3s2_kernel(const f32x4 *col, f32x4 *dx, int B, int H, int W, int C4) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t total = (size_t)B * H * W * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int px = (int)(r % W);
-        r /= W;
-        const int py = (int)(r % H);
-        const int b = (int)(r / H);
+        const auto [c, px, py, b] = split_bhwc(i, C4, W, H);
         f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -180,12 +200,7 @@ __global__ void __launch_bounds__(256) col2im4s2_kernel(const f32x4 *g, const f3
     const int Ho = 2 * H, Wo = 2 * W;
     const size_t total = (size_t)B * Ho * Wo * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int X = (int)(r % Wo);
-        r /= Wo;
-        const int Y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
+        const auto [c, X, Y, b] = split_bhwc(i, C4, Wo, Ho);
         const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
         f32x4 acc = (bias && !scale) ? bias[c] : zero;
 #pragma unroll
@@ -213,12 +228,7 @@ __global__ void __launch_bounds__(256) upsample2_bwd_kernel(const f32x4 *dy, f32
     const int Hs = H / 2, Ws = W / 2;
     const size_t total = (size_t)B * Hs * Ws * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int sx = (int)(r % Ws);
-        r /= Ws;
-        const int sy = (int)(r % Hs);
-        const int b = (int)(r / Hs);
+        const auto [c, sx, sy, b] = split_bhwc(i, C4, Ws, Hs);
         const f32x4 *s = dy + (((size_t)b * H + 2 * sy) * W + 2 * sx) * C4 + c;
         const f32x4 a = s[0], bb = s[C4], cc = s[(size_t)W * C4], d = s[(size_t)W * C4 + C4];
         f32x4 o;
@@ -440,12 +450,7 @@ __global__ void __launch_bounds__(256) im2col_nchw_kernel(const float *x, float 
     const size_t total = (size_t)B * Ho * Wo * Kpad;
     const int K = C * KH * KW;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int k = (int)(idx % Kpad);
-        size_t r = idx / Kpad;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
+        const auto [k, ox, oy, b] = split_bhwc(idx, Kpad, Wo, Ho);
         float v = 0.0f;
         if (k < K) {
             const int kx = k % KW, ky = (k / KW) % KH, c = k / (KW * KH);
@@ -490,12 +495,7 @@ __global__ void __launch_bounds__(256) im2col_nchw_fixed_kernel(const float *x, 
 __global__ void __launch_bounds__(256) maxpool3s2_kernel(const f32x4 *x, f32x4 *y, int B, int H, int W, int C4, int Ho, int Wo) {
     const size_t total = (size_t)B * Ho * Wo * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
+        const auto [c, ox, oy, b] = split_bhwc(i, C4, Wo, Ho);
         const float ninf = -__builtin_huge_valf();
         f32x4 o = {ninf, ninf, ninf, ninf};
 #pragma unroll
@@ -523,12 +523,7 @@ __global__ void __launch_bounds__(256) maxpool3s2_bwd_kernel(const f32x4 *dy, co
                                                              int C4, int Ho, int Wo) {
     const size_t total = (size_t)B * H * W * C4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ix = (int)(r % W);
-        r /= W;
-        const int iy = (int)(r % H);
-        const int b = (int)(r / H);
+        const auto [c, ix, iy, b] = split_bhwc(i, C4, W, H);
         f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
         // windows oy with 2*oy-1 <= iy <= 2*oy+1
         const int oy_lo = iy / 2, oy_hi = (iy + 1) / 2, ox_lo = ix / 2, ox_hi = (ix + 1) / 2;
@@ -636,117 +631,44 @@ __global__ void __launch_bounds__(256) add_inplace_kernel(float *dst, const floa
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] += src[i];
 }
 
+// What a tensor of E keeps of an fp32 value: the value, or the stored-value rule of the half tensors (half_store.h)
+template <typename E> DREAM_DEVICE E stored_as(float t);
+template <> DREAM_DEVICE float stored_as<float>(float t) { return t; }
+template <> DREAM_DEVICE _Float16 stored_as<_Float16>(float t) { return sat_half(t); }
+
 // out = a + b (encoder skip tensors joining the decoder, dream/models.py:774-799); optionally publishes max|out|.
-__global__ void __launch_bounds__(256) add_kernel(const float *a, const float *b, float *out, size_t n, unsigned *amax) {
-    const size_t n4 = n / 4;
+// On halfs (activation_storage="fp16"): out = half(a + b), the fp32 sum of two halfs (exact but for the one rounding of the add),
+// saturated to +-65504, rounded to nearest even; max|a + b| is published before the saturation.
+template <typename V>
+__global__ void __launch_bounds__(256) add_kernel(const elem_t<V> *a, const elem_t<V> *b, elem_t<V> *out, size_t n, unsigned *amax) {
+    const size_t nv = n / lanes_of<V>;
     float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        f32x4 u = ((const f32x4 *)a)[i];
-        const f32x4 v = ((const f32x4 *)b)[i];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
+        const V u = ((const V *)a)[i], v = ((const V *)b)[i];
+        V o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            u[k] += v[k];
-            m = fmaxf(m, fabsf(u[k]));
-        }
-        ((f32x4 *)out)[i] = u;
-    }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float u = a[i] + b[i];
-        out[i] = u;
-        m = fmaxf(m, fabsf(u));
-    }
-    if (amax) publish_amax(amax, m);
-}
-
-// ---- activations stored as IEEE half (activation_storage="fp16"): 16 bytes = 8 halfs per lane -----------------------------------
-// max-pool 2x2 on halfs: the maximum of four halfs is one of them -- exact, no rounding, nothing to publish
-__global__ void __launch_bounds__(256) maxpool2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8) {
-    const int Ho = H / 2, Wo = W / 2;
-    const size_t total = (size_t)B * Ho * Wo * C8;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C8);
-        size_t r = i / C8;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const f16x8 *s = x + (((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c;
-        const f16x8 v00 = s[0], v01 = s[C8], v10 = s[(size_t)W * C8], v11 = s[(size_t)W * C8 + C8];
-        f16x8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (_Float16)fmaxf(fmaxf((float)v00[k], (float)v01[k]), fmaxf((float)v10[k], (float)v11[k]));
-        y[i] = o;
-    }
-}
-
-// out = half(a + b): the fp32 sum of two halfs (exact but for the one rounding of the add), saturated to +-65504, rounded to nearest
-// even; publishes max|a + b| before the saturation
-__global__ void __launch_bounds__(256) add_f16_kernel(const _Float16 *a, const _Float16 *b, _Float16 *out, size_t n, unsigned *amax) {
-    const size_t n8 = n / 8;
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        const f16x8 u = ((const f16x8 *)a)[i], v = ((const f16x8 *)b)[i];
-        f16x8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < lanes_of<V>; ++k) {
             const float t = (float)u[k] + (float)v[k];
             m = fmaxf(m, fabsf(t));
-            o[k] = sat_half(t);
+            o[k] = stored_as<elem_t<V>>(t);
         }
-        ((f16x8 *)out)[i] = o;
+        ((V *)out)[i] = o;
     }
-    for (size_t i = n8 * 8 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    for (size_t i = nv * lanes_of<V> + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float t = (float)a[i] + (float)b[i];
         m = fmaxf(m, fabsf(t));
-        out[i] = sat_half(t);
+        out[i] = stored_as<elem_t<V>>(t);
     }
     if (amax) publish_amax(amax, m);
 }
 
 // ---- ResnetSimple's half-storage walk (inference_activation_storage="fp16"): 16 bytes = 8 halfs per lane -------------
-// subsample2_kernel / im2col3s2_kernel on halfs: copies (and zeros), nothing is rounded, nothing to publish
-__global__ void __launch_bounds__(256) subsample2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8) {
-    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    const size_t total = (size_t)B * Ho * Wo * C8;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C8);
-        size_t r = i / C8;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        y[i] = x[(((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c];
-    }
-}
-__global__ void __launch_bounds__(256) im2col3s2_f16_kernel(const f16x8 *x, f16x8 *col, int B, int H, int W, int C8) {
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const size_t total = (size_t)B * Ho * Wo * 9 * C8;
-    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C8);
-        size_t r = i / C8;
-        const int t = (int)(r % 9);
-        r /= 9;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const int py = 2 * oy - 1 + t / 3, px = 2 * ox - 1 + t % 3;
-        col[i] = (py >= 0 && py < H && px >= 0 && px < W) ? x[(((size_t)b * H + py) * W + px) * C8 + c] : zero;
-    }
-}
-
 // maxpool3s2_kernel on halfs: the maximum of up to nine halfs is one of them -- exact; padding never wins (-inf), and every window
 // holds a pixel of the image
 __global__ void __launch_bounds__(256) maxpool3s2_f16_kernel(const f16x8 *x, f16x8 *y, int B, int H, int W, int C8, int Ho, int Wo) {
     const size_t total = (size_t)B * Ho * Wo * C8;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C8);
-        size_t r = i / C8;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
+        const auto [c, ox, oy, b] = split_bhwc(i, C8, Wo, Ho);
         const float ninf = -__builtin_huge_valf();
         float o[8] = {ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
 #pragma unroll
@@ -804,87 +726,6 @@ __global__ void __launch_bounds__(256) im2col_nchw_f16_fixed_kernel(const float 
 }
 
 // ---- training with the saved activations stored as IEEE half (train_activation_storage="fp16") -------------------------------------
-// maxpool2_bwd_kernel with a half forward input: dy and dx stay fp32, x is read as four halfs (8 bytes) per lane and window element.
-// A half compares as its fp32 value, so the first maximum in window scan order -- and the RELU mask -- are those of the fp32 kernel on
-// the widened x; leftover rows / columns of odd extents get zero the same way.
-template <bool RELU>
-__global__ void __launch_bounds__(256) maxpool2_bwd_x16_kernel(const f32x4 *dy, const f16x4 *x, f32x4 *dx, int B, int H, int W, int C4) {
-    const int Ho = H / 2, Wo = W / 2;
-    const size_t total = (size_t)B * Ho * Wo * C4;
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        size_t r = i / C4;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c, row = (size_t)W * C4;
-        const f16x4 v[4] = {x[base], x[base + C4], x[base + row], x[base + row + C4]};
-        const f32x4 g = dy[i];
-        f32x4 o[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int arg = 0;
-            float best = (float)v[0][k];
-#pragma unroll
-            for (int j = 1; j < 4; ++j)
-                if ((float)v[j][k] > best) { best = (float)v[j][k]; arg = j; }
-            const float gk = (!RELU || best > 0.0f) ? g[k] : 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : 0.0f;
-        }
-        dx[base] = o[0];
-        dx[base + C4] = o[1];
-        dx[base + row] = o[2];
-        dx[base + row + C4] = o[3];
-        const bool last_x = (ox == Wo - 1) && (W & 1), last_y = (oy == Ho - 1) && (H & 1);
-        if (last_x) { dx[base + 2 * C4] = zero; dx[base + row + 2 * C4] = zero; }
-        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + C4] = zero; }
-        if (last_x && last_y) dx[base + 2 * row + 2 * C4] = zero;
-    }
-}
-
-// ... and with dy and dx half as well (train_gradient_storage="fp16": the gradients of the run are stored as half times 2^e_g): 8 halfs
-// (16 bytes) per lane and window element.  Exact -- every dx is a copy of a dy or zero --, so no scale is read and none is applied.
-template <bool RELU>
-__global__ void __launch_bounds__(256) maxpool2_bwd_x16_dy16_kernel(const f16x8 *dy, const f16x8 *x, f16x8 *dx, int B, int H, int W, int C8) {
-    const int Ho = H / 2, Wo = W / 2;
-    const size_t total = (size_t)B * Ho * Wo * C8;
-    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C8);
-        size_t r = i / C8;
-        const int ox = (int)(r % Wo);
-        r /= Wo;
-        const int oy = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const size_t base = (((size_t)b * H + 2 * oy) * W + 2 * ox) * C8 + c, row = (size_t)W * C8;
-        const f16x8 v[4] = {x[base], x[base + C8], x[base + row], x[base + row + C8]};
-        const f16x8 g = dy[i];
-        f16x8 o[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            int arg = 0;
-            float best = (float)v[0][k];
-#pragma unroll
-            for (int j = 1; j < 4; ++j)
-                if ((float)v[j][k] > best) { best = (float)v[j][k]; arg = j; }
-            const _Float16 gk = (!RELU || best > 0.0f) ? g[k] : (_Float16)0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j][k] = arg == j ? gk : (_Float16)0;
-        }
-        dx[base] = o[0];
-        dx[base + C8] = o[1];
-        dx[base + row] = o[2];
-        dx[base + row + C8] = o[3];
-        const bool last_x = (ox == Wo - 1) && (W & 1), last_y = (oy == Ho - 1) && (H & 1);
-        if (last_x) { dx[base + 2 * C8] = zero; dx[base + row + 2 * C8] = zero; }
-        if (last_y) { dx[base + 2 * row] = zero; dx[base + 2 * row + C8] = zero; }
-        if (last_x && last_y) dx[base + 2 * row + 2 * C8] = zero;
-    }
-}
-
 // out = float(x): the widening pass behind the last half-storage conv of a training forward (exact); 8 halfs per lane
 __global__ void __launch_bounds__(256) widen_f16_kernel(const _Float16 *x, float *out, size_t n) {
     const size_t n8 = n / 8;
@@ -943,203 +784,130 @@ __global__ void __launch_bounds__(256) stage_input_bwd_kernel(const float *g, fl
     }
 }
 
+// The six dream_maxpool2*_bwd* entry points: <GV, XV> picks the storage form (maxpool2_bwd_kernel), `name` goes into the error texts.
+// The fp32 form has never asked for C > 0 (nothing is launched over then) or for aligned pointers, and still does not.
+template <bool RELU, typename GV, typename XV>
+int maxpool2_bwd(const char *name, const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream) {
+    constexpr int L = lanes_of<GV>;
+    constexpr bool half_x = sizeof(elem_t<XV>) == 2, half_dy = sizeof(elem_t<GV>) == 2;
+    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && (C > 0 || !half_x) && C % L == 0,
+                  half_dy ? "%s: bad arguments (C %% 8)" : "%s: bad arguments", name);
+    DREAM_REQUIRE(!half_x || (aligned16(dy, dx) && ((size_t)x & (sizeof(XV) - 1)) == 0),
+                  half_dy ? "%s: dy, x, dx must be 16-byte aligned" : "%s: dy, dx must be 16-byte and x 8-byte aligned", name);
+    return launch_stream(maxpool2_bwd_kernel<RELU, GV, XV>, (size_t)B * (H / 2) * (W / 2) * (C / L), stream, (const GV *)dy, (const XV *)x,
+                         (GV *)dx, B, H, W, C / L);
+}
+
 }  // namespace
 
 extern "C" int dream_maxpool2_nhwc_f32(const float *x, float *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0, "maxpool2: bad arguments (C=%d must be a multiple of 4)", C);
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(maxpool2_kernel<f32x4>, (size_t)B * (H / 2) * (W / 2) * (C / 4), stream, (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4);
 }
 extern "C" int dream_maxpool2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_f16: bad arguments (C=%d must be a multiple of 8)", C);
     DREAM_REQUIRE(aligned16(x, y), "maxpool2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(maxpool2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(maxpool2_kernel<f16x8>, (size_t)B * (H / 2) * (W / 2) * (C / 8), stream, (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
 }
 extern "C" int dream_maxpool2_bwd_nhwc_f32(const float *dy, const float *x, float *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C % 4 == 0, "maxpool2_bwd: bad arguments");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (const f32x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<false, f32x4, f32x4>("maxpool2_bwd", dy, x, dx, B, H, W, C, stream);
 }
 extern "C" int dream_maxpool2_relu_bwd_nhwc_f32(const float *dy, const float *x, float *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C % 4 == 0, "maxpool2_relu_bwd: bad arguments");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (const f32x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<true, f32x4, f32x4>("maxpool2_relu_bwd", dy, x, dx, B, H, W, C, stream);
 }
 // ... with the forward input x stored as IEEE half (train_activation_storage="fp16"): dy, dx fp32; x [B,H,W,C] half, 8-byte aligned
 extern "C" int dream_maxpool2_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0, "maxpool2_bwd_x16: bad arguments");
-    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 7) == 0, "maxpool2_bwd_x16: dy, dx must be 16-byte and x 8-byte aligned");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_x16_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (const f16x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<false, f32x4, f16x4>("maxpool2_bwd_x16", dy, x, dx, B, H, W, C, stream);
 }
 extern "C" int dream_maxpool2_relu_bwd_x16_nhwc_f32(const float *dy, const void *x, float *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0, "maxpool2_relu_bwd_x16: bad arguments");
-    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 7) == 0, "maxpool2_relu_bwd_x16: dy, dx must be 16-byte and x 8-byte aligned");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_x16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (const f16x4 *)x, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<true, f32x4, f16x4>("maxpool2_relu_bwd_x16", dy, x, dx, B, H, W, C, stream);
 }
 // ... with dy and dx stored as IEEE half too (train_gradient_storage="fp16"): dy [B,H/2,W/2,C], x, dx [B,H,W,C] half, 16-byte aligned,
 // C % 8 == 0; exact (a copy or zero)
 extern "C" int dream_maxpool2_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_bwd_x16_dy16: bad arguments (C %% 8)");
-    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 15) == 0, "maxpool2_bwd_x16_dy16: dy, x, dx must be 16-byte aligned");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(maxpool2_bwd_x16_dy16_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16x8 *)dy, (const f16x8 *)x, (f16x8 *)dx, B, H, W, C / 8);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<false, f16x8, f16x8>("maxpool2_bwd_x16_dy16", dy, x, dx, B, H, W, C, stream);
 }
 extern "C" int dream_maxpool2_relu_bwd_x16_dy16_nhwc_f16(const void *dy, const void *x, void *dx, int B, int H, int W, int C, void *stream) {
-    DREAM_REQUIRE(dy && x && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2_relu_bwd_x16_dy16: bad arguments (C %% 8)");
-    DREAM_REQUIRE(aligned16(dy, dx) && ((size_t)x & 15) == 0, "maxpool2_relu_bwd_x16_dy16: dy, x, dx must be 16-byte aligned");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(maxpool2_bwd_x16_dy16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16x8 *)dy, (const f16x8 *)x, (f16x8 *)dx, B, H, W, C / 8);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return maxpool2_bwd<true, f16x8, f16x8>("maxpool2_relu_bwd_x16_dy16", dy, x, dx, B, H, W, C, stream);
 }
 // out[i] = float(x[i]), i < n: x half, out fp32, both 16-byte aligned
 extern "C" int dream_widen_f16_f32(const void *x, float *out, size_t n, void *stream) {
     DREAM_REQUIRE(x && out, "widen_f16: null pointer");
     DREAM_REQUIRE(aligned16(x, out), "widen_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
-    hipLaunchKernelGGL(widen_f16_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x, out, n);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(widen_f16_kernel, n / 8 + 1, stream, (const _Float16 *)x, out, n);
 }
 extern "C" int dream_subsample2_nhwc_f32(const float *x, float *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "subsample2: bad arguments (C=%d must be a multiple of 4)", C);
     const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
-    hipLaunchKernelGGL(subsample2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(subsample2_kernel<f32x4>, total, stream, (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4);
 }
 extern "C" int dream_scatter2_nhwc_f32(const float *ys, float *x, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(ys && x && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "scatter2: bad arguments (C=%d must be a multiple of 4)", C);
-    const size_t total = (size_t)B * H * W * (C / 4);
-    hipLaunchKernelGGL(scatter2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)ys, (f32x4 *)x, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(scatter2_kernel, (size_t)B * H * W * (C / 4), stream, (const f32x4 *)ys, (f32x4 *)x, B, H, W, C / 4);
 }
 extern "C" int dream_im2col3s2_nhwc_f32(const float *x, float *col, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && col && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "im2col3s2: bad arguments (C=%d must be a multiple of 4)", C);
     const size_t total = (size_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 9 * (C / 4);
-    hipLaunchKernelGGL(im2col3s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)x, (f32x4 *)col, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(im2col3s2_kernel<f32x4>, total, stream, (const f32x4 *)x, (f32x4 *)col, B, H, W, C / 4);
 }
 extern "C" int dream_col2im3s2_nhwc_f32(const float *col, float *dx, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(col && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "col2im3s2: bad arguments (C=%d must be a multiple of 4)", C);
-    const size_t total = (size_t)B * H * W * (C / 4);
-    hipLaunchKernelGGL(col2im3s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)col, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(col2im3s2_kernel, (size_t)B * H * W * (C / 4), stream, (const f32x4 *)col, (f32x4 *)dx, B, H, W, C / 4);
 }
 extern "C" int dream_col2im4s2_nhwc_f32(const float *g, const float *scale, const float *shift, float *z, int B, int H, int W, int C, int flags,
                                         void *stream) {
     DREAM_REQUIRE(g && z && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "col2im4s2: bad arguments (C=%d must be a multiple of 4)", C);
     DREAM_REQUIRE((flags & ~DREAM_CONV_RELU) == 0, "col2im4s2: unsupported flags 0x%x", flags);
-    const size_t total = (size_t)B * 2 * H * 2 * W * (C / 4);
-    hipLaunchKernelGGL(col2im4s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)g, (const f32x4 *)scale,
-                       (const f32x4 *)shift, (f32x4 *)z, B, H, W, C / 4, (flags & DREAM_CONV_RELU) ? 1 : 0);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(col2im4s2_kernel, (size_t)B * 2 * H * 2 * W * (C / 4), stream, (const f32x4 *)g, (const f32x4 *)scale,
+                         (const f32x4 *)shift, (f32x4 *)z, B, H, W, C / 4, (flags & DREAM_CONV_RELU) ? 1 : 0);
 }
 extern "C" int dream_upsample2_bwd_nhwc_f32(const float *dy, float *dx, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(dy && dx && B > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "upsample2_bwd: bad arguments");
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(upsample2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (f32x4 *)dx, B, H, W, C / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(upsample2_bwd_kernel, (size_t)B * (H / 2) * (W / 2) * (C / 4), stream, (const f32x4 *)dy, (f32x4 *)dx, B, H, W, C / 4);
 }
 extern "C" int dream_relu_bwd_f32(const float *dy, const float *y, float *dx, size_t n, void *stream) {
     DREAM_REQUIRE(dy && y && dx, "relu_bwd: null pointer");
     DREAM_REQUIRE(aligned16(dy, y, dx), "relu_bwd: pointers must be 16-byte aligned (the kernel moves float4)");
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(relu_bwd_kernel, n / 4 + 1, stream, dy, y, dx, n);
 }
 extern "C" int dream_nchw_to_nhwc_f32(const float *x, float *y, int B, int C, int H, int W, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc: bad arguments");
-    const dim3 grid(ceil_div(H * W, 64), ceil_div(C, 64), B);
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, C, H * W);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(nchw_to_nhwc_kernel, dim3(ceil_div(H * W, 64), ceil_div(C, 64), B), stream, x, y, C, H * W);
 }
 extern "C" int dream_nchw_to_nhwc_pad_f32(const float *x, float *y, int B, int C, int H, int W, int Cpad, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, "nchw_to_nhwc_pad: bad arguments");
-    hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel, dim3(grid_for((size_t)B * H * W * Cpad)), dim3(256), 0, (hipStream_t)stream,
-                       x, y, B, C, H * W, Cpad);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(nchw_to_nhwc_pad_kernel, (size_t)B * H * W * Cpad, stream, x, y, B, C, H * W, Cpad);
 }
 extern "C" int dream_nhwc_to_nchw_f32(const float *x, float *y, int B, int C, int H, int W, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0, "nhwc_to_nchw: bad arguments");
-    const dim3 grid(ceil_div(H * W, 64), ceil_div(C, 64), B);
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, C, H * W);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(nhwc_to_nchw_kernel, dim3(ceil_div(H * W, 64), ceil_div(C, 64), B), stream, x, y, C, H * W);
 }
 extern "C" int dream_pack_conv3x3_weight(const float *w_oihw, float *packed, int Cout, int Cin, int CoutPad,
                                          int CinPad, int mode, void *stream) {
     DREAM_REQUIRE(w_oihw && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1), "pack_conv3x3_weight: bad arguments");
     // CoutPad / CinPad are the padded ROW / COLUMN counts of the packed tensor (see pack_w_kernel)
     DREAM_REQUIRE(CoutPad >= (mode == 0 ? Cout : Cin) && CinPad >= (mode == 0 ? Cin : Cout), "pack_conv3x3_weight: padding smaller than the tensor");
-    hipLaunchKernelGGL(pack_w_kernel, dim3(grid_for((size_t)9 * CoutPad * CinPad)), dim3(256), 0, (hipStream_t)stream,
-                       w_oihw, packed, Cout, Cin, CoutPad, CinPad, mode, 9);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(pack_w_kernel, (size_t)9 * CoutPad * CinPad, stream, w_oihw, packed, Cout, Cin, CoutPad, CinPad, mode, 9);
 }
 extern "C" int dream_pack_conv_weight(const float *w_oihw, float *packed, int Cout, int Cin, int ntaps, int RowsPad,
                                       int ColsPad, int mode, void *stream) {
     DREAM_REQUIRE(w_oihw && packed && Cout > 0 && Cin > 0 && ntaps >= 1 && (mode == 0 || mode == 1), "pack_conv_weight: bad arguments");
     DREAM_REQUIRE(RowsPad >= (mode == 0 ? Cout : Cin) && ColsPad >= (mode == 0 ? Cin : Cout), "pack_conv_weight: padding smaller than the tensor");
-    hipLaunchKernelGGL(pack_w_kernel, dim3(grid_for((size_t)ntaps * RowsPad * ColsPad)), dim3(256), 0, (hipStream_t)stream,
-                       w_oihw, packed, Cout, Cin, RowsPad, ColsPad, mode, ntaps);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(pack_w_kernel, (size_t)ntaps * RowsPad * ColsPad, stream, w_oihw, packed, Cout, Cin, RowsPad, ColsPad, mode, ntaps);
 }
 extern "C" int dream_pack_convT4x4_weight(const float *wT, float *packed, int Cin, int Cout, int RowsPad, int ColsPad,
                                           void *stream) {
     DREAM_REQUIRE(wT && packed && Cin > 0 && Cout > 0 && RowsPad >= Cout && ColsPad >= Cin, "pack_convT4x4_weight: bad arguments");
-    hipLaunchKernelGGL(pack_wT4_kernel, dim3(grid_for((size_t)16 * RowsPad * ColsPad)), dim3(256), 0, (hipStream_t)stream,
-                       wT, packed, Cin, Cout, RowsPad, ColsPad);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(pack_wT4_kernel, (size_t)16 * RowsPad * ColsPad, stream, wT, packed, Cin, Cout, RowsPad, ColsPad);
 }
 extern "C" int dream_upsample_conv3x3_weight_as_convT4x4(const float *w_oihw, float *wT4, int Cout, int Cin, void *stream) {
     DREAM_REQUIRE(w_oihw && wT4 && Cout > 0 && Cin > 0, "upsample_conv3x3_weight: bad arguments");
-    hipLaunchKernelGGL(upsample_conv_weight_kernel, dim3(grid_for((size_t)16 * Cout * Cin)), dim3(256), 0, (hipStream_t)stream,
-                       w_oihw, wT4, Cout, Cin);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(upsample_conv_weight_kernel, (size_t)16 * Cout * Cin, stream, w_oihw, wT4, Cout, Cin);
 }
 extern "C" int dream_bn_fold_f32(const float *gamma, const float *beta, const float *running_mean, const float *running_var,
                                  const float *conv_bias, float eps, float *scale, float *shift, int C, void *stream) {
     DREAM_REQUIRE(gamma && beta && running_mean && running_var && scale && shift && C > 0, "bn_fold: bad arguments");
-    hipLaunchKernelGGL(bn_fold_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta, running_mean,
-                       running_var, conv_bias, eps, scale, shift, C);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(bn_fold_kernel, dim3(ceil_div(C, 256)), stream, gamma, beta, running_mean, running_var, conv_bias, eps, scale, shift, C);
 }
 extern "C" int dream_im2col_nchw_f32(const float *x, float *y, int B, int C, int H, int W, int KH, int KW, int stride,
                                      int pad, int Kpad, void *stream) {
@@ -1147,50 +915,33 @@ extern "C" int dream_im2col_nchw_f32(const float *x, float *y, int B, int C, int
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     DREAM_REQUIRE(Ho > 0 && Wo > 0, "im2col: empty output");
     if (C == 3 && KH == 7 && KW == 7 && stride == 2 && pad == 3 && Kpad % 4 == 0 && (size_t)Wo * (Kpad / 4) < ((size_t)1 << 30) &&
-        (size_t)C * H * W < ((size_t)1 << 30) && B <= 65535) {
-        hipLaunchKernelGGL((im2col_nchw_fixed_kernel<3, 7, 7, 2, 3>), dim3((unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                           x, y, H, W, Ho, Wo, Kpad);
-        DREAM_LAUNCH_OK();
-        return 0;
-    }
-    hipLaunchKernelGGL(im2col_nchw_kernel, dim3(grid_for((size_t)B * Ho * Wo * Kpad)), dim3(256), 0, (hipStream_t)stream,
-                       x, y, B, C, H, W, KH, KW, stride, pad, Ho, Wo, Kpad);
-    DREAM_LAUNCH_OK();
-    return 0;
+        (size_t)C * H * W < ((size_t)1 << 30) && B <= 65535)
+        return launch_grid(im2col_nchw_fixed_kernel<3, 7, 7, 2, 3>, dim3((unsigned)Ho, (unsigned)B), stream, x, y, H, W, Ho, Wo, Kpad);
+    return launch_stream(im2col_nchw_kernel, (size_t)B * Ho * Wo * Kpad, stream, x, y, B, C, H, W, KH, KW, stride, pad, Ho, Wo, Kpad);
 }
 extern "C" int dream_maxpool3s2_nhwc_f32(const float *x, float *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool3s2: bad arguments");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 4))), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4, Ho, Wo);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(maxpool3s2_kernel, (size_t)B * Ho * Wo * (C / 4), stream, (const f32x4 *)x, (f32x4 *)y, B, H, W, C / 4, Ho, Wo);
 }
 // ---- ResnetSimple's half-storage walk: the four streaming kernels on IEEE halfs (16-byte aligned, C % 8 == 0) --------------------
 extern "C" int dream_subsample2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "subsample2_f16: bad arguments (C=%d must be a multiple of 8)", C);
     DREAM_REQUIRE(aligned16(x, y), "subsample2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
     const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
-    hipLaunchKernelGGL(subsample2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(subsample2_kernel<f16x8>, total, stream, (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8);
 }
 extern "C" int dream_im2col3s2_nhwc_f16(const void *x, void *col, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && col && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "im2col3s2_f16: bad arguments (C=%d must be a multiple of 8)", C);
     DREAM_REQUIRE(aligned16(x, col), "im2col3s2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
     const size_t total = (size_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 9 * (C / 8);
-    hipLaunchKernelGGL(im2col3s2_f16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f16x8 *)x, (f16x8 *)col, B, H, W, C / 8);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(im2col3s2_kernel<f16x8>, total, stream, (const f16x8 *)x, (f16x8 *)col, B, H, W, C / 8);
 }
 extern "C" int dream_maxpool3s2_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "maxpool3s2_f16: bad arguments (C=%d must be a multiple of 8)", C);
     DREAM_REQUIRE(aligned16(x, y), "maxpool3s2_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_f16_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 8))), dim3(256), 0, (hipStream_t)stream,
-                       (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8, Ho, Wo);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(maxpool3s2_f16_kernel, (size_t)B * Ho * Wo * (C / 8), stream, (const f16x8 *)x, (f16x8 *)y, B, H, W, C / 8, Ho, Wo);
 }
 extern "C" int dream_im2col_nchw_f16(const float *x, void *y, unsigned *amax_out, int B, int C, int H, int W, int KH, int KW, int stride,
                                      int pad, int Kpad, void *stream) {
@@ -1202,34 +953,24 @@ extern "C" int dream_im2col_nchw_f16(const float *x, void *y, unsigned *amax_out
     DREAM_REQUIRE(Ho > 0 && Wo > 0, "im2col_f16: empty output");
     DREAM_REQUIRE((size_t)Wo * (Kpad / 8) < ((size_t)1 << 30) && (size_t)C * H * W < ((size_t)1 << 30) && B <= 65535,
                   "im2col_f16: the image or the batch is too large for the kernel's 32-bit indices");
-    hipLaunchKernelGGL((im2col_nchw_f16_fixed_kernel<3, 7, 7, 2, 3>), dim3((unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       x, (_Float16 *)y, H, W, Ho, Wo, Kpad, amax_out);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(im2col_nchw_f16_fixed_kernel<3, 7, 7, 2, 3>, dim3((unsigned)Ho, (unsigned)B), stream, x, (_Float16 *)y, H, W, Ho, Wo, Kpad,
+                       amax_out);
 }
 extern "C" int dream_unpack_conv3x3_weight(const float *packed, float *w_oihw, int Cout, int Cin, int CoutPad,
                                            int CinPad, void *stream) {
     DREAM_REQUIRE(w_oihw && packed && Cout > 0 && Cin > 0 && CoutPad >= Cout && CinPad >= Cin, "unpack: bad arguments");
-    hipLaunchKernelGGL(unpack_w_kernel, dim3(grid_for((size_t)9 * Cout * Cin)), dim3(256), 0, (hipStream_t)stream,
-                       packed, w_oihw, Cout, Cin, CoutPad, CinPad, 9);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(unpack_w_kernel, (size_t)9 * Cout * Cin, stream, packed, w_oihw, Cout, Cin, CoutPad, CinPad, 9);
 }
 extern "C" int dream_unpack_conv_weight(const float *packed, float *w, int Rows, int Cols, int ntaps, int RowsPad,
                                         int ColsPad, void *stream) {
     DREAM_REQUIRE(w && packed && Rows > 0 && Cols > 0 && ntaps > 0 && RowsPad >= Rows && ColsPad >= Cols, "unpack_conv_weight: bad arguments");
-    hipLaunchKernelGGL(unpack_w_kernel, dim3(grid_for((size_t)ntaps * Rows * Cols)), dim3(256), 0, (hipStream_t)stream,
-                       packed, w, Rows, Cols, RowsPad, ColsPad, ntaps);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(unpack_w_kernel, (size_t)ntaps * Rows * Cols, stream, packed, w, Rows, Cols, RowsPad, ColsPad, ntaps);
 }
 extern "C" int dream_maxpool3s2_bwd_nhwc_f32(const float *dy, const float *x, float *dx, int B, int H, int W, int C, void *stream) {
     DREAM_REQUIRE(dy && x && dx && B > 0 && H > 0 && W > 0 && C % 4 == 0, "maxpool3s2_bwd: bad arguments");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(grid_for((size_t)B * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream,
-                       (const f32x4 *)dy, (const f32x4 *)x, (f32x4 *)dx, B, H, W, C / 4, Ho, Wo);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(maxpool3s2_bwd_kernel, (size_t)B * H * W * (C / 4), stream, (const f32x4 *)dy, (const f32x4 *)x, (f32x4 *)dx, B, H, W,
+                         C / 4, Ho, Wo);
 }
 // Many tensors gathered into one flat buffer by ONE launch (the optimizer's flat gradient buffer: torch hands every parameter its
 // own gradient tensor, and 318 hipMemcpyAsync calls cost a ResNet-101 step 1.4 ms at its very end -- 3 % -- for 216 MB).  The
@@ -1257,10 +998,7 @@ extern "C" size_t dream_copy_chunk_bytes(void) { return sizeof(dream_copy_chunk)
 extern "C" int dream_multi_copy_f32(const void *srcs, const void *chunks, int nchunks, void *stream) {
     DREAM_REQUIRE(srcs && chunks && nchunks >= 0, "multi_copy: bad arguments");
     if (nchunks == 0) return 0;
-    hipLaunchKernelGGL(multi_copy_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const float *const *)srcs,
-                       (const dream_copy_chunk *)chunks);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(multi_copy_kernel, dim3((unsigned)nchunks), stream, (const float *const *)srcs, (const dream_copy_chunk *)chunks);
 }
 
 // MaxPool2d(3,2,1) for training: y and the winner's position inside its window (uint8, 0..8) / the backward pass from those
@@ -1268,19 +1006,15 @@ extern "C" int dream_maxpool3s2_idx_nhwc_f32(const float *x, float *y, unsigned 
     DREAM_REQUIRE(x && y && idx && B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool3s2_idx: bad arguments");
     DREAM_REQUIRE((size_t)H * W * C < ((size_t)1 << 31), "maxpool3s2_idx: image too large for 32-bit offsets");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_idx_kernel, dim3((unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)x,
-                       (f32x4 *)y, (u8x4 *)idx, H, W, C / 4, Ho, Wo);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(maxpool3s2_idx_kernel, dim3((unsigned)Ho, (unsigned)B), stream, (const f32x4 *)x, (f32x4 *)y, (u8x4 *)idx, H, W, C / 4,
+                       Ho, Wo);
 }
 extern "C" int dream_maxpool3s2_idx_bwd_nhwc_f32(const float *dy, const unsigned char *idx, float *dx, int B, int H, int W, int C,
                                                  void *stream) {
     DREAM_REQUIRE(dy && idx && dx && B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool3s2_idx_bwd: bad arguments");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3s2_idx_bwd_kernel, dim3((unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream, (const f32x4 *)dy,
-                       (const u8x4 *)idx, (f32x4 *)dx, H, W, C / 4, Ho, Wo);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_grid(maxpool3s2_idx_bwd_kernel, dim3((unsigned)H, (unsigned)B), stream, (const f32x4 *)dy, (const u8x4 *)idx, (f32x4 *)dx, H, W,
+                       C / 4, Ho, Wo);
 }
 // common.h: zero / copy whole words with a kernel (graph-safe replacements of hipMemsetAsync / hipMemcpyAsync)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1300,16 +1034,12 @@ __global__ void __launch_bounds__(256) copy_words_kernel(unsigned *dst, const un
 int dream_zero_words(void *dst, size_t nbytes, hipStream_t stream) {
     DREAM_REQUIRE(dst && nbytes % 4 == 0 && (((size_t)dst) & 3) == 0, "zero_words: whole aligned 32-bit words expected");
     if (nbytes == 0) return 0;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(grid_for(nbytes / 16 + 1)), dim3(256), 0, stream, (unsigned *)dst, nbytes / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(zero_words_kernel, nbytes / 16 + 1, stream, (unsigned *)dst, nbytes / 4);
 }
 int dream_copy_words(void *dst, const void *src, size_t nbytes, hipStream_t stream) {
     DREAM_REQUIRE(dst && src && nbytes % 4 == 0 && ((((size_t)dst) | ((size_t)src)) & 3) == 0, "copy_words: whole aligned 32-bit words expected");
     if (nbytes == 0) return 0;
-    hipLaunchKernelGGL(copy_words_kernel, dim3(grid_for(nbytes / 16 + 1)), dim3(256), 0, stream, (unsigned *)dst, (const unsigned *)src, nbytes / 4);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(copy_words_kernel, nbytes / 16 + 1, stream, (unsigned *)dst, (const unsigned *)src, nbytes / 4);
 }
 
 extern "C" int dream_copy_f32(float *dst, const float *src, size_t n, void *stream) {
@@ -1319,80 +1049,61 @@ extern "C" int dream_copy_f32(float *dst, const float *src, size_t n, void *stre
 extern "C" int dream_add_inplace_f32(float *dst, const float *src, size_t n, void *stream) {
     DREAM_REQUIRE(dst && src, "add_inplace: null pointer");
     DREAM_REQUIRE(aligned16(dst, src), "add_inplace: pointers must be 16-byte aligned (the kernel moves float4)");
-    hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(add_inplace_kernel, n / 4 + 1, stream, dst, src, n);
 }
 extern "C" int dream_add_f32(const float *a, const float *b, float *out, size_t n, unsigned *amax_out, void *stream) {
     DREAM_REQUIRE(a && b && out, "add: null pointer");
     DREAM_REQUIRE(aligned16(a, b, out), "add: pointers must be 16-byte aligned (the kernel moves float4)");
     if (amax_out && dream_zero_words(amax_out, sizeof(unsigned), (hipStream_t)stream)) return 2;
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, amax_out);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(add_kernel<f32x4>, n / 4 + 1, stream, a, b, out, n, amax_out);
 }
 extern "C" int dream_add_f16(const void *a, const void *b, void *out, size_t n, unsigned *amax_out, void *stream) {
     DREAM_REQUIRE(a && b && out, "add_f16: null pointer");
     DREAM_REQUIRE(aligned16(a, b, out), "add_f16: pointers must be 16-byte aligned (the kernel moves 8 halfs)");
-    hipLaunchKernelGGL(add_f16_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16 *)a, (const _Float16 *)b, (_Float16 *)out, n, amax_out);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(add_kernel<f16x8>, n / 8 + 1, stream, (const _Float16 *)a, (const _Float16 *)b, (_Float16 *)out, n, amax_out);
 }
 extern "C" int dream_stage_input_nhwc_f32(const float *img_nchw, const float *maps_nchw, float *out_nhwc, int B, int H, int W,
                                           int Ci, int K, int up, int Cpad, unsigned *amax_out, void *stream) {
     DREAM_REQUIRE(img_nchw && maps_nchw && out_nhwc && B > 0 && H > 0 && W > 0 && Ci > 0 && K > 0, "stage_input: bad arguments");
     DREAM_REQUIRE(up >= 1 && H % up == 0 && W % up == 0 && Cpad % 4 == 0 && Cpad >= Ci + K, "stage_input: bad up / Cpad");
     if (amax_out && dream_zero_words(amax_out, sizeof(unsigned), (hipStream_t)stream)) return 2;
-    hipLaunchKernelGGL(stage_input_kernel, dim3(grid_for((size_t)B * H * W * (Cpad / 4))), dim3(256), 0, (hipStream_t)stream,
-                       img_nchw, maps_nchw, out_nhwc, B, H, W, Ci, K, up, Cpad, amax_out);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(stage_input_kernel, (size_t)B * H * W * (Cpad / 4), stream, img_nchw, maps_nchw, out_nhwc, B, H, W, Ci, K, up, Cpad,
+                         amax_out);
 }
 extern "C" int dream_stage_input_bwd_f32(const float *g_nhwc, float *dmaps_nchw, int B, int H, int W, int Ci, int K, int up,
                                          int Cpad, int accumulate, void *stream) {
     DREAM_REQUIRE(g_nhwc && dmaps_nchw && B > 0 && H > 0 && W > 0 && Ci > 0 && K > 0, "stage_input_bwd: bad arguments");
     DREAM_REQUIRE(up >= 1 && H % up == 0 && W % up == 0 && Cpad >= Ci + K, "stage_input_bwd: bad up / Cpad");
-    hipLaunchKernelGGL(stage_input_bwd_kernel, dim3(grid_for((size_t)B * K * (H / up) * (W / up))), dim3(256), 0,
-                       (hipStream_t)stream, g_nhwc, dmaps_nchw, B, H, W, Ci, K, up, Cpad, accumulate);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(stage_input_bwd_kernel, (size_t)B * K * (H / up) * (W / up), stream, g_nhwc, dmaps_nchw, B, H, W, Ci, K, up, Cpad,
+                         accumulate);
 }
 extern "C" size_t dream_loss_workspace(size_t n) { return (size_t)grid_for(n) * sizeof(double); }
+// both losses: per-workgroup partial sums of `kernel` into the workspace, then their fixed-order sum
+template <typename K>
+static int loss_fwd_bwd(K kernel, const float *out, const float *target, float *grad, float *loss_sum, void *workspace, size_t n, float scale,
+                        void *stream) {
+    const unsigned nb = grid_for(n);
+    if (const int failed = launch_grid(kernel, dim3(nb), stream, out, target, grad, (double *)workspace, n, scale)) return failed;
+    return launch_grid(loss_finalize_kernel, dim3(1), stream, (const double *)workspace, (int)nb, loss_sum);
+}
 extern "C" int dream_mse_fwd_bwd_f32(const float *out, const float *target, float *grad, float *loss_sum, void *workspace,
                                      size_t n, double n_total, void *stream) {
     DREAM_REQUIRE(out && target && loss_sum && workspace && n > 0 && n_total > 0, "mse: bad arguments");
-    const unsigned nb = grid_for(n);
-    hipLaunchKernelGGL(mse_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, out, target, grad, (double *)workspace,
-                       n, (float)(2.0 / n_total));
-    DREAM_LAUNCH_OK();
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, (int)nb, loss_sum);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return loss_fwd_bwd(mse_kernel, out, target, grad, loss_sum, workspace, n, (float)(2.0 / n_total), stream);
 }
 extern "C" int dream_smoothl1_fwd_bwd_f32(const float *out, const float *target, float *grad, float *loss_sum, void *workspace,
                                           size_t n, double n_total, void *stream) {
     DREAM_REQUIRE(out && target && loss_sum && workspace && n > 0 && n_total > 0, "smoothl1: bad arguments");
-    const unsigned nb = grid_for(n);
-    hipLaunchKernelGGL(smoothl1_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, out, target, grad, (double *)workspace,
-                       n, (float)(1.0 / n_total));
-    DREAM_LAUNCH_OK();
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, (int)nb, loss_sum);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return loss_fwd_bwd(smoothl1_kernel, out, target, grad, loss_sum, workspace, n, (float)(1.0 / n_total), stream);
 }
 extern "C" int dream_adam_step_f32(float *p, const float *g, float *m, float *v, size_t n, float lr, double beta1,
                                    double beta2, float eps, int step, void *stream) {
     DREAM_REQUIRE(p && g && m && v && step >= 1, "adam: bad arguments");
     const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(adam_kernel, n, stream, p, g, m, v, n, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2,
+                         (float)(1.0 - beta2), eps);
 }
 extern "C" int dream_sgd_step_f32(float *p, const float *g, size_t n, float lr, void *stream) {
     DREAM_REQUIRE(p && g, "sgd: null pointer");
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, n, lr);
-    DREAM_LAUNCH_OK();
-    return 0;
+    return launch_stream(sgd_kernel, n, stream, p, g, n, lr);
 }

@@ -333,6 +333,7 @@ CASES = [
     ("conv1x1", _case(pc.check_conv1x1, 2, 5, 7, 64, 36)),
     ("first_conv", _case(pc.check_first_conv, 2, 5, 7)),
     ("pool_and_layouts", pc.check_pool_and_layouts),
+    ("streaming_forms", pc.check_streaming_forms),
     ("softargmax", pc.check_softargmax),
     ("conv_f16x3", _case(pc.check_conv_f16x3, 2, 5, 7, 32, 7, 3, RELU)),
     ("conv_transpose4x4", _case(pc.check_conv_transpose4x4, 1, 3, 5, 64, 32)),

@@ -476,6 +476,59 @@ def check_pool_and_layouts(dev):
     assert float(pk[:, 40:].abs().max()) == 0.0 and float(pk[:, :, 24:].abs().max()) == 0.0
 
 
+STREAMING_SHAPES = ((2, 5, 7, 8), (1, 2, 2, 8), (1, 3, 3, 4))
+
+
+def _pool2_bwd_ref(xf, dy, relu):
+    """torch's own backward of max_pool2d(2) (relu: of max_pool2d(relu(x))) on the CPU; NHWC in, NHWC out."""
+    x = xf.permute(0, 3, 1, 2).clone().requires_grad_()
+    F.max_pool2d(F.relu(x) if relu else x, 2).backward(dy.permute(0, 3, 1, 2))
+    return x.grad.permute(0, 2, 3, 1)
+
+
+def check_streaming_forms(dev):
+    """Every storage form of max-pool 2x2 (forward; backward with and without the ReLU mask) and of max-pool 3x3/s2 against torch on the
+    CPU -- F.max_pool2d and its autograd on the widened input, in fp32 --, bit for bit: a copy, a maximum and a zero are exact in every
+    form.  The forms of an operation are instantiations of one kernel template, so a half form that equals the fp32 form on the widened
+    input says nothing about the body they share; this check does.  Shapes, the smallest at which a lane count or a leftover can go
+    wrong: two frames with both extents odd and exactly one f16x8 vector (two f32x4) of channels; one window; four channels (no
+    multiple of 8: the fp32 and x16 forms only)."""
+    g = torch.Generator().manual_seed(3)
+    for shape in STREAMING_SHAPES:
+        b, h, w, c = shape
+        ho, wo = h // 2, w // 2
+        xh = torch.randn(shape, generator=g).relu().half()          # exact zeros: all-zero windows and ties at 0
+        xh[0, 0, 1, :] = xh[0, 0, 0, :]                             # ties at a positive maximum: the first in scan order wins
+        xh[0, 1, 0, : c // 2] = xh[0, 0, 0, : c // 2]
+        xf = xh.float()
+        dy = torch.randn(b, ho, wo, c, generator=g)
+        dyh = dy.half()
+        win = xf[:, :2 * ho, :2 * wo].reshape(b, ho, 2, wo, 2, c).permute(0, 1, 3, 5, 2, 4).reshape(b, ho, wo, c, 4)
+        top = win.max(-1).values
+        assert int((((win == top[..., None]).sum(-1) > 1) & (top > 0)).sum()) > 0, shape        # the input really holds positive ties
+        assert int((top == 0).sum()) > 0, shape                                                 # ... and all-zero windows
+        halfs = c % 8 == 0
+        want = F.max_pool2d(xf.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+        assert torch.equal(ops.maxpool2(to(dev, xf)).cpu(), want), shape
+        if halfs:
+            y = ops.maxpool2_f16(to(dev, xh)).cpu()
+            assert y.dtype == torch.float16 and torch.equal(y.float(), want), shape
+        want = F.max_pool2d(xf.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+        assert torch.equal(ops.maxpool3s2(to(dev, xf)).cpu(), want), shape
+        if halfs:
+            y = ops.maxpool3s2_f16(to(dev, xh)).cpu()
+            assert y.dtype == torch.float16 and torch.equal(y.float(), want), shape
+        for relu in (False, True):
+            want = _pool2_bwd_ref(xf, dy, relu)
+            dx = ops.maxpool2_bwd(to(dev, dy), to(dev, xf), relu=relu).cpu()
+            assert dx.dtype == torch.float32 and torch.equal(dx, want), (shape, relu)
+            dx = ops.maxpool2_bwd_x16(to(dev, dy), to(dev, xh), relu=relu).cpu()
+            assert dx.dtype == torch.float32 and torch.equal(dx, want), (shape, relu)
+            if halfs:
+                dx = ops.maxpool2_bwd_x16_dy16(to(dev, dyh), to(dev, xh), relu=relu).cpu()
+                assert dx.dtype == torch.float16 and torch.equal(dx.float(), _pool2_bwd_ref(xf, dyh.float(), relu)), (shape, relu)
+
+
 def peak_golden():
     return np.load(os.path.join(GOLD, "peaks_golden.npz"))
 

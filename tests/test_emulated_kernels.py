@@ -179,6 +179,10 @@ def test_first_conv_pool_layouts(emu):
     pc.check_pool_and_layouts("cpu")
 
 
+def test_streaming_forms(emu):
+    pc.check_streaming_forms("cpu")
+
+
 @pytest.mark.parametrize("name", [n for n, (m, _) in cases.peak_cases().items() if m.shape[1] * m.shape[2] <= 50000])
 def test_peaks_bit_exact(emu, name):
     pc.check_peaks_case("cpu", name)

@@ -71,6 +71,10 @@ def test_first_conv_pool_layouts():
     pc.check_pool_and_layouts(DEV)
 
 
+def test_streaming_forms():
+    pc.check_streaming_forms(DEV)
+
+
 @pytest.mark.parametrize("name", sorted(cases.peak_cases().keys()))
 def test_peaks_bit_exact(name):
     pc.check_peaks_case(DEV, name)
