@@ -88,6 +88,10 @@ _SIGNATURES = {
     "dream_convT4x4_wgrad_f16_splitk": (_I, [_I] * 6),
     "dream_convT4x4_wgrad_f16_workspace": (_SZ, [_I] * 6),
     "dream_convT4x4_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dream_upsample_conv3x3_wgrad_f16_splitk": (_I, [_I] * 5),
+    "dream_upsample_conv3x3_wgrad_f16_workspace": (_SZ, [_I] * 5),
+    "dream_upsample_conv3x3_wgrad_f16_fold": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dream_upsample_conv3x3_wgrad_f16_nhwc_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dream_maxpool3s2_idx_bwd_nhwc_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

@@ -135,117 +135,51 @@ struct WgradT4Params {
 };
 
 __global__ void __launch_bounds__(256, 2) wgrad_convT4_f16_kernel(const WgradT4Params p) {
-    DREAM_DYNAMIC_LDS(_Float16, smem);
-    _Float16 *sY = smem;                  // [RW][SY]      x, transposed: [ci][position]
-    _Float16 *sX = smem + RW * SY;        // [2][CW][SXT]  the phase's dz patch, transposed, shifted by dx = 0 | 1
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
-    const int wo = wave >> 1, wi = wave & 1;
-    const int li = lane & 31, lh = lane >> 5;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int nblk = p.nrb * p.ncb * 4;
-    const int blk = slot % nblk, ks = (slot / nblk) * 8 + xcd;
-    if (ks >= p.splitk) return;
-    const int ph = blk & 3, pa = ph >> 1, pb = ph & 1;
-    const int rbk = (blk >> 2) % p.nrb, cbk = (blk >> 2) / p.nrb;
-    const int ci0 = rbk * RW, co0 = cbk * CW;
-    const float sg = pow2f(scale_exponent(*p.amax_dz));
+    constexpr bool XS = false;
+    const unsigned *const amax_x = nullptr;          // (not read)
+#include "wgrad_convT4_f16_body.inc"
+}
 
-    f32x16 acc[4];
+// ---- DreamHourglass's train_upsample_precision="fp16" (DESIGN.md 4.8o): the weight gradient of nn.Upsample(2) + Conv2d(3x3) as that of the
+// equivalent ConvTranspose2d(k4,s2,p1).  The hourglass scales every operand by its tensor's amax (the input of upsample_0_3.4 is the output
+// of a conv without a ReLU), so x is staged as half(x * 2^e_x), e_x = scale_exponent(amax_x): the rounding the forward applied, no clamp.
+// A kernel of its own from the same text, so that the one above stays instruction-identical.
+__global__ void __launch_bounds__(256, 2) wgrad_convT4_f16_xs_kernel(const WgradT4Params p, const unsigned *amax_x) {
+    constexpr bool XS = true;
+#include "wgrad_convT4_f16_body.inc"
+}
+
+// ... and its reduce, which also folds the 4x4 gradient back to the 3x3 one: per (co, ci) the sixteen tap slots of part[ks][4 ky + kx][ci][co]
+// are summed over the slices in slice order, then dw3[r][c] = sum over ky in K(r), kx in K(c) of dwT[ky][kx], K(0) = {2,3}, K(1) = {1,2},
+// K(2) = {0,1} (the adjoint of dream_upsample_conv3x3_weight_as_convT4x4; wgrad_wino.hip's convT4x4_grad_to_conv3x3_kernel), the four
+// slots added in ascending (ky, kx); times 2^-ex * 2^-eg once (two exact steps; a null amax: factor 1) -> OIHW [Cdz][Cin][3][3].  A fixed
+// order throughout: two runs give the same bits.  Lanes run along co (the contiguous index of the partials).
+__global__ void __launch_bounds__(256) wgrad_convT4_fold3x3_reduce_kernel(const float *part, float *dw, int splitk, int Cin, int Cdz, int RowsPad,
+                                                                          const unsigned *amax_x, const unsigned *amax_dz) {
+    const float ix = amax_x ? pow2f(-scale_exponent(*amax_x)) : 1.0f, ig = amax_dz ? pow2f(-scale_exponent(*amax_dz)) : 1.0f;
+    const size_t n = (size_t)Cin * Cdz, slot_stride = (size_t)RowsPad * Cdz;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int ci = (int)(i / (size_t)Cdz), co = (int)(i - (size_t)ci * Cdz);
+        const float *src = part + (size_t)ci * Cdz + co;
+        float v[16];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+        for (int k = 0; k < 16; ++k) v[k] = 0.0f;
+        for (int ks = 0; ks < splitk; ++ks) {
+            float t[16];                             // sixteen independent loads in flight, added in slice order
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-
-    const int q = tid & 15;                          // channel quad of the staging
-    const int grp = tid >> 4;                        // x staging: the 8 positions (ty = grp >> 1, tx = 8 * (grp & 1) ..)
-    const bool x_chan_ok = ci0 + q * 4 < p.Cin;      // channel counts are multiples of 4
-    const bool g_chan_ok = co0 + q * 4 < p.Cdz;
-    const int Ho = 2 * p.H, Wo = 2 * p.W;
-
-    for (int tile = ks; tile < p.tiles_total; tile += p.splitk) {
-        int t = tile;
-        const int tix = t % p.tiles_x;
-        t /= p.tiles_x;
-        const int tiy = t % p.tiles_y;
-        const int b = t / p.tiles_y;
-        const int y0 = tiy * TH, x0 = tix * TW;
-        const float *xb = p.x + (size_t)b * p.H * p.W * p.Cin + ci0 + q * 4;
-        const float *gb = p.dz + (size_t)b * Ho * Wo * p.Cdz + co0 + q * 4;
-
-        __syncthreads();                             // previous tile fully consumed
-        // ---- x: 8 consecutive positions x 4 channels per thread (loads from clamped, always-legal addresses + a select) --------------
-        {
-            const int oy = y0 + (grp >> 1), ox0 = x0 + (grp & 1) * 8;
-            f32x4 v[8];
+            for (int k = 0; k < 16; ++k) t[k] = src[((size_t)ks * 16 + k) * slot_stride];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool ok = x_chan_ok && oy < p.H && ox0 + j < p.W;
-                v[j] = *(const f32x4 *)(ok ? xb + ((size_t)oy * p.W + ox0 + j) * p.Cin : p.x);
-                v[j] = ok ? v[j] : zero4;
+            for (int k = 0; k < 16; ++k) v[k] += t[k];
+        }
+        float *o = dw + ((size_t)co * Cin + ci) * 9;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int ky = 2 - r, kx = 2 - c;               // K(r) = {2 - r, 3 - r}
+                const float s = ((v[4 * ky + kx] + v[4 * ky + kx + 1]) + v[4 * ky + 4 + kx]) + v[4 * ky + 4 + kx + 1];
+                o[3 * r + c] = (s * ix) * ig;
             }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                f16x8 h;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) h[j] = (_Float16)fminf(fmaxf(v[j][c], -65504.0f), 65504.0f);      // the one rounding of x
-                *(f16x8 *)(sY + (q * 4 + c) * SY + grp * 8) = h;
-            }
-        }
-        // ---- dz: 9 positions of a patch row of the phase (position stride 2) x 4 channels per unit; two shifted copies ---------------
-        for (int u = tid >> 4; u < TPH * 2; u += 16) {
-            const int py = u >> 1, half = u & 1;
-            const int gu = y0 - pa + py, gv0 = x0 - pb + half * 8;
-            f16x4 h[9];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const bool ok = g_chan_ok && gu >= 0 && gu < p.H && gv0 + j >= 0 && gv0 + j < p.W;
-                f32x4 v = *(const f32x4 *)(ok ? gb + ((size_t)(2 * gu + pa) * Wo + 2 * (gv0 + j) + pb) * p.Cdz : p.dz);
-                v = ok ? v : zero4;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) h[j][c] = (_Float16)(v[c] * sg);      // the one rounding of dz
-            }
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    f16x8 piece;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) piece[j] = h[j + dx][c];
-                    *(f16x8 *)(sX + (dx * CW + q * 4 + c) * SXT + py * TW + half * 8) = piece;
-                }
-        }
-        __syncthreads();
-
-        // ---- k-steps: one tile row (16 positions) each; patch row s + dy serves tap row dy -------------------------------------------
-        const _Float16 *aY = sY + (wo * 32 + li) * SY + lh * 8;
-        const _Float16 *bX = sX + (wi * 32 + li) * SXT + lh * 8;
-        f16x8 row[2][2];                             // [patch row % 2][shift]
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) row[0][dx] = *(const f16x8 *)(bX + dx * CW * SXT);
-#pragma unroll
-        for (int s = 0; s < TH; ++s) {
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) row[(s + 1) % 2][dx] = *(const f16x8 *)(bX + dx * CW * SXT + (s + 1) * TW);
-            const f16x8 a = *(const f16x8 *)(aY + s * TW);
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) acc[dy * 2 + dx] = mfma_f32_32x32x16_f16(a, row[(s + dy) % 2][dx], acc[dy * 2 + dx]);
-        }
-    }
-
-    // ---- partials (still in the scaled domain): tap (dy, dx) of this phase is slice 4 (2 dy + 1 - a) + 2 dx + 1 - b ---------------------
-#pragma unroll
-    for (int tp = 0; tp < 4; ++tp) {
-        const int slice = 4 * (2 * (tp >> 1) + 1 - pa) + 2 * (tp & 1) + 1 - pb;
-        float *part = p.part + ((size_t)ks * 16 + slice) * p.RowsPad * p.Cdz;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = ci0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int i = co0 + wi * 32 + li;
-            if (o < p.RowsPad && i < p.Cdz) part[(size_t)o * p.Cdz + i] = acc[tp][r];
-        }
     }
 }
 
@@ -413,4 +347,61 @@ extern "C" int dream_convT4x4_wgrad_f16_nhwc_f32(const float *x, const float *dz
                        (hipStream_t)stream, (const float *)p.part, dw_packed, n, p.splitk, (const unsigned *)nullptr, amax_dz);
     DREAM_LAUNCH_OK();
     return 0;
+}
+
+// ---- the weight gradient of nn.Upsample(2) + Conv2d(3x3) on the fp16 matrix cores (DreamHourglass's train_upsample_precision="fp16"; replaces
+// ATen's conv backward-weight reached from loss.backward() for the upsample convs of dream/models.py:688-733) -------------------------------
+// H x W: the low-resolution input of the upsample.  The contraction is that of the equivalent ConvTranspose2d(k4,s2,p1): split and workspace
+// are the convT4 launch's, with the rows padded to whole 64-channel tiles here.
+extern "C" int dream_upsample_conv3x3_wgrad_f16_splitk(int B, int H, int W, int Cin, int Cdz) {
+    return dream_convT4x4_wgrad_f16_splitk(B, H, W, Cin, Cdz, Cin > 0 ? ceil_div(Cin, 64) * 64 : 0);
+}
+
+extern "C" size_t dream_upsample_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin, int Cdz) {
+    return dream_convT4x4_wgrad_f16_workspace(B, H, W, Cin, Cdz, Cin > 0 ? ceil_div(Cin, 64) * 64 : 0);
+}
+
+// The reduce of that launch on its own: part [splitk][16][RowsPad][Cdz] (slot 4 ky + kx of the 4x4 gradient, scaled domain) -> dw_oihw
+// [Cdz][Cin][3][3] = 2^-(ex+eg) * fold(sum over the slices); amax_x / amax_dz may be null (factor 1).
+extern "C" int dream_upsample_conv3x3_wgrad_f16_fold(const float *part, const unsigned *amax_x, const unsigned *amax_dz, float *dw_oihw,
+                                                     int splitk, int Cin, int Cdz, int RowsPad, void *stream) {
+    DREAM_REQUIRE(part && dw_oihw, "upsample_conv3x3_wgrad_f16_fold: null pointer");
+    DREAM_REQUIRE(splitk > 0 && Cin > 0 && Cdz > 0 && RowsPad >= Cin, "upsample_conv3x3_wgrad_f16_fold: bad shape (split %d, Cin %d, Cdz %d, pad %d)",
+                  splitk, Cin, Cdz, RowsPad);
+    size_t grid = ((size_t)Cin * Cdz + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(wgrad_convT4_fold3x3_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, part, dw_oihw, splitk, Cin, Cdz,
+                       RowsPad, amax_x, amax_dz);
+    DREAM_LAUNCH_OK();
+    return 0;
+}
+
+// x [B,H,W,Cin] fp32 with H = Ho / 2, W = Wo / 2 (the input of the upsample), amax_x: device scalar, bit pattern of (an upper bound of) max|x|:
+// x is rounded as half(x 2^e_x), what the forward launch did; dz [B,Ho,Wo,Cdz] fp32 with its amax_dz likewise -> dw_oihw [Cdz][Cin][3][3], the
+// gradient of the 3x3 weight.  Cin % 32 == 0, Cdz % 4 == 0; x, dz, dw_oihw and the workspace (dream_upsample_conv3x3_wgrad_f16_workspace)
+// 16-byte aligned; flags 0.  Two launches, no atomics: two runs give the same bits.
+extern "C" int dream_upsample_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dz, const unsigned *amax_dz,
+                                                         float *dw_oihw, void *workspace, int B, int Ho, int Wo, int Cin, int Cdz, int flags,
+                                                         void *stream) {
+    DREAM_REQUIRE(flags == 0, "upsample_conv3x3_wgrad_f16: flags %d not supported", flags);
+    DREAM_REQUIRE(Ho >= 2 && Wo >= 2 && Ho % 2 == 0 && Wo % 2 == 0,
+                  "upsample_conv3x3_wgrad_f16: dz of %d x %d: the output of an upsample has even dimensions", Ho, Wo);
+    const int H = Ho / 2, W = Wo / 2, RowsPad = Cin > 0 ? ceil_div(Cin, 64) * 64 : 0;
+    DREAM_REQUIRE(shape_ok_T4(B, H, W, Cin, Cdz, RowsPad), "upsample_conv3x3_wgrad_f16: bad shape (B %d, %d x %d, Cin %d, Cdz %d): Cin %% 32, Cdz %% 4",
+                  B, H, W, Cin, Cdz);
+    DREAM_REQUIRE((size_t)B * Ho * Wo * (size_t)(Cin > Cdz ? Cin : Cdz) < ((size_t)1 << 40), "upsample_conv3x3_wgrad_f16: tensor too large");
+    DREAM_REQUIRE(x && amax_x && dz && amax_dz && dw_oihw && workspace, "upsample_conv3x3_wgrad_f16: null pointer");
+    DREAM_REQUIRE((((size_t)x | (size_t)dz | (size_t)dw_oihw | (size_t)workspace) & 15) == 0, "upsample_conv3x3_wgrad_f16: pointers must be 16-byte aligned");
+    WgradT4Params p;
+    p.x = x; p.dz = dz; p.amax_dz = amax_dz; p.part = (float *)workspace;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cdz = Cdz; p.RowsPad = RowsPad;
+    p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH);
+    p.tiles_total = B * p.tiles_x * p.tiles_y;
+    p.splitk = plan_splitk_T4(B, H, W, Cdz, RowsPad);
+    p.nrb = ceil_div(RowsPad, RW); p.ncb = ceil_div(Cdz, CW);
+    if (dream_allow_full_lds((const void *)wgrad_convT4_f16_xs_kernel)) return 2;
+    const dim3 grid((unsigned)(p.nrb * p.ncb * 4 * ceil_div(p.splitk, 8) * 8));
+    hipLaunchKernelGGL(wgrad_convT4_f16_xs_kernel, grid, dim3(256), LDS_BYTES_T4, (hipStream_t)stream, p, amax_x);
+    DREAM_LAUNCH_OK();
+    return dream_upsample_conv3x3_wgrad_f16_fold(p.part, amax_x, amax_dz, dw_oihw, p.splitk, Cin, Cdz, RowsPad, stream);
 }

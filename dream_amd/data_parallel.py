@@ -423,7 +423,7 @@ class DreamDataParallel(nn.Module):
         BatchNorm running statistics by one small copy each, and only for evaluation (training uses batch statistics)."""
         for rep in self._replicas[:n - 1]:
             rep.train(self.module.training)
-            for attr in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "inference_head_fusion", "conv_ksplit", "train_precision", "train_gemm_precision", "train_decoder_precision", "train_activation_storage",
+            for attr in ("precision", "activation_storage", "inference_activation_storage", "inference_conv_ksplit", "inference_head_fusion", "conv_ksplit", "train_precision", "train_gemm_precision", "train_decoder_precision", "train_upsample_precision", "train_activation_storage",
                          "train_gradient_storage", "conv_algorithm", "conv1x1_algorithm", "convT_algorithm"):
                 if hasattr(self.module, attr) and getattr(rep, attr) != getattr(self.module, attr):
                     setattr(rep, attr, getattr(self.module, attr))
@@ -790,7 +790,7 @@ class DreamDataParallel(nn.Module):
             return self.module(x, *args, **kwargs)
         one = self.n_devices(x.shape[0]) == 1
         if one and self.single_device_graphs and self.module.training and torch.is_grad_enabled():
-            for name in ("train_precision", "train_gemm_precision", "train_decoder_precision"):
+            for name in ("train_precision", "train_gemm_precision", "train_decoder_precision", "train_upsample_precision"):
                 if getattr(self.module, name, "fp32") != "fp32":
                     raise ValueError("dream_amd: hip_graph_train (DREAM_TRAIN_GRAPH=1) does not replay %s=%r steps; switch one of "
                                      "them off" % (name, getattr(self.module, name)))

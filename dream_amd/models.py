@@ -67,14 +67,16 @@ _SWITCHES = (
     ("train_precision", ("fp32", "fp16"), (), "training", True),
     ("train_activation_storage", ("fp32", "fp16"), (("train_precision", "fp16"),), "training", False),
     ("train_gradient_storage", ("fp32", "fp16"), (("train_precision", "fp16"), ("train_activation_storage", "fp16")), "training", False),
+    ("train_upsample_precision", ("fp32", "fp16"), (("train_precision", "fp16"),), "training", False),
 )
 
 # What one walk of the plan does, resolved once from the switches (DreamHourglass._resolve_switches).  ``family``: the kernels of an
 # inference conv, "fp32" | "f16x3" | "f16"; ``act16`` / ``ksplit``: inference stores its activations as half / may split a small launch;
 # ``half_train``: the plain convs of a training pass run on the fp16 matrix cores; ``store16`` / ``grad16``: the plan indices whose
 # output / the gradient with respect to whose output a training pass stores as half; ``half_storage``: the walk writes the
-# half-storage peak scalar (half_storage_peak()).
-_Walk = collections.namedtuple("_Walk", "family act16 ksplit half_train store16 grad16 half_storage")
+# half-storage peak scalar (half_storage_peak()); ``ups16``: the convs behind an upsample (_half_ups_entry) of a training pass run on the
+# fp16 matrix cores as well.
+_Walk = collections.namedtuple("_Walk", "family act16 ksplit half_train store16 grad16 half_storage ups16")
 
 # ... and ResnetSimple's, in the order ResnetSimple._resolve_switches checks them: (attribute, allowed values, needs, the pass that reads
 # it).  An unknown value is refused in both passes; ``precision`` is not checked (None): a value outside _HALF_OPS takes the fp32 walk.
@@ -283,6 +285,12 @@ class DreamHourglass(nn.Module):
         # gradient is fp32.  Read once per training forward; inference ignores it.  See half_gradient_peak().
         self.train_gradient_storage = "fp32"
         self._gradient_peak = _PeakScalar("half_gradient_peak(): no backward with train_gradient_storage=\"fp16\" has run")
+        # Training with train_precision="fp16" only: "fp16" = the convs behind nn.Upsample(2) (_half_ups_entry: for vgg_q upsample_0_4.4 and
+        # upsample_0_3.4) run their three products on the fp16 matrix cores too, as the equivalent ConvTranspose2d(k4,s2,p1): forward
+        # conv_f16.hip's plain transposed form, data gradient its convT4 dgrad form, weight gradient wgrad_f16.hip's scaled-x form folded
+        # back to 3x3.  Tensors stay fp32 in HBM; operands are scaled by their tensor's amax.  "fp32" (default): those
+        # convs keep their fp32 launches.  Read once per training forward; inference ignores it.
+        self.train_upsample_precision = "fp32"
         # fp32 3x3 stride-1 convs: "winograd" = F(2x2,3x3) on the fp32 matrix cores wherever it is the faster exact-fp32
         # form (csrc/conv_wino.hip: 2.25x fewer MFMA cycles, same IEEE fp32 arithmetic up to round-off), "direct" = the
         # implicit-GEMM kernel everywhere (csrc/conv_mfma.hip, the reference form)
@@ -428,7 +436,7 @@ class DreamHourglass(nn.Module):
         if any(self._plan[li][0] == "pool" and li - 1 not in grad16 for li in grad16):
             raise ValueError("train_gradient_storage=\"fp16\": a max-pool directly behind the first conv is not built")
         return _Walk(_HALF_OPS.get(read["precision"], "fp32"), act16, read["conv_ksplit"] == "auto", read["train_precision"] == "fp16",
-                     store16, grad16, act16 or half_storage)
+                     store16, grad16, act16 or half_storage, read["train_upsample_precision"] == "fp16")
 
     @staticmethod
     def _half_train_entry(kind, mod, flags, in_channels):
@@ -437,6 +445,16 @@ class DreamHourglass(nn.Module):
         multiples of 32 (the "plain" convs: for vgg_q every VGG conv after the first, the decoder and head convs but the two upsample
         convs and the K-channel output conv)."""
         if kind != "conv" or flags & (CONV_UPSAMPLE2X | CONV_OUT_NCHW):
+            return False
+        cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
+        return int(in_channels) == cin and cin % 32 == 0 and cout % 32 == 0
+
+    @staticmethod
+    def _half_ups_entry(kind, mod, flags, in_channels):
+        """The rule of train_upsample_precision="fp16", one for the forward pass, the data gradient and the weight gradient: a 3x3 conv
+        that follows nn.Upsample(2) and does not write the NCHW output, whose input carries exactly cin channels, cin and cout multiples
+        of 32 (for vgg_q upsample_0_4.4 and upsample_0_3.4; with full_output upsample_0_2.2 and upsample_0_1.2 as well)."""
+        if kind != "conv" or not flags & CONV_UPSAMPLE2X or flags & CONV_OUT_NCHW:
             return False
         cout, cin = int(mod.weight.shape[0]), int(mod.weight.shape[1])
         return int(in_channels) == cin and cin % 32 == 0 and cout % 32 == 0
@@ -638,11 +656,12 @@ class DreamHourglass(nn.Module):
                     act = ops.nchw_to_nhwc(act, cpad=self.input_channel_pad())
                 w, bias = params[self._param_slot[li]], params[self._param_slot[li] + 1]
                 half_entry = walk.half_train and self._half_train_entry(kind, mod, flags, act.shape[3])
+                ups_entry = walk.ups16 and self._half_ups_entry(kind, mod, flags, act.shape[3])       # (fp32 in and out, always)
                 group, sub = self._group(layers, li, act, save, split, half_entry)
                 # the form of this entry: its kernels, and whether they work on a stored half (then no amax travels)
                 if save:
                     stored = (kind == "first" and li in store16) or (half_entry and act.dtype == torch.float16)
-                    family = "f16" if half_entry or stored else "fp32"
+                    family = "f16" if half_entry or ups_entry or stored else "fp32"
                 else:
                     family, stored = walk.family, act16
                 if group == "pair+pool":
@@ -656,7 +675,7 @@ class DreamHourglass(nn.Module):
                     if family == "fp32":
                         out, amax = self._conv_fp32(kind, mod, act, amax, w, bias, group_flags, skip)
                     else:
-                        if half_entry:
+                        if half_entry or ups_entry:
                             # what the backward needs: the amax of the fp32 input -- that of the launch that produced ``act`` where it is
                             # still that tensor's, one absmax pass otherwise -- or None: the stored half is the operand
                             if not stored and amax is None:
@@ -674,6 +693,15 @@ class DreamHourglass(nn.Module):
                     keep[li] = out
                 act, li = out, li + 1
         return act, saved
+
+    def _wgrad_fp32(self, inp, g, cout, cin, ups):
+        """The fp32 weight + bias gradient of a 3x3 conv entry (``ups``: behind nn.Upsample(2), ``inp`` its low-resolution input)."""
+        if (self.conv_algorithm == "winograd" and int(inp.shape[3]) == cin
+                and ops.wgrad_winograd_pays(int(g.shape[0]) * int(g.shape[1]) * int(g.shape[2]), cin, cout)
+                and (not ups or (cin % 64 == 0 and cout % 64 == 0 and g.shape[1] % 2 == 0 and g.shape[2] % 2 == 0))):
+            # 16/36 of the multiplications; the nearest x2 upsample in front of the conv is fused into the patch load
+            return ops.conv3x3_wgrad_winograd(inp, g, cout, cin, flags=CONV_UPSAMPLE2X if ups else 0)
+        return ops.conv3x3_wgrad(inp, g, cout, cin, ups)
 
     def run_backward(self, saved, grad_out_nchw, need_input_grad=False, reducer=None):
         """dL/d(belief maps) [B,K,Ho,Wo] -> list of parameter gradients in plan_parameters() order (and, for a
@@ -758,6 +786,21 @@ class DreamHourglass(nn.Module):
                     g_input = self._conv3x3(mod, 1, g)                         # [B,H,W,cin]
                 g = None
                 continue
+            if li in saved.half and flags & CONV_UPSAMPLE2X:
+                # train_upsample_precision="fp16": the forward ran this upsample conv as the equivalent 4x4 transposed conv on the fp16 matrix
+                # cores; so do both products of its backward.  x, dy and dx are fp32; dy is scaled by the amax it carries (the masked data
+                # gradient of the conv behind wrote it) or by one pass, which serves both products.  dx is at low resolution and carries no
+                # mask: the ReLU backward of the entry in front stays the element-wise pass.
+                x_amax = saved.half[li]
+                g_amax = g_amax if g_amax is not None else ops.absmax(g)
+                def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ax=x_amax, ag=g_amax):
+                    if ops.upsample_conv3x3_wgrad_f16_pays(int(inp.shape[0]), int(inp.shape[1]), int(inp.shape[2]), cin, cout):
+                        grads[pi], grads[pi + 1] = ops.upsample_conv3x3_wgrad_f16(inp, ax, g, ag, cout, cin)
+                    else:
+                        grads[pi], grads[pi + 1] = self._wgrad_fp32(inp, g, cout, cin, CONV_UPSAMPLE2X)
+                _on_side(side, leaf, inp, g, x_amax, g_amax)
+                g, g_amax = ops.conv_transpose4x4s2_dgrad_f16(g, g_amax, self._packed.get(mod.weight, "ups_f16b"), cin), None
+                continue
             if li in saved.half:
                 # the forward ran this entry on the fp16 matrix cores: both products of its backward run there too.  What varies is which
                 # of x (train_activation_storage: the forward left no amax), dy and dx (train_gradient_storage: half, times 2^e_g) are
@@ -776,13 +819,7 @@ class DreamHourglass(nn.Module):
                 continue
             g_amax = None
             def leaf(pi=pi, inp=inp, g=g, cout=cout, cin=cin, ups=flags & CONV_UPSAMPLE2X):
-                if (self.conv_algorithm == "winograd" and int(inp.shape[3]) == cin
-                        and ops.wgrad_winograd_pays(int(g.shape[0]) * int(g.shape[1]) * int(g.shape[2]), cin, cout)
-                        and (not ups or (cin % 64 == 0 and cout % 64 == 0 and g.shape[1] % 2 == 0 and g.shape[2] % 2 == 0))):
-                    # 16/36 of the multiplications; the nearest x2 upsample in front of the conv is fused into the patch load
-                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad_winograd(inp, g, cout, cin, flags=CONV_UPSAMPLE2X if ups else 0)
-                else:
-                    grads[pi], grads[pi + 1] = ops.conv3x3_wgrad(inp, g, cout, cin, ups)
+                grads[pi], grads[pi + 1] = self._wgrad_fp32(inp, g, cout, cin, ups)
             _on_side(side, leaf, inp, g)
             cols_pad = self._packed.get(mod.weight, "direct", 1)[3]
             if int(g.shape[3]) != cols_pad:
@@ -1281,6 +1318,15 @@ class DreamHourglassMultiStage(nn.Module):
             st.train_precision = value
 
     @property
+    def train_upsample_precision(self):
+        return self.stage1.train_upsample_precision
+
+    @train_upsample_precision.setter
+    def train_upsample_precision(self, value):
+        for st in self.stages():
+            st.train_upsample_precision = value
+
+    @property
     def conv_algorithm(self):
         return self.stage1.conv_algorithm
 
@@ -1618,6 +1664,7 @@ class ResnetSimple(nn.Module):
     activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "its half-stored inference is a switch of its own: inference_activation_storage")
     conv_ksplit = _FixedSwitch("off", "ResnetSimple does not split its convs", "its convs read and write fp32")
     train_gradient_storage = _FixedSwitch("fp32", "ResnetSimple stores its gradients in fp32 only", "ResnetSimple trains in fp32 only")
+    train_upsample_precision = _FixedSwitch("fp32", "ResnetSimple has no conv behind nn.Upsample(2)", "its decoder's half-precision training is train_decoder_precision")
     train_activation_storage = _FixedSwitch("fp32", _FP32_ACTIVATIONS, "ResnetSimple trains in fp32 only")
 
     def _read_switches(self):

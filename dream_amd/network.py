@@ -243,7 +243,7 @@ class DreamNetwork:
                 raise RuntimeError("dream_amd: hip_graph_train needs the model behind DreamDataParallel (what DreamNetwork builds); this "
                                    "network's model is a %s" % type(self.model).__name__)
             return
-        for name in ("train_precision", "train_gemm_precision", "train_decoder_precision"):
+        for name in ("train_precision", "train_gemm_precision", "train_decoder_precision", "train_upsample_precision"):
             if on and getattr(self.model.module, name, "fp32") != "fp32":
                 raise ValueError("dream_amd: hip_graph_train does not replay %s=%r steps; switch one of them off"
                                  % (name, getattr(self.model.module, name)))

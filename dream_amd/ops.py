@@ -1020,6 +1020,51 @@ def convT4x4_wgrad_f16(x_nhwc, dz_nhwc, amax_dz, flags=0):
     return dw
 
 
+# ---- DreamHourglass train_upsample_precision="fp16": the convs behind nn.Upsample(2) on the fp16 matrix cores --------------
+# forward: conv_transpose4x4s2_f16 on the "ups_f16" pack; data gradient: conv_transpose4x4s2_dgrad_f16 on the plane below; weight gradient:
+def pack_upsample_conv_dgrad_weight_f16(w_oihw):
+    """Conv2d(k3,p1) weight [Cout,Cin,3,3] applied after a nearest x2 upsample -> (hi, None, exp, cin): the 16-slice half plane
+    [4 ty + tx][rows_pad >= Cin][Cout] of the equivalent ConvTranspose2d(k4,s2,p1) weight (upsample_conv_weight) that
+    conv_transpose4x4s2_dgrad_f16 reads."""
+    return pack_convT4x4_dgrad_weight_f16(upsample_conv_weight(w_oihw))
+
+
+def upsample_conv3x3_wgrad_f16_splitk(b, h, w, cin, cout):
+    """Position slices the fp16 weight gradient of an upsample conv on a [b,h,w,cin] input is split into (a host computation)."""
+    return int(_hip.lib().dream_upsample_conv3x3_wgrad_f16_splitk(b, h, w, cin, cout))
+
+
+def upsample_conv3x3_wgrad_f16_pays(b, h, w, cin, cout):
+    """Does the fp16 weight gradient of an upsample conv beat the fp32 launch on this problem ([b,h,w,cin] the low-resolution input)?
+    Every measured launch does (profiles/microbench_train_upsample_precision.txt): nothing is sent back to fp32."""
+    return True
+
+
+def upsample_conv3x3_wgrad_f16(x_nhwc, amax_x, dz_nhwc, amax_dz, cout, cin, flags=0):
+    """Weight + bias gradient of nn.Upsample(2) + Conv2d(3x3) on the fp16 matrix cores (csrc/wgrad_f16.hip): x [B,H,W,cin] the input of the
+    upsample, rounded as fp16(x 2^e_x) from ``amax_x`` (what the forward did), dz [B,2H,2W,cout] as fp16(dz 2^e_g) from ``amax_dz``; the
+    contraction of the equivalent 4x4 transposed conv, split over position tiles, summed in a fixed order and folded to the 3x3 weight
+    (two runs give the same bits) -> (dW OIHW [cout,cin,3,3], dbias [cout] = the fp32 channel sum of the unrounded dz)."""
+    x, dz = _f32(x_nhwc), _f32(dz_nhwc)
+    b, h, w = (int(v) for v in x.shape[:3])
+    if int(x.shape[3]) != cin or tuple(int(v) for v in dz.shape) != (b, 2 * h, 2 * w, cout):
+        raise RuntimeError("upsample_conv3x3_wgrad_f16: dz %s does not go with x %s, %d -> %d channels" % (tuple(dz.shape), tuple(x.shape), cin, cout))
+    ws = _workspace(_hip.lib().dream_upsample_conv3x3_wgrad_f16_workspace(b, h, w, cin, cout), x.device)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    call("dream_upsample_conv3x3_wgrad_f16_nhwc_f32", ptr(x), ptr(amax_x), ptr(dz), ptr(amax_dz), ptr(dw), ptr(ws), b, 2 * h, 2 * w, cin, cout,
+         flags, stream())
+    return dw, channel_sum(dz)
+
+
+def upsample_conv3x3_wgrad_f16_fold(part, amax_x, amax_dz, cout, cin):
+    """The reduce of that launch on its own: part [splitk][16][rows_pad][cout] -> dW OIHW [cout,cin,3,3] (null amax: factor 1)."""
+    part = _f32(part)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=part.device)
+    call("dream_upsample_conv3x3_wgrad_f16_fold", ptr(part), ptr(amax_x), ptr(amax_dz), ptr(dw), int(part.shape[0]), cin, cout,
+         int(part.shape[2]), stream())
+    return dw
+
+
 def conv_transpose4x4s2(x_nhwc, packed, cout, scale=None, shift=None, flags=0, direct_taps=16):
     """direct_taps: multiply-adds per (input pixel, cin, cout) of the direct algorithm this launch stands for -- 16 for a
     4x4 transposed conv, 36 when it replaces upsample + conv3x3; only used by bench.py's FLOP accounting."""

@@ -59,6 +59,8 @@ class _PackedCache:
             return ops.pack_conv_weight_f16(w, direction)
         if form == "ups_f16":
             return ops.pack_convT4x4_weight_f16(ops.upsample_conv_weight(w))
+        if form == "ups_f16b":                    # ... and the 16-slice plane its data gradient reads (train_upsample_precision="fp16")
+            return ops.pack_upsample_conv_dgrad_weight_f16(w)
         raise ValueError("unknown packed form %r" % (form,))
 
 

@@ -853,6 +853,23 @@ int dream_convT4x4_wgrad_f16_splitk(int B, int H, int W, int Cin, int Cdz, int R
 size_t dream_convT4x4_wgrad_f16_workspace(int B, int H, int W, int Cin, int Cdz, int RowsPad);
 int dream_convT4x4_wgrad_f16_nhwc_f32(const float *x, const float *dz, const unsigned *amax_dz, float *dw_packed, void *workspace, int B,
                                       int Ho, int Wo, int Cin, int Cdz, int RowsPad, int flags, void *stream);
+/* DreamHourglass train_upsample_precision="fp16": the weight gradient of nn.Upsample(2) + Conv2d(3x3) as that of the equivalent
+ * ConvTranspose2d(k4,s2,p1), folded back to the 3x3 weight.  x [B,Ho/2,Wo/2,Cin] (the input of the upsample), amax_x: device scalar, bit
+ * pattern of (an upper bound of) max|x| -- x is rounded as fp16(x 2^ex), no clamp; dz [B,Ho,Wo,Cdz] and amax_dz likewise ->
+ * dw_oihw [Cdz][Cin][3][3]:
+ *   dwT[ci,co,ky,kx] = sum_{b,i,j} fp16(x 2^ex)[b,i,j,ci] * fp16(dz 2^eg)[b,2i+ky-1,2j+kx-1,co]
+ *   dW[co,ci,r,c] = 2^-(ex+eg) sum_{ky in K(r), kx in K(c)} dwT[ci,co,ky,kx],   K(0) = {2,3}, K(1) = {1,2}, K(2) = {0,1}.
+ * Cin % 32 == 0, Cdz % 4 == 0, Ho and Wo even, pointers 16-byte aligned, flags 0.  Split over position tiles of the low-resolution map
+ * (.._splitk(B, Ho/2, Wo/2, Cin, Cdz) slices: a host computation, 0 for a refused shape) into `workspace` (.._workspace() bytes);
+ * .._fold is the second launch on its own: part [splitk][16][RowsPad][Cdz], slot 4 ky + kx, summed in slice order, the four slots of a
+ * 3x3 tap in ascending (ky, kx), scaled once (a null amax: factor 1).  No atomics: two runs give the same bits.  The bias gradient stays
+ * dream_channel_sum_nhwc_f32(dz). */
+int dream_upsample_conv3x3_wgrad_f16_splitk(int B, int H, int W, int Cin, int Cdz);
+size_t dream_upsample_conv3x3_wgrad_f16_workspace(int B, int H, int W, int Cin, int Cdz);
+int dream_upsample_conv3x3_wgrad_f16_fold(const float *part, const unsigned *amax_x, const unsigned *amax_dz, float *dw_oihw, int splitk,
+                                          int Cin, int Cdz, int RowsPad, void *stream);
+int dream_upsample_conv3x3_wgrad_f16_nhwc_f32(const float *x, const unsigned *amax_x, const float *dz, const unsigned *amax_dz, float *dw_oihw,
+                                              void *workspace, int B, int Ho, int Wo, int Cin, int Cdz, int flags, void *stream);
 /* the same pool for training: also stores which element of its 3x3 window won (uint8 0..8 = 3 dy + dx, the first maximum in scan
  * order: ATen's max_pool2d_with_indices), so that the backward pass compares one byte per window instead of recomputing nine-way
  * arg-maxima; idx: [B,Ho,Wo,C] bytes */
